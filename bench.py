@@ -2,6 +2,7 @@
 """Throughput of the hot path on MI355X: grid-point-steps/s of the fused five-field RK integrators.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rk4_single|sweep_rk45|rk45_single|dd_rk45] ...
+                    [--full] [--dump-outputs DIR]     (DIR: e.g. bench_outputs/, which git ignores)
 
 Default (N=1): BASELINE.json's headline - ONE grid of 2^20 depth cells, fixed-step classical RK4, fp64,
 fused HIP stencil (configs[1] at the size the north_star quotes its target on).  A "step" is one RK4
@@ -13,17 +14,26 @@ the GPU and waits for them.  Rank r binds cuda:LOCAL_RANK and joins an RCCL ("nc
 headline line is the same workload on every rank (each rank integrates its own grid: weak scaling, no
 data-path collective); BASELINE configs[2]/[3] (the batched sweep, 4096 instances per GPU, no collective) and
 configs[4] (ONE grid of 2^22 cells domain-decomposed over all ranks, RCCL all-gather per attempt) are timed
-afterwards and reported under `extra`, best effort and under a deadline (a failure or hang there cannot take
+afterwards with --full and reported under `extra`, best effort and under a deadline (a failure or hang there cannot take
 the headline line with it).
 
 Timing: W untimed warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier +
-torch.cuda.synchronize() on both sides; the block is repeated until >= 50 ms have been timed and the MEDIAN
-block (max over ranks per block) is reported (`reps`), so that a small K measures the kernel and not one
-launch/synchronise round trip.
+torch.cuda.synchronize() on both sides and each starting from the state the warm-up left; the block is
+repeated until >= 50 ms have been timed and the MEDIAN block (max over ranks per block) is reported (`reps`),
+so that a small K measures the kernel and not one launch/synchronise round trip.
 
 One JSON line is printed by rank 0 (contract in the task description); `roofline` is for the dominant
 kernel with HIP-event timing on the launch stream, `cpu_baseline` is the oracle (a C port of the
 reference's serial loop) timed on this host on a bounded sample of the same workload.
+
+A plain run measures the headline only: set-up, warm-up, the timed steps, the result line (`cpu_baseline` null, no
+`extra`).  --full adds what takes runs of its own: the CPU baseline and, for the default workload, the extras above.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed call left to its caller as DIR/<name>.npy
+(float64): `y` the state (field-major, [5, N]; the sweeps [instances, 5, N]), `stats` for the RK45 paths
+([t_reached, h_next, n_accepted, n_rejected, nfev] per instance).  Above 60 MiB in all, a fixed seeded sample of the
+cells (instances for the sweeps) is written instead, with its indices (`cells` / `instances`).  The inputs are
+deterministic, and every timed block starts from the same warmed-up state, so equal arguments give equal outputs.
 """
 import argparse
 import json
@@ -48,6 +58,9 @@ BYTES_PER_POINT_STEP = 80.0    # 5 fields x 8 B read + 5 x 8 B written per grid-
 MIN_TIMED_S = 0.05             # repeat the K-step block until this much has been timed
 MAX_REPS = 400
 EXTRAS_DEADLINE_S = float(os.environ.get("MARL_BENCH_EXTRAS_DEADLINE", "240"))
+SETTLE_MAX_STEPS = 4000        # rk4_single: the untimed settle call is as long as the timed call, up to this many steps
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: above this, a seeded sample of cells / instances is written
+DUMP_SEED = 20240601
 
 
 def parse_args(argv=None):
@@ -61,8 +74,10 @@ def parse_args(argv=None):
     ap.add_argument("--layout", type=int, default=1, help="device layout of single-grid runs: 0 field-major, 1 tiled")
     ap.add_argument("--variant", type=int, default=-1, help="kernel variant (see DESIGN.md); -1 = default")
     ap.add_argument("--no-reuse", action="store_true", help="rk4_single: every evaluation takes the full transcendental path")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline workload only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extras")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and the extras (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's outputs as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -100,6 +115,30 @@ def synthetic(p, N):
     x = (np.arange(N) + 0.5) * (L / N)
     y = np.stack([np.full(N, p[k]) for k in ("CAIni", "CCIni", "cCaIni", "cCO3Ini", "PhiIni")])
     return (y * (1.0 + 0.01 * np.sin(2 * np.pi * 8 * x / L))).ravel()
+
+
+def write_outputs(path, sampled, axis, index_name, whole=None):
+    """--dump-outputs: the arrays of `sampled` (which share `axis`) and of `whole` as path/<name>.npy, float64.  Beyond
+    DUMP_MAX_BYTES a fixed seeded sample along `axis` is written, and its sorted indices as path/<index_name>.npy."""
+    import numpy as np
+    whole = whole or {}
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in sampled.values()) + sum(a.nbytes for a in whole.values())
+    if total > DUMP_MAX_BYTES:
+        n = next(iter(sampled.values())).shape[axis]
+        per = sum(a.nbytes for a in sampled.values()) // n + 8       # bytes of one sampled slice + its index
+        k = max(1, (DUMP_MAX_BYTES - sum(a.nbytes for a in whole.values())) // per)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(k, n), replace=False))
+        sampled = {name: np.take(a, idx, axis=axis) for name, a in sampled.items()}
+        sampled[index_name] = idx
+    for name, a in (sampled | whole).items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def rk45_stats(results):
+    """[t_reached, h_next, n_accepted, n_rejected, nfev] per result, as the --dump-outputs `stats` array."""
+    import numpy as np
+    return np.array([[r.t_reached, r.h_next, r.n_accepted, r.n_rejected, r.nfev] for r in results], dtype=np.float64)
 
 
 def main():
@@ -160,14 +199,17 @@ def main():
 
     base = asdict(Map_Scenario())
 
-    def timed(fn_warm, fn_block, repeat=True):
+    def timed(fn_warm, fn_block, repeat=True, fn_reset=None):
         """Warm-up, then blocks of the timed region (fn_block enqueues EXACTLY K steps), each bracketed by barrier +
-        synchronize on both sides.  Returns (median over blocks of the max-over-ranks wall time [s], median HIP-event
-        time of this rank's blocks [ms], number of blocks)."""
+        synchronize on both sides and preceded by fn_reset (untimed: puts back the state the warm-up left, so that the
+        last block's result does not depend on how many blocks ran).  Returns (median over blocks of the max-over-ranks
+        wall time [s], median HIP-event time of this rank's blocks [ms], number of blocks)."""
         fn_warm()
 
         def one():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if fn_reset is not None:
+                fn_reset()
             barrier()
             e0.record(stream)
             t0 = time.perf_counter()
@@ -186,8 +228,17 @@ def main():
         walls = max_over_ranks([b[0] for b in blocks])
         return float(np.median(walls)), float(np.median([b[1] for b in blocks])), reps
 
+    def field_major(eq, buf, layout):
+        """--dump-outputs: the device state `buf` (in `layout`) as a host field-major array [5 * N]."""
+        if layout == 0:
+            return buf.cpu().numpy()
+        fm = torch.empty(eq.state_doubles(0), dtype=torch.float64, device="cuda")
+        eq.convert_layout_device(buf.data_ptr(), fm.data_ptr(), layout, 0)
+        torch.cuda.synchronize()
+        return fm.cpu().numpy()
+
     # ---- workloads ------------------------------------------------------------------------------------------
-    def run_rk4_single(N, steps, warmup, layout, variant, no_reuse=False):
+    def run_rk4_single(N, steps, warmup, layout, variant, no_reuse=False, outputs=None):
         p = base | {"N": N}
         eq = LMAHeureuxPorosityDiff.from_scenario(p, device=local_rank)
         eq.use_stream(stream.cuda_stream)
@@ -201,17 +252,24 @@ def main():
         dt = 0.25 * (eq.Depths.length / N) ** 2
         # untimed settle phase (~60 ms of the same kernel): the chip's clocks ramp for tens of ms after idle, and a short
         # --steps run would otherwise measure the ramp; then the W warm-up steps, then the blocks of K timed steps
-        # (as long as the timed call when that is longer: the streamed path is ONE launch per call, and a profile of this
-        # command should see launches of one length)
-        eq.integrate_rk4_device(buf.data_ptr(), dt, max(2000, steps), layout)
-        wall, ev_ms, reps = timed(lambda: eq.integrate_rk4_device(buf.data_ptr(), dt, warmup, layout),
-                                  lambda: eq.integrate_rk4_device(buf.data_ptr(), dt, steps, layout))
+        # (as long as the timed call when that is longer, up to SETTLE_MAX_STEPS: the streamed path is ONE launch per call,
+        # and a profile of this command should see launches of one length; a long --steps run needs no longer settle)
+        eq.integrate_rk4_device(buf.data_ptr(), dt, min(max(2000, steps), SETTLE_MAX_STEPS), layout)
+        warm = torch.empty_like(buf)
+
+        def warm_up():
+            eq.integrate_rk4_device(buf.data_ptr(), dt, warmup, layout)
+            warm.copy_(buf)
+        wall, ev_ms, reps = timed(warm_up, lambda: eq.integrate_rk4_device(buf.data_ptr(), dt, steps, layout),
+                                  fn_reset=lambda: buf.copy_(warm))
         eq.synchronize()   # (outside the timed region: surfaces a streamed run that gave up waiting - marl_synchronize)
         assert bool(torch.isfinite(buf).all()), "state went non-finite"
+        if outputs is not None:
+            outputs["y"] = field_major(eq, buf, layout).reshape(5, N)
         eq.close()
         return wall, ev_ms, reps
 
-    def run_sweep(N, B, steps, warmup, adaptive, variant=-1):
+    def run_sweep(N, B, steps, warmup, adaptive, variant=-1, outputs=None):
         # 16x16x16-style grid over the three knobs the reference's tests vary, B instances per GPU
         k = max(1, round(B ** (1 / 3)))
         idx = np.arange(B) + rank * B
@@ -245,10 +303,14 @@ def main():
             rej = np.array([r.n_rejected for r in stats["res"]])
             assert np.all(acc + rej == steps), "every instance must have spent its attempt budget"
             info = {"accepted_steps_mean": float(acc.mean()), "rejected_steps_mean": float(rej.mean())}
+        if outputs is not None:
+            outputs["y"] = buf.cpu().numpy().reshape(B, 5, N)
+            if adaptive:
+                outputs["stats"] = rk45_stats(stats["res"])
         eq.close()
         return wall, ev_ms, reps, info
 
-    def run_rk45_single(N, steps, warmup, layout, variant=-1):
+    def run_rk45_single(N, steps, warmup, layout, variant=-1, outputs=None):
         p = base | {"N": N}
         eq = LMAHeureuxPorosityDiff.from_scenario(p, device=local_rank)
         eq.use_stream(stream.cuda_stream)
@@ -267,10 +329,13 @@ def main():
             bufs.append(b)
         wall, ev_ms, reps = timed(lambda: go(warmup, bufs[0]), lambda: go(steps, bufs[1]), repeat=False)
         r = out["res"]
+        if outputs is not None:
+            outputs["y"] = field_major(eq, bufs[1], layout).reshape(5, N)
+            outputs["stats"] = rk45_stats([r])
         eq.close()
         return wall, ev_ms, reps, {"accepted_steps": r.n_accepted, "rejected_steps": r.n_rejected}
 
-    def run_dd(N, steps, warmup):
+    def run_dd(N, steps, warmup, outputs=None):
         """BASELINE configs[4]: ONE grid of N cells split over all ranks, halo strips + step-control records in one
         all-gather per attempt (RCCL)."""
         from marlpde_amd.domain import DomainDecomposedRK45, owned_slice
@@ -288,6 +353,9 @@ def main():
         wall, ev_ms, reps = timed(lambda: go(warmup, ys[0]), lambda: go(steps, ys[1]), repeat=False)
         st = out["st"]
         info = {"accepted_steps": int(st.n_accepted), "rejected_steps": int(st.n_rejected), "transport": dd.transport}
+        if outputs is not None:   # this rank's cells [begin, end) of the grid (all of it on one rank)
+            outputs["y"] = ys[1].cpu().numpy().reshape(5, dd.end - dd.begin)
+            outputs["stats"] = np.array([[st.t, st.h_next, st.n_accepted, st.n_rejected, st.nfev]], dtype=np.float64)
         dd.close()
         return wall, ev_ms, reps, info
 
@@ -298,14 +366,15 @@ def main():
     steps = args.steps if args.steps is not None else defaults[args.workload][0]
     warmup = args.warmup if args.warmup is not None else defaults[args.workload][1]
     extra = {}
+    outputs = {} if (args.dump_outputs and rank == 0) else None
     if args.workload == "dd_rk45":
-        wall, ev_ms, reps, info = run_dd(N, steps, warmup)
+        wall, ev_ms, reps, info = run_dd(N, steps, warmup, outputs)
         units = float(N) * steps / world       # per-rank share; `value` multiplies by world below
         workload = f"dd_rk45 ONE grid N={N} over {world} rank(s), halo exchange + all-gathered step control (BASELINE configs[4])"
         kernel, parallelism, scaling = "rk45_attempt_kernel", f"1-D domain decomposition over {world} rank(s); one all-gather (halo strips + step-control record) per attempted step", "strong"
         extra.update(info)
     elif args.workload == "rk4_single":
-        wall, ev_ms, reps = run_rk4_single(N, steps, warmup, args.layout, args.variant, args.no_reuse)
+        wall, ev_ms, reps = run_rk4_single(N, steps, warmup, args.layout, args.variant, args.no_reuse, outputs)
         units = float(N) * steps
         workload = (f"rk4_fused_single_grid N={N} fp64 (north_star target size 2^20; BASELINE configs[1] is the same kernel at "
                     f"N=65536, reported under extra), dt=0.25dx^2" + (", transcendental reuse disabled" if args.no_reuse else ""))
@@ -317,7 +386,7 @@ def main():
         kernel = "rk4_stream_kernel" if streamed else "rk4_fused_kernel"
         parallelism, scaling = f"{world} rank(s), each integrating its own grid; no collective in the data path", "weak"
     elif args.workload in ("sweep_rk45", "sweep_rk4"):
-        wall, ev_ms, reps, info = run_sweep(N, args.batch, steps, warmup, args.workload == "sweep_rk45", args.variant)
+        wall, ev_ms, reps, info = run_sweep(N, args.batch, steps, warmup, args.workload == "sweep_rk45", args.variant, outputs)
         units = float(N) * args.batch * steps
         workload = (f"{args.workload} batch={args.batch} instances/GPU x N={N}, one workgroup per instance "
                     f"(BASELINE configs[2]/[3]); steps = attempted steps")
@@ -325,16 +394,21 @@ def main():
         parallelism, scaling = f"instances sharded over {world} rank(s); no collective in the data path", "weak"
         extra.update(info)
     else:
-        wall, ev_ms, reps, info = run_rk45_single(N, steps, warmup, args.layout, args.variant)
+        wall, ev_ms, reps, info = run_rk45_single(N, steps, warmup, args.layout, args.variant, outputs)
         units = float(N) * steps
         workload = f"rk45_fused_single_grid N={N} fp64, rtol=atol=1e-3; steps = attempted steps"
         kernel, parallelism, scaling = "rk45_attempt_kernel", f"{world} rank(s), each integrating its own grid; no collective in the data path", "weak"
         extra.update(info)
     value = units * world / wall
+    if outputs is not None:
+        if args.workload in ("sweep_rk45", "sweep_rk4"):   # y [B, 5, N] and stats [B, 5]: sampled by instance
+            write_outputs(args.dump_outputs, outputs, 0, "instances")
+        else:                                              # y [5, N]: sampled by cell
+            write_outputs(args.dump_outputs, {"y": outputs.pop("y")}, 1, "cells", whole=outputs)
 
-    # ---- CPU baseline (rank 0 only; the oracle is the checker / baseline, never the product) -----------------
+    # ---- CPU baseline (--full; rank 0 only; the oracle is the checker / baseline, never the product) ---------
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         from oracle import oracle as orc
         orc.build()
         ncores = min(len(os.sched_getaffinity(0)), 16)  # a 1-GPU box shares its host: 16 CPUs per GPU
@@ -463,7 +537,8 @@ def main():
         # RCCL set-up on the multi-GPU node), and that must be red, not a flag inside a green line
         os._exit(int(os.environ.get("MARL_BENCH_TIMEOUT_RC", "3" if world > 1 else "0")))
 
-    do_extras = args.workload == "rk4_single" and args.n is None and args.variant < 0 and not args.no_extras and not args.no_reuse
+    do_extras = (args.full and args.workload == "rk4_single" and args.n is None and args.variant < 0 and not args.no_extras
+                 and not args.no_reuse)
     if do_extras:
         dog = threading.Timer(EXTRAS_DEADLINE_S, deadline)
         dog.daemon = True

@@ -22,7 +22,7 @@ def _run(args, env_extra, timeout):
 
 
 def test_bench_two_ranks_rehearsal_on_one_gpu():
-    p, lines = _run(["--gpus", "2", "--steps", "8", "--warmup", "2"],
+    p, lines = _run(["--gpus", "2", "--steps", "8", "--warmup", "2", "--full"],
                     {"MARL_BENCH_BACKEND": "gloo", "MARL_BENCH_ONE_DEVICE": "1", "MARL_BENCH_EXTRAS_DEADLINE": "420", "MARL_BENCH_TIMEOUT_RC": "7"}, 900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines                 # exactly one line on stdout, from rank 0
@@ -42,7 +42,7 @@ def test_bench_five_ranks_rehearsal_on_one_gpu():
     """The rank launch, port, deadline, sharding and gather logic at a rank count near the node's 8: FIVE ranks on cuda:0 (a gpurun box
     admits six GPU processes at once, and this test process is one of them), gloo collectives, reduced extras
     (MARL_BENCH_LIGHT_EXTRAS).  Five does not divide the grid or the sweep: uneven slabs, uneven halo owners."""
-    p, lines = _run(["--gpus", "5", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"],
+    p, lines = _run(["--gpus", "5", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--full"],
                     {"MARL_BENCH_BACKEND": "gloo", "MARL_BENCH_ONE_DEVICE": "1", "MARL_BENCH_EXTRAS_DEADLINE": "600", "MARL_BENCH_LIGHT_EXTRAS": "1"}, 1000)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, lines
@@ -58,11 +58,43 @@ def test_bench_five_ranks_rehearsal_on_one_gpu():
 def test_bench_watchdog_marks_the_line_and_can_exit_nonzero():
     """A deadline of 0 s fires while the first extra runs: the headline line must come out once, marked at top level, and the
     exit code is the one MARL_BENCH_TIMEOUT_RC asks for (0 by default: the headline was measured before the extras started)."""
-    p, lines = _run(["--steps", "8", "--warmup", "2", "--no-cpu-baseline"], {"MARL_BENCH_EXTRAS_DEADLINE": "0.001", "MARL_BENCH_TIMEOUT_RC": "7"}, 600)
+    p, lines = _run(["--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--full"], {"MARL_BENCH_EXTRAS_DEADLINE": "0.001", "MARL_BENCH_TIMEOUT_RC": "7"}, 600)
     assert p.returncode == 7, (p.returncode, p.stderr[-2000:])
     assert len(lines) == 1
     j = json.loads(lines[0])
     assert j["extras_timed_out"] is True and j["n_gpus"] == 1 and j["value"] > 1e9
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """A plain run (no --full) prints the headline line without CPU baseline or extras; --dump-outputs writes the state the timed
+    call left (field-major [5, N]), which is the oracle's RK4 of the same input over settle + warm-up + timed steps, and a second
+    run with the same arguments writes the same array."""
+    from dataclasses import asdict
+
+    import numpy as np
+
+    from common import rel_to_max, synthetic_state
+    from marlpde_amd.parameters import Map_Scenario
+    from oracle import oracle as orc
+    N, steps, warmup = 4096, 8, 2
+    ys = []
+    for k in range(2):
+        p, lines = _run(["--n", str(N), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / f"run{k}")], {}, 600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert len(lines) == 1, lines
+        j = json.loads(lines[0])
+        assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0 and j["value"] > 0
+        assert j["cpu_baseline"] is None and "extra" not in j and j["extras_timed_out"] is False
+        assert sorted(os.listdir(tmp_path / f"run{k}")) == ["y.npy"]
+        ys.append(np.load(tmp_path / f"run{k}" / "y.npy"))
+    assert ys[0].shape == (5, N) and ys[0].dtype == np.float64
+    assert np.array_equal(ys[0], ys[1])
+    base = asdict(Map_Scenario()) | {"N": N}
+    L = base["max_depth"] / base["Xstar"]
+    orc.build()
+    ref = orc.rk4(orc.params_from_dict(base), N, synthetic_state(base, N), 0.25 * (L / N) ** 2,
+                  2000 + warmup + steps)   # bench.py's settle call is 2000 steps long
+    assert rel_to_max(ys[0], ref) <= 1e-9
 
 
 def test_slab_comm_init_rejects_a_bad_id_without_entering_rccl():

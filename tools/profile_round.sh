@@ -10,7 +10,7 @@ out=$1
 quick=$2
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-python3 bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+python3 bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 echo "bench default done"
 for w in sweep_rk45 rk45_single sweep_rk4 dd_rk45; do
   python3 bench.py --no-cpu-baseline --workload $w > "$out/bench_$w.json" 2> "$out/bench_$w.err"
