@@ -34,12 +34,97 @@ def rel_to_max(a, b):
     return float(np.max(np.abs(a - b) / scale))
 
 
+EPS = float(np.finfo(np.float64).eps)
+
+# Increment measure of the fine-grid explicit runs (tests/test_gpu_parity.py).  rel_to_max compares the final STATE; a short run at a fine
+# grid changes the state by 1e-9 .. 1e-6 of its maximum, so RUN_TOL = 1e-10 there hardly constrains what was computed.  This measure compares
+# the computed CHANGE: per field f
+#     max|got - ref| <= rel * max|ref - y0| + ulps * nsteps * eps * max|y0|
+# (second term: the state is rounded once per step whatever its increment).  `measured` is the worst max|got - ref| / max|ref - y0| over fields,
+# cases and parametrisations of that test on an MI355X; `rel` is at most ~10x that.  RK45 runs near the stability limit amplify rounding (the
+# *_rk45 rows are 10-1000x the RK4 rows): there the bound records what a run reproduces, not a rounding floor.  The configurations of the RK4 tests at N >= 65 536 are
+# shared with tests/test_parity_sensitivity.py, which checks on the CPU that these bounds flag a perturbed model constant.
+INCR_TOL = {
+    # key (test and part)              bound              measured on MI355X: worst ratio over fields and cases
+    "rk4_fused_variants":          dict(rel=5e-11, ulps=2, measured=5.2e-12),
+    "rk4_config2":                 dict(rel=1e-10, ulps=2, measured=1.4e-11),
+    "rk4_full_size":               dict(rel=5e-9, ulps=2, measured=5.2e-10),
+    "stage_reuse_boundary_rk4":    dict(rel=3e-11, ulps=2, measured=3.1e-12),
+    "stage_reuse_boundary_rk45":   dict(rel=8e-9, ulps=2, measured=8.4e-10),
+    "rk45_fused_large_grid":       dict(rel=1e-11, ulps=2, measured=9.7e-13),
+    "rk45_host_t_eval":            dict(rel=2e-10, ulps=2, measured=2.3e-11),
+    "rk45_schedules_vd":           dict(rel=4e-12, ulps=2, measured=4.0e-13),
+    "vd_rk4":                      dict(rel=1e-13, ulps=2, measured=1.3e-14),
+    "vd_rk45":                     dict(rel=7e-12, ulps=2, measured=7.3e-13),
+    "mixed_upwind_rk4":            dict(rel=3e-13, ulps=2, measured=3.0e-14),
+    "mixed_upwind_rk45":           dict(rel=4e-9, ulps=2, measured=4.2e-10),
+    "slabs":                       dict(rel=1e-11, ulps=2, measured=1.2e-12),
+    # tests/test_gpu_increment.py
+    "sat_rk4":                     dict(rel=1e-11, ulps=2, measured=9.6e-13),
+    "sat_rk45":                    dict(rel=2e-7, ulps=2, measured=1.8e-8),
+    "sat_rk4_large":               dict(rel=3e-10, ulps=2, measured=3.4e-11),
+    "sat_rk45_large":              dict(rel=5e-8, ulps=2, measured=5.4e-9),
+    "sat_slabs":                   dict(rel=2e-10, ulps=2, measured=1.8e-11),
+    "sat_sweep":                   dict(rel=6e-12, ulps=2, measured=5.7e-13),
+    "rk45_baseline":               dict(rel=1e-6, ulps=2, measured=1.2e-7),
+}
+
+# fixed-step configurations at N >= 65 536 (the GPU tests run these; the sensitivity test perturbs the oracle at the same ones)
+RK4_FINE_CONFIGS = {
+    "rk4_config2": dict(scenario="default", N=65536, nsteps=37, amplitude=0.01, dtf=0.25),
+    "rk4_full_size": dict(scenario="default", N=1 << 20, nsteps=8, amplitude=0.01, dtf=0.25),
+}
+
+
+def increment_errors(got, ref, y0):
+    """Per field: max|got - ref|, max|ref - y0|, max|y0|."""
+    g, r, y = (np.asarray(a, dtype=np.float64).reshape(5, -1) for a in (got, ref, y0))
+    return np.max(np.abs(g - r), axis=1), np.max(np.abs(r - y), axis=1), np.max(np.abs(y), axis=1)
+
+
+def increment_ok(got, ref, y0, key, nsteps):
+    """(passes, per-field err / max|ref - y0|, message) of the increment measure with the INCR_TOL[key] bound."""
+    tol = INCR_TOL[key]
+    err, inc, scale = increment_errors(got, ref, y0)
+    bound = tol["rel"] * inc + tol["ulps"] * max(int(nsteps), 1) * EPS * scale
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(inc > 0, err / inc, np.where(err > 0, np.inf, 0.0))
+    fields = ("CA", "CC", "cCa", "cCO3", "Phi")
+    msg = f"{key} (rel {tol['rel']:.0e}, ulps {tol['ulps']}, {nsteps} steps): " + ", ".join(
+        f"{f} |got-ref| {e:.2e} / incr {i:.2e} = {q:.2e}" + ("" if e <= b else f" > bound {b:.2e}")
+        for f, e, i, q, b in zip(fields, err, inc, ratio, bound))
+    return bool(np.all(err <= bound)), ratio, msg
+
+
+def assert_increment(got, ref, y0, key, nsteps):
+    """Assert the increment measure; the per-field ratios are printed as one JSON line (pytest -rA), the record the measured values of
+    INCR_TOL are read from."""
+    import json
+    ok, ratio, msg = increment_ok(got, ref, y0, key, nsteps)
+    print("INCREMENT", json.dumps({"key": key, "nsteps": int(nsteps), "ratio": [float(q) for q in ratio], "ok": ok}))
+    assert ok, msg
+
+
 def synthetic_state(p, N, amplitude=0.01, waves=8):
     """The bench's deterministic smooth state: initial values x (1 + a sin(2 pi k x / L))."""
     L = p["max_depth"] / p["Xstar"]
     x = (np.arange(N) + 0.5) * (L / N)
     y = np.stack([np.full(N, p[k]) for k in ("CAIni", "CCIni", "cCaIni", "cCO3Ini", "PhiIni")])
     return (y * (1.0 + amplitude * np.sin(2 * np.pi * waves * x / L))).ravel()
+
+
+def saturating_state(p, N, waves=8, level=1.05, amplitude=0.3, ramp=0.03):
+    """A smooth state through the saturation branches: the solutes ramp from their Dirichlet values at x = 0 (weight 1 - exp(-(x / l)^2),
+    l = ramp * L) to level * (1 + amplitude * sin / cos), so O2 = cCa cCO3 crosses 1 several times and O3 = KRat O2 exceeds 1 where both
+    are high; the solids and the porosity are synthetic_state's (equal to their boundary values at x = 0 in the scenarios used here)."""
+    L = p["max_depth"] / p["Xstar"]
+    x = (np.arange(N) + 0.5) * (L / N)
+    y = synthetic_state(p, N, amplitude=0.01, waves=waves).reshape(5, N).copy()
+    s = 1.0 - np.exp(-(x / (ramp * L)) ** 2)
+    a = 2 * np.pi * waves * x / L
+    y[2] = p["cCa0"] + s * (level * (1 + amplitude * np.sin(a)) - p["cCa0"])
+    y[3] = p["cCO30"] + s * (level * (1 + amplitude * np.cos(a + 0.3)) - p["cCO30"])
+    return y.ravel()
 
 
 def noisy_state(p, N, seed=0, sigma=0.05):
