@@ -112,6 +112,17 @@ struct StencilBlock {
     // instead of three (it lives across every stage, and the fused integrators sit at their register cap)
     static_assert(CPT <= 8, "three 8-bit fields");
     unsigned masks;
+    // wave-uniform: bit c is set when the c-th cell of SOME lane of the wave is global cell 0 or N-1 (the ballot of is_edge(c), taken
+    // once per window: re-taken in every evaluation it rebuilt a lane mask in vector registers - two VALU instructions per stage).
+    // Only where the transcendental cache is (the fine-grid kernels): in the 1024-thread one-workgroup sweeps, one more value carried
+    // through the kernel grows the scratch spill of rk45_sweep_kernel (184 -> 192 B); they keep the ballot per evaluation
+    static constexpr bool EDGE_ONCE = CACHE;
+    unsigned edge_cells;
+    __device__ __forceinline__ bool edge_wave(int c) const
+    {
+        if constexpr (EDGE_ONCE) return (edge_cells >> c) & 1u;
+        else return __builtin_amdgcn_ballot_w64(is_edge(c) != 0) != 0;
+    }
     __device__ __forceinline__ unsigned is_first(int c) const { return (masks >> c) & 1u; }
     __device__ __forceinline__ unsigned is_last(int c) const { return (masks >> (8 + c)) & 1u; }
     __device__ __forceinline__ unsigned in_zone(int c) const { return (masks >> (16 + c)) & 1u; }
@@ -161,6 +172,11 @@ struct StencilBlock {
             const int64_t g = g0 + i;
             masks |= ((g == 0) ? (1u << i) : 0u) | ((g == N - 1) ? (0x100u << i) : 0u) | ((g >= mlo && g < mhi) ? (0x10000u << i) : 0u);
         }
+        edge_cells = 0;
+        if constexpr (EDGE_ONCE) {
+#pragma unroll
+            for (int i = 0; i < CPT; i++) edge_cells |= (__builtin_amdgcn_ballot_w64(is_edge(i) != 0) != 0) ? (1u << i) : 0u;
+        }
     }
 
     // k[c] = RHS(stage state ys) for the thread's CPT cells.  Contains exactly one __syncthreads(): the own-cell phase
@@ -179,7 +195,7 @@ struct StencilBlock {
             const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl.upw) != 0;
 #pragma unroll
             for (int f = 0; f < NF; f++) up[f] = (f >= 2 || need_right_solids) ? wave_from_right(ys[0][f]) : 0.0;
-            if (__builtin_amdgcn_ballot_w64(is_edge(0) != 0) != 0) {   // physical boundaries: two cells of the whole grid
+            if (edge_wave(0)) {   // physical boundaries: two cells of the whole grid
                 if (is_last(0)) {
 #pragma unroll
                     for (int f = 0; f < NF; f++) up[f] = ghost_upper(f, ys[0][f], um[f]);
@@ -220,8 +236,21 @@ struct StencilBlock {
         // the solids are differenced against the upwind neighbour only: with U > 0 in every lane (burial - the normal
         // case) the right-hand values of CA and CC are never used and their two LDS reads are skipped
         const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl[CPT - 1].upw) != 0;
+        if constexpr (CPT == 1 && CACHE) {
 #pragma unroll
-        for (int f = 0; f < NF; f++) right[f] = (f >= 2 || need_right_solids) ? e[f * BLK + tr] : 0.0;  // right neighbour's FIRST cell
+            for (int f = 2; f < NF; f++) right[f] = e[f * BLK + tr];   // right neighbour's FIRST cell
+            // a wave-uniform branch around the two reads; without them right[0], right[1] hold whatever their registers held: point_rates,
+            // told that no lane mixes upwind directions, does not read them (a 0.0 put there instead costs a v_mov_b64 each, every stage;
+            // so does a plain unset value, which the compiler materialises as 0 - the empty asm defines them without an instruction)
+            asm volatile("" : "=v"(right[0]), "=v"(right[1]));
+            if (need_right_solids) {
+                right[0] = e[tr];
+                right[1] = e[BLK + tr];
+            }
+        } else {   // (the one-workgroup sweeps keep the select form: the branch grows rk45_sweep_kernel's scratch)
+#pragma unroll
+            for (int f = 0; f < NF; f++) right[f] = (f >= 2 || need_right_solids) ? e[f * BLK + tr] : 0.0;  // right neighbour's FIRST cell
+        }
         parity ^= 1;
 #pragma unroll
         for (int c = 0; c < CPT; c++) {
@@ -232,7 +261,7 @@ struct StencilBlock {
                 up[f] = (c == CPT - 1) ? right[f] : ys[c < CPT - 1 ? c + 1 : c][f];
             }
             // physical boundaries: two cells of the whole grid - a wave-uniform branch, skipped by every other wave
-            if (__builtin_amdgcn_ballot_w64(is_edge(c) != 0) != 0) {
+            if (edge_wave(c)) {
                 if (is_last(c)) {
 #pragma unroll
                     for (int f = 0; f < NF; f++) up[f] = ghost_upper(f, ys[c][f], um[f]);

@@ -260,10 +260,20 @@ struct PointCache {
     double Phi, O2, cPhi, nib;
     double* s;                       // this cell's LDS slots (slot j at s[(j - FIRST_LDS) * STRIDE])
     double v[FIRST_LDS > 0 ? FIRST_LDS : 1];
-    bool fv_quiet;                   // all three Peclet numbers were < 0.9 PECLET_MIN at the centre
+    bool fv_quiet;                   // wave-uniform: in every lane all three Peclet numbers were < 0.9 PECLET_MIN at the centre
     __device__ __forceinline__ double get(int j) const { return j < FIRST_LDS ? v[j] : s[(j - FIRST_LDS) * STRIDE]; }
     __device__ __forceinline__ void set(int j, double x) { if (j < FIRST_LDS) v[j] = x; else s[(j - FIRST_LDS) * STRIDE] = x; }
 };
+
+// 10.0 as an fp64 operand of the point evaluation.  The cached modes (the fine-grid kernels) take it from scalar registers: VOP3
+// v_fma_f64 reads the pair directly, where a literal costs two v_mov_b32 into a vector pair every evaluation.  TR_PLAIN (the one-workgroup
+// sweeps and the stand-alone RHS) keeps the literal: the two extra scalar registers there made rk4_sweep_kernel 0.7 % slower.
+template <int MODE>
+__device__ __forceinline__ double ten_operand()
+{
+    if constexpr (MODE == TR_PLAIN) return 10.0;
+    else return pin_uniform(10.0);
+}
 
 // One RHS evaluation of a cell is split in two phases, so that the neighbour values (10 doubles) are not held in
 // registers while the transcendental part runs, and so that a stencil kernel can do the own-cell work BEFORE the
@@ -326,7 +336,7 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
             const double x = d * invPhi0, y = d * invom0, u = dO * ib0;
             double l1p, ip, w, gy;
             double da;                                                                    // change of 10 - 10/Phi = -10 (ip - invPhi0)
-            if (tiny) {
+            if (__builtin_expect(tiny, 1)) {
                 l1p = x * __builtin_fma(x, -0.5, 1.0);                                    // log1p(x)
                 const double t10 = invPhi0 * __builtin_fma(-x, x, x);                     // invPhi0 x (1 - x)
                 ip = invPhi0 - t10;                                                       // 1/(Phi0 (1+x)) = invPhi0 (1 - x + x^2)
@@ -343,7 +353,7 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
             const double z = -2.0 * l1p * invden0;                                        // (den - den0)/den0
             invPhi = ip;
             invom = invom0 * gy;
-            if (tiny) {
+            if (__builtin_expect(tiny, 1)) {
                 invden = __builtin_fma(-invden0, __builtin_fma(-z, z, z), invden0);       // invden0 (1 - z + z^2)
                 ex = e0 * __builtin_fma(da, __builtin_fma(da, 0.5, 1.0), 1.0);
                 tC = tC0 * __builtin_fma(w, __builtin_fma(w, 0.5, 1.0), 1.0);
@@ -354,7 +364,9 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
             }
             // wave-uniform on purpose: a per-lane condition is if-converted, and the Peclet test (with the reciprocal
             // that recovers den) would then run in every evaluation
-            fv_check = fv_check && __builtin_amdgcn_ballot_w64(!pc.fv_quiet) != 0;
+            // (fv_quiet holds the ballot of the fill: a wave-uniform flag tested on the scalar side, no lane mask rebuilt per evaluation.
+            // A fill with FV_switch off sets it, so it alone decides: the switch itself need not stay live across the stages)
+            fv_check = !pc.fv_quiet;
             if (fv_check) {
                 asm volatile("");
                 den = rcp_nr(invden);   // only the Peclet numbers need den itself
@@ -379,7 +391,8 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
 #ifdef MARL_ABLATE_EXP
         ex = 0.01 * __builtin_fma(-10.0, invPhi, 10.0);
 #else
-        ex = fast_exp(__builtin_fma(-10.0, invPhi, 10.0), T);
+        const double ten = ten_operand<MODE>();   // (cached modes: one scalar pair serves as -10 and as 10)
+        ex = fast_exp(__builtin_fma(-ten, invPhi, ten), T);
 #endif
         const bool over = O2 > 1.0;
         const double nsel = over ? K.n1 : K.n2;
@@ -453,7 +466,9 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
 
     // ---- Fiadeiro-Veronis weights (:433-462) all vanish when every |Pe| < PECLET_MIN (always on fine grids)
     bool fv_active = false;
-    pl.Wd = 0.0;
+    // pl.Wd is set only where fv_active can be, and point_rates reads it nowhere else: the cached modes carry no zero for it (a v_mov_b64
+    // per evaluation); TR_PLAIN keeps its code as it was
+    if constexpr (MODE == TR_PLAIN) pl.Wd = 0.0;
 #ifdef MARL_ABLATE_FV   // kernel-lab builds only: central gradients throughout
     fv_check = false;
 #endif
@@ -473,7 +488,9 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
         // (0 -> 28 B/lane of scratch, rk45_single -9 %) for a branch those kernels never take.
         if constexpr (MODE == TR_PLAIN) pl.fv_solutes = __builtin_amdgcn_ballot_w64(!(psol < PECLET_MIN)) != 0;
         pl.Wd = Wd;
-        if constexpr (MODE == TR_FILL || MODE == TR_AUTO) { if (!reuse) pc.fv_quiet = pmax < 0.9 * PECLET_MIN; }  // in range, Pe moves by < 1e-3 relative
+        if constexpr (MODE == TR_FILL || MODE == TR_AUTO) {   // in range, Pe moves by < 1e-3 relative
+            if (!reuse) pc.fv_quiet = __builtin_amdgcn_ballot_w64(!(pmax < 0.9 * PECLET_MIN)) == 0;   // (a fill is wave-uniform: reuse is)
+        }
     } else if constexpr (MODE == TR_FILL || MODE == TR_AUTO) {
         if (!reuse) pc.fv_quiet = true;  // FV_switch off
     }
@@ -491,7 +508,7 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
     }
     pl.h1x = (Phi * invden) * K.inv_dx2;                            // Phi/den / dx^2
     pl.h2f = invden * __builtin_fma(2.0, invden, 1.0);              // (2+den)/den^2
-    const double q = __builtin_fma(rF, __builtin_fma(2.0, Phi, 10.0), -K.rr10);  // rhorat (2 Phi F + 10 (F-1))  (:495)
+    const double q = __builtin_fma(rF, __builtin_fma(2.0, Phi, ten_operand<MODE>()), -K.rr10);  // rhorat (2 Phi F + 10 (F-1))  (:495)
     pl.Q4 = __builtin_fma(-Phi, q, W);                              // -(dWdx Phi + W Phi') = -Phi' (W - Phi q)  (:518-520)
     pl.DaR = DaR;
 }
