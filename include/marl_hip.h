@@ -54,7 +54,9 @@ const char* marl_last_error(const marl_ctx* ctx); /* ctx may be NULL: error of t
 int marl_set_stream(marl_ctx* ctx, void* hip_stream);
 int marl_synchronize(marl_ctx* ctx);
 /* Tuning knobs; unknown names are an error.  See DESIGN.md.
- *   rk4_variant, rk45_variant, sweep_variant (kernel shapes; -1 = default), host_layout (device layout used behind the
+ *   rk4_variant (fused RK4 steps per launch: 0..4 = 1 / 2 / 4 / 8 / 16; anything else, e.g. -1: chosen by grid size; with dPhi_variable
+ *   always 4), sweep_variant (one-workgroup window: 0 / 1 / 2 = 256 / 512 / 1024 cells, used when it holds N; otherwise, e.g. -1, the
+ *   smallest that does), rk45_variant (accepted, no effect: the adaptive kernels have one shape), host_layout (device layout used behind the
  *   host-pointer entry points), poll_interval (attempts enqueued between status reads), no_reuse (1: every RHS evaluation of
  *   the fused kernels takes its full transcendental path - the input-independent worst case, for benchmarks), radau_solver
  *   (linear systems of the implicit path: 0 block parallel cyclic reduction - the default; 1 sequential block Thomas, a cross-check that

@@ -90,7 +90,7 @@ struct marl_ctx {
     double* zc_d = nullptr;     // device view of the same memory
     bool zc_on = false;         // the run in progress uses it
     // options
-    int64_t rk4_variant = -1, rk45_variant = -1, sweep_variant = -1, host_layout = LAYOUT_TILED, poll = 64;
+    int64_t rk4_variant = -1, sweep_variant = -1, host_layout = LAYOUT_TILED, poll = 64;
     int64_t rk4_stream = 1;     // the fixed-step loop of one grid as ONE dataflow launch (rk4_stream_kernel): 0 never, 1 large grids, 2 always
     int64_t rk4_small = 1;      // grids of up to two workgroups per CU at 16 steps per launch: the build of marl_rk4_small.hip (0: the common one)
     int64_t rk4_stream_third = 1;   // an odd number of levels goes through a third state buffer, so that no whole-state copy follows (0: copy)
@@ -386,7 +386,7 @@ int marl_set_option(marl_ctx* ctx, const char* name, int64_t value)
     if (!ctx || !name) return -1;
     const std::string n(name);
     if (n == "rk4_variant") ctx->rk4_variant = value;
-    else if (n == "rk45_variant") ctx->rk45_variant = value;
+    else if (n == "rk45_variant") { }   // accepted, no effect: the adaptive kernels have one shape
     else if (n == "sweep_variant") ctx->sweep_variant = value;
     else if (n == "host_layout") ctx->host_layout = value ? LAYOUT_TILED : LAYOUT_FIELD_MAJOR;
     else if (n == "poll_interval") ctx->poll = value > 0 ? value : 1;
@@ -511,43 +511,40 @@ static void record_to_events(const double* r, double* g)
     g[0] = r[1]; g[1] = r[2]; g[2] = r[3]; g[3] = r[5] - 1.0; g[4] = r[6] - 1.0; g[5] = r[4]; g[6] = r[7];
 }
 
-// ---- fused RK4 variants ------------------------------------------------------------------------
-struct Rk4Variant { int blk, cpt, nsteps; };
+// ---- fused RK4: launch depths -------------------------------------------------------------------
 // One shape ships: 256-thread blocks, one cell per thread (4 waves per SIMD), at 1 / 2 / 4 / 8 / 16 steps per launch - the default
-// depth depends on the grid size, the shallower ones also serve as the remainder chain.  (Other block shapes and cells per thread
-// were measured in round 1 and live in tools/rk4_lab.hip only.)
-static const Rk4Variant kRk4Variants[] = {{256, 1, 1}, {256, 1, 2}, {256, 1, 4}, {256, 1, 8}, {256, 1, 16}};
-constexpr int kNumRk4Variants = sizeof(kRk4Variants) / sizeof(kRk4Variants[0]);
+// depth depends on the grid size, the shallower ones also serve as the remainder chain.  Option rk4_variant = index into this list.
+// (Other block sizes are timed in tools/rk4_lab.hip only.)
+static const int kRk4Depths[] = {1, 2, 4, 8, 16};
+constexpr int kNumRk4Depths = sizeof(kRk4Depths) / sizeof(kRk4Depths[0]);
 
-template <int BLK, int CPT, int NSTEPS, bool VD = false>
+template <int NSTEPS, bool VD = false>
 static void launch_rk4_t(marl_ctx* ctx, const double* yin, double* yout, int layout, double dt)
 {
-    constexpr int V = BLK * CPT - 8 * NSTEPS;
+    constexpr int V = 256 - 8 * NSTEPS;
     const int64_t n = ctx->slab.out_hi - ctx->slab.out_lo;
     const dim3 grid((unsigned)((n + V - 1) / V));
     if (layout == LAYOUT_TILED)
-        hipLaunchKernelGGL((rk4_fused_kernel<BLK, CPT, LAYOUT_TILED, NSTEPS, VD>), grid, dim3(BLK), 0, ctx->stream, yin, yout, ctx->dconsts, ctx->slab, dt);
+        hipLaunchKernelGGL((rk4_fused_kernel<256, LAYOUT_TILED, NSTEPS, VD>), grid, dim3(256), 0, ctx->stream, yin, yout, ctx->dconsts, ctx->slab, dt);
     else
-        hipLaunchKernelGGL((rk4_fused_kernel<BLK, CPT, LAYOUT_FIELD_MAJOR, NSTEPS, VD>), grid, dim3(BLK), 0, ctx->stream, yin, yout, ctx->dconsts, ctx->slab, dt);
+        hipLaunchKernelGGL((rk4_fused_kernel<256, LAYOUT_FIELD_MAJOR, NSTEPS, VD>), grid, dim3(256), 0, ctx->stream, yin, yout, ctx->dconsts, ctx->slab, dt);
 }
 
-// The kernel sets instantiated with the time-varying porosity diffusion coefficient (dPhi_variable): one
-// one-cell-per-thread shape per integrator - the option is a model variant, not a tuning surface.
-constexpr int kVdRk4Variant = 2;    // {256, 1, 4}
-constexpr int kVdRk45Variant = 0;   // {256, 1}
+// The kernels instantiated with the time-varying porosity diffusion coefficient (dPhi_variable): RK4 depths 4 (the default) and 1
+// (the remainder) and the one RK45 set - the option is a model variant, not a tuning surface.
+constexpr int kVdRk4Depth = 4;
 
 extern "C" int marl_small_rk4_16(int tiled, unsigned grid, hipStream_t stream, const double* yin, double* yout, const void* consts, const int64_t slab5[5],
                                  double dt);   // marl_rk4_small.hip
 
-// nsteps: steps fused in this launch - the variant's own depth, or a smaller instantiated one for the remainder
-static int launch_rk4(marl_ctx* ctx, int v, int nsteps, const double* yin, double* yout, int layout, double dt)
+// nsteps: steps fused in this launch - the run's own depth, or a smaller instantiated one for the remainder
+static int launch_rk4(marl_ctx* ctx, int nsteps, const double* yin, double* yout, int layout, double dt)
 {
-    (void)v;
     switch (nsteps) {
-        case 1: if (ctx->var_dphi) launch_rk4_t<256, 1, 1, true>(ctx, yin, yout, layout, dt); else launch_rk4_t<256, 1, 1>(ctx, yin, yout, layout, dt); break;
-        case 2: launch_rk4_t<256, 1, 2>(ctx, yin, yout, layout, dt); break;
-        case 4: if (ctx->var_dphi) launch_rk4_t<256, 1, 4, true>(ctx, yin, yout, layout, dt); else launch_rk4_t<256, 1, 4>(ctx, yin, yout, layout, dt); break;
-        case 8: launch_rk4_t<256, 1, 8>(ctx, yin, yout, layout, dt); break;
+        case 1: if (ctx->var_dphi) launch_rk4_t<1, true>(ctx, yin, yout, layout, dt); else launch_rk4_t<1>(ctx, yin, yout, layout, dt); break;
+        case 2: launch_rk4_t<2>(ctx, yin, yout, layout, dt); break;
+        case 4: if (ctx->var_dphi) launch_rk4_t<4, true>(ctx, yin, yout, layout, dt); else launch_rk4_t<4>(ctx, yin, yout, layout, dt); break;
+        case 8: launch_rk4_t<8>(ctx, yin, yout, layout, dt); break;
         case 16: {
             // grids whose workgroups fit the chip at TWO per CU (N <= 65 536 on 256 CUs: BASELINE configs[1]) take the build of this kernel
             // that trades occupancy for registers and ILP (marl_rk4_small.hip: 3.43 against 3.65 us per step at N = 65 536); with a third
@@ -564,7 +561,7 @@ static int launch_rk4(marl_ctx* ctx, int v, int nsteps, const double* yin, doubl
                 if (e != 0) return fail(ctx, -100 - e, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
                 return 0;
             }
-            launch_rk4_t<256, 1, 16>(ctx, yin, yout, layout, dt);
+            launch_rk4_t<16>(ctx, yin, yout, layout, dt);
             break;
         }
         default: return fail(ctx, -1, "rk4: %d steps per launch not instantiated", nsteps);
@@ -573,14 +570,15 @@ static int launch_rk4(marl_ctx* ctx, int v, int nsteps, const double* yin, doubl
     return 0;
 }
 
-static int default_rk4_variant(const marl_ctx* ctx)
+// steps per launch of a run
+static int default_rk4_depth(const marl_ctx* ctx)
 {
-    if (ctx->var_dphi) return kVdRk4Variant;
-    if (ctx->rk4_variant >= 0 && ctx->rk4_variant < kNumRk4Variants) return (int)ctx->rk4_variant;
+    if (ctx->var_dphi) return kVdRk4Depth;
+    if (ctx->rk4_variant >= 0 && ctx->rk4_variant < kNumRk4Depths) return kRk4Depths[ctx->rk4_variant];
     const int64_t n = ctx->slab.out_hi - ctx->slab.out_lo;
     // 256-thread blocks; the smaller the grid, the more the launch boundary matters against the recomputed halo:
     // 16 / 8 / 4 steps per launch (tools/variant_sweep.sh)
-    return n <= 98304 ? 4 : (n <= 262144 ? 3 : 2);
+    return n <= 98304 ? 16 : (n <= 262144 ? 8 : 4);
 }
 
 #ifndef MARL_LAB_STREAM_BLK   // (kernel-lab switch: threads per workgroup of the streamed loop; 512 = half the halo share, twice the waves per barrier)
@@ -673,8 +671,7 @@ constexpr int64_t kStreamMinCells = 196608;
 // y (device, `layout`) advanced in place; `tmp` is a second buffer of the same size
 static int rk4_run(marl_ctx* ctx, double* y, double* tmp, int layout, double dt, int64_t nsteps)
 {
-    const int v = default_rk4_variant(ctx);
-    const int per = kRk4Variants[v].nsteps;
+    const int per = default_rk4_depth(ctx);
     double* a = y;
     double* b = tmp;
     int64_t left = nsteps;
@@ -690,7 +687,7 @@ static int rk4_run(marl_ctx* ctx, double* y, double* tmp, int layout, double dt,
         left -= levels * per;
     }
     while (left >= per) {
-        if (int rc = launch_rk4(ctx, v, per, a, b, layout, dt)) return rc;
+        if (int rc = launch_rk4(ctx, per, a, b, layout, dt)) return rc;
         std::swap(a, b);
         left -= per;
     }
@@ -699,7 +696,7 @@ static int rk4_run(marl_ctx* ctx, double* y, double* tmp, int layout, double dt,
     for (int chunk = per / 2; chunk >= 1 && left > 0; chunk /= 2) {
         const int c = family ? chunk : 1;
         while (left >= c) {
-            if (int rc = launch_rk4(ctx, v, c, a, b, layout, dt)) return rc;
+            if (int rc = launch_rk4(ctx, c, a, b, layout, dt)) return rc;
             std::swap(a, b);
             left -= c;
             if (family) break;   // at most one launch per power of two
@@ -709,60 +706,51 @@ static int rk4_run(marl_ctx* ctx, double* y, double* tmp, int layout, double dt,
     return 0;
 }
 
-// ---- sweep variants ----------------------------------------------------------------------------
-struct SweepVariant { int blk, cpt; };
-// one cell per thread; the smallest window that holds the grid is taken
-static const SweepVariant kSweepVariants[] = {{256, 1}, {512, 1}, {1024, 1}};
-constexpr int kNumSweepVariants = sizeof(kSweepVariants) / sizeof(kSweepVariants[0]);
+// ---- one-workgroup sweeps: window sizes ---------------------------------------------------------
+// one cell per thread; the smallest window that holds the grid is taken (option sweep_variant = index of another one that holds it)
+static const int kSweepBlocks[] = {256, 512, 1024};
+constexpr int kNumSweepBlocks = sizeof(kSweepBlocks) / sizeof(kSweepBlocks[0]);
 
-static int default_sweep_variant(marl_ctx* ctx)
+// threads (= cells) of the sweep window of this grid; 0: the grid does not fit one workgroup
+static int sweep_block(const marl_ctx* ctx)
 {
-    if (ctx->sweep_variant >= 0 && ctx->sweep_variant < kNumSweepVariants && (int64_t)kSweepVariants[ctx->sweep_variant].blk >= ctx->N)
-        return (int)ctx->sweep_variant;
-    for (int i = 0; i < kNumSweepVariants; i++)
-        if ((int64_t)kSweepVariants[i].blk * kSweepVariants[i].cpt >= ctx->N) return i;
-    return -1;
-}
-
-#define SWEEP_DISPATCH(KERNEL, ...)                                                                           \
-    switch (v) {                                                                                              \
-        case 0: if (ctx->var_dphi) hipLaunchKernelGGL((KERNEL<256, 1, true>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); \
-                else hipLaunchKernelGGL((KERNEL<256, 1>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;    \
-        case 1: if (ctx->var_dphi) hipLaunchKernelGGL((KERNEL<512, 1, true>), grid, dim3(512), 0, ctx->stream, __VA_ARGS__); \
-                else hipLaunchKernelGGL((KERNEL<512, 1>), grid, dim3(512), 0, ctx->stream, __VA_ARGS__); break;    \
-        case 2: if (ctx->var_dphi) hipLaunchKernelGGL((KERNEL<1024, 1, true>), grid, dim3(1024), 0, ctx->stream, __VA_ARGS__); \
-                else hipLaunchKernelGGL((KERNEL<1024, 1>), grid, dim3(1024), 0, ctx->stream, __VA_ARGS__); break;  \
-        default: return fail(ctx, -1, "sweep variant %d not instantiated", v);                                \
-    }
-
-// ---- fused RK45 variants -----------------------------------------------------------------------
-struct Rk45Variant { int blk, cpt; };
-static const Rk45Variant kRk45Variants[] = {{256, 1}};   // (other shapes were measured in round 1; none faster)
-constexpr int kNumRk45Variants = sizeof(kRk45Variants) / sizeof(kRk45Variants[0]);
-
-static int default_rk45_variant(const marl_ctx* ctx)
-{
-    if (ctx->var_dphi) return kVdRk45Variant;
-    if (ctx->rk45_variant >= 0 && ctx->rk45_variant < kNumRk45Variants) return (int)ctx->rk45_variant;
+    if (ctx->sweep_variant >= 0 && ctx->sweep_variant < kNumSweepBlocks && (int64_t)kSweepBlocks[ctx->sweep_variant] >= ctx->N)
+        return kSweepBlocks[ctx->sweep_variant];
+    for (int i = 0; i < kNumSweepBlocks; i++)
+        if ((int64_t)kSweepBlocks[i] >= ctx->N) return kSweepBlocks[i];
     return 0;
 }
 
-static int64_t rk45_blocks(const marl_ctx* ctx, int v)
+// (switches on `blk`, a sweep_block() of the caller)
+#define SWEEP_DISPATCH(KERNEL, ...)                                                                           \
+    switch (blk) {                                                                                            \
+        case 256: if (ctx->var_dphi) hipLaunchKernelGGL((KERNEL<256, true>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); \
+                else hipLaunchKernelGGL((KERNEL<256>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;       \
+        case 512: if (ctx->var_dphi) hipLaunchKernelGGL((KERNEL<512, true>), grid, dim3(512), 0, ctx->stream, __VA_ARGS__); \
+                else hipLaunchKernelGGL((KERNEL<512>), grid, dim3(512), 0, ctx->stream, __VA_ARGS__); break;       \
+        case 1024: if (ctx->var_dphi) hipLaunchKernelGGL((KERNEL<1024, true>), grid, dim3(1024), 0, ctx->stream, __VA_ARGS__); \
+                else hipLaunchKernelGGL((KERNEL<1024>), grid, dim3(1024), 0, ctx->stream, __VA_ARGS__); break;     \
+        default: return fail(ctx, -1, "sweep: no %d-thread window", blk);                                     \
+    }
+
+// ---- fused RK45 --------------------------------------------------------------------------------
+// One shape: 256-thread windows that write 256 - 2 * 6 cells (option rk45_variant is accepted and ignored: only 0 ever existed).
+static int64_t rk45_blocks(const marl_ctx* ctx)
 {
-    const int V = kRk45Variants[v].blk * kRk45Variants[v].cpt - 12;
+    const int V = 256 - 12;
     const int64_t n = ctx->slab.out_hi - ctx->slab.out_lo;
     return (n + V - 1) / V;
 }
 
 constexpr int64_t kReduceGroups = 64;
-template <int BLK, int CPT, bool VD = false>
+template <bool VD = false>
 static void launch_attempt_t(marl_ctx* ctx, int64_t nb, int layout)
 {
     if (layout == LAYOUT_TILED)
-        hipLaunchKernelGGL((rk45_attempt_kernel<BLK, CPT, LAYOUT_TILED, VD>), dim3((unsigned)nb), dim3(BLK), 0, ctx->stream, ctx->buf[0], ctx->buf[1],
+        hipLaunchKernelGGL((rk45_attempt_kernel<256, LAYOUT_TILED, VD>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, ctx->buf[0], ctx->buf[1],
                            ctx->buf[2], ctx->buf[3], ctx->dconsts, ctx->slab, ctx->dctrl, ctx->part);
     else
-        hipLaunchKernelGGL((rk45_attempt_kernel<BLK, CPT, LAYOUT_FIELD_MAJOR, VD>), dim3((unsigned)nb), dim3(BLK), 0, ctx->stream, ctx->buf[0],
+        hipLaunchKernelGGL((rk45_attempt_kernel<256, LAYOUT_FIELD_MAJOR, VD>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, ctx->buf[0],
                            ctx->buf[1], ctx->buf[2], ctx->buf[3], ctx->dconsts, ctx->slab, ctx->dctrl, ctx->part);
 }
 
@@ -779,13 +767,10 @@ static const double* reduce_first_level(marl_ctx* ctx, int64_t* nrec)
     return out;
 }
 
-static int launch_attempt(marl_ctx* ctx, int v, int layout)
+static int launch_attempt(marl_ctx* ctx, int layout)
 {
-    const int64_t nb = rk45_blocks(ctx, v);
-    switch (v) {
-        case 0: if (ctx->var_dphi) launch_attempt_t<256, 1, true>(ctx, nb, layout); else launch_attempt_t<256, 1>(ctx, nb, layout); break;
-        default: return fail(ctx, -1, "rk45 variant %d not instantiated", v);
-    }
+    const int64_t nb = rk45_blocks(ctx);
+    if (ctx->var_dphi) launch_attempt_t<true>(ctx, nb, layout); else launch_attempt_t<>(ctx, nb, layout);
     LAUNCH_OK(ctx);
     int64_t nrec = nb;
     const double* recs = reduce_first_level(ctx, &nrec);
@@ -856,7 +841,7 @@ static int launch_rk45_stream_t(marl_ctx* ctx, int layout, int64_t tiles, int64_
 // one after the other and the last runs alone.  N = 65 536: +35 %, 2^19: +7 %, 2^20: -1 %, 2^22: -10 %.  Default: grids of up to
 // three rounds of resident workgroups (N <= ~750 000 cells on 256 CUs); larger grids keep one launch per attempt.
 constexpr int64_t kRk45StreamRounds = 3;
-static bool rk45_use_stream(marl_ctx* ctx, int v)
+static bool rk45_use_stream(marl_ctx* ctx)
 {
     if (ctx->rk45_stream == 0) return false;
     if (ctx->rk45_stream >= 2) return true;
@@ -865,13 +850,13 @@ static bool rk45_use_stream(marl_ctx* ctx, int v)
         if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return false;
         ctx->cus = prop.multiProcessorCount;
     }
-    return rk45_blocks(ctx, v) <= kRk45StreamRounds * 4 * (int64_t)ctx->cus;
+    return rk45_blocks(ctx) <= kRk45StreamRounds * 4 * (int64_t)ctx->cus;
 }
 
-static int launch_rk45_stream(marl_ctx* ctx, int v, int layout, int64_t max_attempts, bool dd = false)
+static int launch_rk45_stream(marl_ctx* ctx, int layout, int64_t max_attempts, bool dd = false)
 {
     if (int rc = rk45_stream_setup(ctx)) return rc;
-    const int64_t tiles = rk45_blocks(ctx, v);
+    const int64_t tiles = rk45_blocks(ctx);
     if (tiles >= (1ll << 31)) return fail(ctx, -1, "rk45 stream: grid too large");
     return ctx->var_dphi ? launch_rk45_stream_t<true>(ctx, layout, tiles, max_attempts, dd) : launch_rk45_stream_t<false>(ctx, layout, tiles, max_attempts, dd);
 }
@@ -894,15 +879,15 @@ static int rk45_stream_account(marl_ctx* ctx, int64_t attempts_in_batch)
     return 0;
 }
 
-template <int BLK, int CPT, bool VD = false>
+template <bool VD = false>
 static void launch_dense_t(marl_ctx* ctx, int64_t nb, int layout, const double* yold, const double* fold, double h,
                            const DenseWeights& dw, double* yout)
 {
     if (layout == LAYOUT_TILED)
-        hipLaunchKernelGGL((rk45_dense_kernel<BLK, CPT, LAYOUT_TILED, VD>), dim3((unsigned)nb), dim3(BLK), 0, ctx->stream, yold, fold, ctx->dconsts,
+        hipLaunchKernelGGL((rk45_dense_kernel<256, LAYOUT_TILED, VD>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, yold, fold, ctx->dconsts,
                            ctx->slab, h, dw, yout, ctx->part);
     else
-        hipLaunchKernelGGL((rk45_dense_kernel<BLK, CPT, LAYOUT_FIELD_MAJOR, VD>), dim3((unsigned)nb), dim3(BLK), 0, ctx->stream, yold, fold,
+        hipLaunchKernelGGL((rk45_dense_kernel<256, LAYOUT_FIELD_MAJOR, VD>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, yold, fold,
                            ctx->dconsts, ctx->slab, h, dw, yout, ctx->part);
 }
 
@@ -918,7 +903,7 @@ static const double kDpP[7][4] = {
 
 // Evaluate the dense output of the LAST accepted step at time t: state into yout (may be NULL) and the
 // seven monitors into g (may be NULL; synchronises when given).
-static int dense_eval(marl_ctx* ctx, int v, int layout, bool small, const Rk45Ctrl& c, double t, double* yout, double* g)
+static int dense_eval(marl_ctx* ctx, int layout, bool small, const Rk45Ctrl& c, double t, double* yout, double* g)
 {
 
     const double x = (t - c.t_old) / c.h_prev;
@@ -931,11 +916,8 @@ static int dense_eval(marl_ctx* ctx, int v, int layout, bool small, const Rk45Ct
     }
     const double* yold = small ? ctx->buf[1] : ctx->buf[c.cur ^ 1];
     const double* fold = small ? ctx->buf[3] : ctx->buf[2 + (c.cur ^ 1)];
-    const int64_t nb = rk45_blocks(ctx, v);
-    switch (v) {
-        case 0: if (ctx->var_dphi) launch_dense_t<256, 1, true>(ctx, nb, layout, yold, fold, c.h_prev, dw, yout); else launch_dense_t<256, 1>(ctx, nb, layout, yold, fold, c.h_prev, dw, yout); break;
-        default: return fail(ctx, -1, "rk45 variant %d not instantiated", v);
-    }
+    const int64_t nb = rk45_blocks(ctx);
+    if (ctx->var_dphi) launch_dense_t<true>(ctx, nb, layout, yold, fold, c.h_prev, dw, yout); else launch_dense_t<>(ctx, nb, layout, yold, fold, c.h_prev, dw, yout);
     LAUNCH_OK(ctx);
     if (g) {
         hipLaunchKernelGGL(reduce_records_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->part, nb, ctx->rec);
@@ -948,7 +930,7 @@ static int dense_eval(marl_ctx* ctx, int v, int layout, bool small, const Rk45Ct
 }
 
 // Brent's method for monitor `e` on the last accepted step (solve_event_equation, ivp.py:51-76)
-static int brent_event(marl_ctx* ctx, int v, int layout, bool small, const Rk45Ctrl& c, int e, double ga, double gb, double* root)
+static int brent_event(marl_ctx* ctx, int layout, bool small, const Rk45Ctrl& c, int e, double ga, double gb, double* root)
 {
     const double xtol = 4 * 2.220446049250313e-16, rtol = xtol;
     double a = c.t_old, b = c.t, fa = ga, fb = gb, g[7];
@@ -972,7 +954,7 @@ static int brent_event(marl_ctx* ctx, int v, int layout, bool small, const Rk45C
         } else { spre = sbis; scur = sbis; }
         xpre = xcur; fpre = fcur;
         if (std::fabs(scur) > delta) xcur += scur; else xcur += (sbis > 0 ? delta : -delta);
-        if (int rc = dense_eval(ctx, v, layout, small, c, xcur, nullptr, g)) return rc;
+        if (int rc = dense_eval(ctx, layout, small, c, xcur, nullptr, g)) return rc;
         fcur = g[e];
     }
     *root = xcur;
@@ -1016,9 +998,8 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
     for (int64_t i = 0; i < n_eval; i++)
         if (t_eval[i] < t0 || t_eval[i] > t1 || (i > 0 && t_eval[i] <= t_eval[i - 1]))
             return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
-    const int v = small ? 0 : default_rk45_variant(ctx);
-    const int sv = small ? default_sweep_variant(ctx) : -1;
-    const int64_t nb = rk45_blocks(ctx, v);
+    const int blk = small ? sweep_block(ctx) : 0;
+    const int64_t nb = rk45_blocks(ctx);
     if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(nb + kReduceGroups, 1024))) return rc;
     const int64_t sd = state_doubles(ctx->slab.n_buf, layout);
     // f(t0, y0) and the monitors at t0
@@ -1044,10 +1025,9 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
     int64_t seen_events[7] = {0, 0, 0, 0, 0, 0, 0};
     Rk45Ctrl& hc = *ctx->hctrl;
     int64_t executed = 0;   // attempts the device has finished, as of the last status read
-    const bool streamed = !small && rk45_use_stream(ctx, v);   // one launch per batch of attempts (rk45_stream_kernel)
+    const bool streamed = !small && rk45_use_stream(ctx);   // one launch per batch of attempts (rk45_stream_kernel)
     while (true) {
         if (small) {
-            const int v = sv;  // SWEEP_DISPATCH switches on `v`
             const dim3 grid(1);
             if (events_on) {   // pauses on monitor sign changes (root finding): the loop shape that decides with this step's events
                 SWEEP_DISPATCH(rk45_sweep_events_kernel, ctx->buf[0], ctx->dconsts, ctx->dctrl, ctx->N, ctx->buf[1], ctx->buf[3])
@@ -1056,11 +1036,11 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
             }
             LAUNCH_OK(ctx);
         } else if (streamed) {
-            if (int rc = launch_rk45_stream(ctx, v, layout, ctx->rk45_stream_attempts)) return rc;
+            if (int rc = launch_rk45_stream(ctx, layout, ctx->rk45_stream_attempts)) return rc;
         } else {
             const int64_t batch = attempts_per_batch(ctx->poll, max_attempts, executed);
             for (int64_t i = 0; i < batch; i++)
-                if (int rc = launch_attempt(ctx, v, layout)) return rc;
+                if (int rc = launch_attempt(ctx, layout)) return rc;
         }
         HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1076,9 +1056,9 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
                 if (hc.n_events[e] > seen_events[e]) {
                     // only the newest sign change can be refined (earlier ones were refined at their own pause)
                     double ga[7];
-                    if (int rc = dense_eval(ctx, v, layout, small, hc, hc.t_old, nullptr, ga)) return rc;
+                    if (int rc = dense_eval(ctx, layout, small, hc, hc.t_old, nullptr, ga)) return rc;
                     double root = hc.ev_last[e];
-                    if (int rc = brent_event(ctx, v, layout, small, hc, e, ga[e], hc.g[e], &root)) return rc;
+                    if (int rc = brent_event(ctx, layout, small, hc, e, ga[e], hc.g[e], &root)) return rc;
                     for (int64_t k = seen_events[e]; k < hc.n_events[e]; k++)
                         if (k < max_events) t_events[e * max_events + k] = root;
                     seen_events[e] = hc.n_events[e];
@@ -1091,7 +1071,7 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
                 double* dst = y_eval_dev + eval_i * sd;
                 if (t_eval[eval_i] <= hc.t_old && hc.n_acc == 1 && t_eval[eval_i] == t0) {
                     HIP_OK(ctx, hipMemcpyAsync(dst, small ? ctx->buf[1] : ctx->buf[hc.cur ^ 1], sizeof(double) * sd, hipMemcpyDeviceToDevice, ctx->stream));
-                } else if (int rc = dense_eval(ctx, v, layout, small, hc, t_eval[eval_i], dst, nullptr)) return rc;
+                } else if (int rc = dense_eval(ctx, layout, small, hc, t_eval[eval_i], dst, nullptr)) return rc;
                 eval_i++;
             }
         } else {
@@ -1189,8 +1169,8 @@ int marl_sweep_rk4_dev(marl_ctx* ctx, double* y_dev, const double* dt, int64_t n
 {
     if (!ctx || !y_dev || !dt || nsteps < 0) return ctx ? fail(ctx, -1, "marl_sweep_rk4_dev: invalid argument") : -1;
     HIP_OK(ctx, hipSetDevice(ctx->device));
-    const int v = default_sweep_variant(ctx);
-    if (v < 0) return fail(ctx, -1, "marl_sweep_rk4_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
+    const int blk = sweep_block(ctx);
+    if (!blk) return fail(ctx, -1, "marl_sweep_rk4_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
     // through the context's pinned buffer: `dt` may be a temporary of the caller (the previous use of hdt has long completed
     // in stream order only if we wait for it - a sweep launch is milliseconds, the wait is free)
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1209,7 +1189,7 @@ int marl_integrate_rk4(marl_ctx* ctx, double* y, double dt, int64_t nsteps)
     const size_t n = (size_t)NF * ctx->N * ctx->batch;
     if (int rc = ensure(ctx, 2, n)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(ctx->buf[2], y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->batch > 1 || default_sweep_variant(ctx) >= 0) {
+    if (ctx->batch > 1 || sweep_block(ctx) > 0) {
         // small grids (one workgroup each, on-chip for all steps) and sweeps
         std::vector<double> dts((size_t)ctx->batch, dt);
         if (int rc = marl_sweep_rk4_dev(ctx, ctx->buf[2], dts.data(), nsteps)) return rc;
@@ -1234,8 +1214,8 @@ int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, doub
     if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
     if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
     HIP_OK(ctx, hipSetDevice(ctx->device));
-    const int v = default_sweep_variant(ctx);
-    if (v < 0) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
+    const int blk = sweep_block(ctx);
+    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
     if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
     hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
                        atol, (int64_t)NF * ctx->N, max_attempts, 0);
@@ -1272,7 +1252,7 @@ int marl_integrate_rk45(marl_ctx* ctx, double* y, double t0, double t1, double f
     if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_rk45: invalid argument") : -1;
     if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_rk45: single-instance context required (use marl_sweep_rk45_dev)");
     HIP_OK(ctx, hipSetDevice(ctx->device));
-    const bool small = default_sweep_variant(ctx) >= 0;
+    const bool small = sweep_block(ctx) > 0;
     const int layout = small ? LAYOUT_FIELD_MAJOR : (int)ctx->host_layout;
     const size_t n = (size_t)NF * ctx->N;
     const size_t sd = (size_t)state_doubles(ctx->N, layout);
@@ -1408,10 +1388,9 @@ int marl_slab_attempt(marl_ctx* ctx, double* rec_dev)
 {
     SLAB_OK(ctx, "marl_slab_attempt")
     if (!rec_dev) return fail(ctx, -1, "marl_slab_attempt: invalid argument");
-    const int v = default_rk45_variant(ctx);
-    const int64_t nb = rk45_blocks(ctx, v);
+    const int64_t nb = rk45_blocks(ctx);
     if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(nb + kReduceGroups, 1024))) return rc;
-    if (ctx->var_dphi) launch_attempt_t<256, 1, true>(ctx, nb, LAYOUT_FIELD_MAJOR); else launch_attempt_t<256, 1>(ctx, nb, LAYOUT_FIELD_MAJOR);
+    if (ctx->var_dphi) launch_attempt_t<true>(ctx, nb, LAYOUT_FIELD_MAJOR); else launch_attempt_t<>(ctx, nb, LAYOUT_FIELD_MAJOR);
     LAUNCH_OK(ctx);
     int64_t nrec = nb;
     const double* recs = reduce_first_level(ctx, &nrec);
@@ -1561,8 +1540,7 @@ int marl_slab_run(marl_ctx* ctx, marl_stats* stats)
     SLAB_OK(ctx, "marl_slab_run")
     if (!stats) return fail(ctx, -1, "marl_slab_run: invalid argument");
     if (!ctx->dd_send) return fail(ctx, -1, "marl_slab_run: call marl_slab_comm_init first");
-    const int v = default_rk45_variant(ctx);
-    const int64_t nb = rk45_blocks(ctx, v);
+    const int64_t nb = rk45_blocks(ctx);
     if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(nb + kReduceGroups, 1024))) return rc;
     const int msg = dd_msg(ctx);
     int64_t executed = 0;
@@ -1570,14 +1548,14 @@ int marl_slab_run(marl_ctx* ctx, marl_stats* stats)
         // ONE slab and no communicator: nothing is exchanged - the single-grid integrator's loop (same kernels, same bits): the persistent
         // launch up to ~750 000 cells, attempt + reduction + control launches above (one launch less per attempt than packing a message
         // nobody reads and unpacking it again)
-        const bool streamed = rk45_use_stream(ctx, v);
+        const bool streamed = rk45_use_stream(ctx);
         while (true) {
             if (streamed) {
-                if (int rc = launch_rk45_stream(ctx, v, LAYOUT_FIELD_MAJOR, ctx->rk45_stream_attempts)) return rc;
+                if (int rc = launch_rk45_stream(ctx, LAYOUT_FIELD_MAJOR, ctx->rk45_stream_attempts)) return rc;
             } else {
                 const int64_t batch = attempts_per_batch(ctx->poll, ctx->dd_max_attempts, executed);
                 for (int64_t i = 0; i < batch; i++)
-                    if (int rc = launch_attempt(ctx, v, LAYOUT_FIELD_MAJOR)) return rc;
+                    if (int rc = launch_attempt(ctx, LAYOUT_FIELD_MAJOR)) return rc;
             }
             HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl), hipMemcpyDeviceToHost, ctx->stream));
             HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1593,7 +1571,7 @@ int marl_slab_run(marl_ctx* ctx, marl_stats* stats)
     // the slab's attempt as ONE launch (rk45_stream_kernel, one attempt, its last workgroup packs the message): two launches + the
     // all-gather per attempt instead of four.  A batch of them is enqueued blindly (attempts after the controller has stopped return
     // at once), so the counters are re-armed by the kernel itself; they must be at zero when the first one starts.
-    const bool dd_stream = ctx->dd_stream == 2 || (ctx->dd_stream == 1 && rk45_use_stream(ctx, v));
+    const bool dd_stream = ctx->dd_stream == 2 || (ctx->dd_stream == 1 && rk45_use_stream(ctx));
     if (dd_stream) {
         if (int rc = rk45_stream_setup(ctx)) return rc;
         if (ctx->rs_arrive_base || ctx->rs_epoch_base || ctx->rs_grab_base)
@@ -1604,9 +1582,9 @@ int marl_slab_run(marl_ctx* ctx, marl_stats* stats)
         const int64_t batch = attempts_per_batch(ctx->poll, ctx->dd_max_attempts, executed);
         for (int64_t i = 0; i < batch; i++) {
             if (dd_stream) {
-                if (int rc = launch_rk45_stream(ctx, v, LAYOUT_FIELD_MAJOR, 1, true)) return rc;
+                if (int rc = launch_rk45_stream(ctx, LAYOUT_FIELD_MAJOR, 1, true)) return rc;
             } else {
-                if (ctx->var_dphi) launch_attempt_t<256, 1, true>(ctx, nb, LAYOUT_FIELD_MAJOR); else launch_attempt_t<256, 1>(ctx, nb, LAYOUT_FIELD_MAJOR);
+                if (ctx->var_dphi) launch_attempt_t<true>(ctx, nb, LAYOUT_FIELD_MAJOR); else launch_attempt_t<>(ctx, nb, LAYOUT_FIELD_MAJOR);
                 LAUNCH_OK(ctx);
                 int64_t nrec = nb;
                 const double* recs = reduce_first_level(ctx, &nrec);

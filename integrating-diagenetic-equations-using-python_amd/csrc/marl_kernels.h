@@ -1,21 +1,29 @@
 // marl_kernels.h - HIP kernels for the five-field RHS and the fused explicit RK time loops (gfx950).
 //
-// Work decomposition (all kernels): a workgroup of BLK threads owns a WINDOW of BLK*CPT
-// consecutive depth cells, CPT consecutive cells per thread, all five fields of a cell in that
-// thread's registers.  A Runge-Kutta stage needs u[i-1], u[i], u[i+1] of the current STAGE state:
-// cells inside a thread come from registers, the two thread-edge cells are exchanged through a
-// double-buffered LDS edge array (one barrier per stage).  Stage vectors K1..Ks never leave
-// registers.  A window is wider than the cells it finally writes by H cells per side; every RHS
-// evaluation invalidates one more cell at each window edge (the halo is recomputed, never
-// communicated), so one launch can advance several stages - a whole RK4 step, NSTEPS RK4 steps, or a
-// whole Dormand-Prince attempt - with ONE read and ONE write of the state: 80 algorithmic bytes per
-// grid-point-step.  Physical boundaries (global cell 0 / N-1) use the ghost-cell rules instead of
-// a halo and are therefore always valid.
+// Work decomposition (all kernels): a workgroup of BLK threads owns a WINDOW of BLK consecutive
+// depth cells, ONE cell per thread, all five fields of the cell in that thread's registers.  A
+// Runge-Kutta stage needs u[i-1], u[i], u[i+1] of the current STAGE state: every thread publishes
+// its cell through a double-buffered LDS edge array and reads its two neighbours' (one barrier per
+// stage).  Stage vectors K1..Ks never leave registers.  A window is wider than the cells it finally
+// writes by H cells per side; every RHS evaluation invalidates one more cell at each window edge
+// (the halo is recomputed, never communicated), so one launch can advance several stages - a whole
+// RK4 step, NSTEPS RK4 steps, or a whole Dormand-Prince attempt - with ONE read and ONE write of the
+// state: 80 algorithmic bytes per grid-point-step.  Physical boundaries (global cell 0 / N-1) use
+// the ghost-cell rules instead of a halo and are therefore always valid.
+//
+// Why only this shape: two others were built, measured and lost.  Several cells per thread (a
+// cells-per-thread template parameter on every kernel here): 2 cells per thread was no faster at any grid size
+// (profiles/r01_lab_reuse_experiments.log).  A one-wave window whose neighbours come
+// from DPP lane shifts instead of LDS, with no barrier (BLK = 64): 3.3 - 3.8 us per
+// additional step at N = 65 536 against 3.64 us for the 256-thread / 16-step kernel - a lone wave
+// of this instruction stream issues one VALU instruction per ~12 cycles with or without the
+// exchange (profiles/r03_lab_n65536.log).  Neither was ever shipped or tested; their code is in the
+// history at the parent of the commit that removed them.
 //
 // State layouts (`LAYOUT`):
 //   FIELD_MAJOR  y[f*ld + i]                         the reference's layout (Evolve_scenario.py:64-65)
 //   TILED        y[(i>>6)*320 + f*64 + (i&63)]       five 512-byte field rows interleaved per 64-cell
-//                                                    tile: one window = one contiguous 40*WIN-byte run
+//                                                    tile: one window = one contiguous 40*BLK-byte run
 #pragma once
 #include <type_traits>
 
@@ -61,21 +69,8 @@ __device__ __forceinline__ double mon_max(double a, double b) { return FINITE ? 
 // ---------------------------------------------------------------------------------------------
 // REUSE = false: no transcendental cache (one-workgroup sweeps on coarse grids, where the stage displacements
 // are far outside the expansions' range).  The cache (marl_math.h, PointCache) also needs its LDS slots to fit
-// the 64 KB a workgroup may declare: wide variants (512 threads, several cells per thread) run without it.
+// the 64 KB a workgroup may declare: the wide blocks (512 threads and more) run without it.
 // VD: the time-varying porosity diffusion coefficient (marl_params.dPhi_variable), see marl_math.h.
-// A lane's neighbour values straight from the neighbouring LANES of its wave (gfx9 DPP wave shifts: two v_mov_b32_dpp per double,
-// VALU speed, no LDS, no barrier).  from_left: lane i receives lane i - 1's value; from_right: lane i + 1's.  Lane 0 / lane 63 receive
-// their own value back - WAVE_TILE windows make those two lanes halo cells whose results are never written.
-__device__ __forceinline__ double wave_from_left(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false));   // wave_shr:1
-}
-__device__ __forceinline__ double wave_from_right(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false));   // wave_shl:1
-}
 
 #ifdef MARL_LAB_PHASE_CLOCK   // kernel-lab build only (tools/rk4_lab.hip): shader-clock cycles per phase of an RHS evaluation, summed over every
 // evaluation of wave 0 of every workgroup: [0] edge writes, [1] own-cell phase (point_local), [2] wait at the exchange barrier, [3] neighbour
@@ -86,21 +81,27 @@ __device__ unsigned long long marl_lab_phase[8];
 #define MARL_PHASE_MARK(k) do { } while (0)
 #endif
 
-template <int BLK, int CPT, bool REUSE = true, bool VD = false>
+// A loop of ONE trip - for the optimiser, not for the reader.  It stands wherever this file used to loop over the cells of a thread
+// around something other than plain arithmetic: the two phases of an evaluation, and the guarded loads and stores of the kernels.  With
+// one cell per thread those loops have no meaning left, but the compiler had been using them: as long as the (later fully unrolled) loop
+// exists, loop-invariant code motion lifts np.sign(W) of the three Peclet weights (marl_math.h, fv_sigma) out of their branches, where
+// value numbering merges them; the physical-boundary branch is laid out without copies on the path that skips it; and the guards keep
+// their polarity and block order, on which the register allocation of the kernels at their cap turns.  Without any of them the fixed-step
+// headline ran 2.1 % slower, N = 65 536 4 %, rk45_single 0.8 %, and rk45_sweep_events_kernel<1024, dPhi_variable> spilled 8 B more; with
+// them every kernel compiles to the machine code it had with the cell loops (profiles/r06_one_cell_per_thread_isa.log).  Nothing but
+// that comparison and the literal-move bounds of tests/test_hot_path_isa.py guards this: after a compiler change, build with and without
+// and keep what measures better.
+#define MARL_ONCE _Pragma("unroll") for (int once_ = 0; once_ < 1; once_++)
+// the five fields of a cell, unrolled (the Runge-Kutta combinations)
+#define MARL_FIELDS _Pragma("unroll") for (int f = 0; f < NF; f++)
+
+template <int BLK, bool REUSE = true, bool VD = false>
 struct StencilBlock {
-    static constexpr int WIN = BLK * CPT;
-    static constexpr int NSIDE = (CPT == 1) ? 1 : 2;
-    // WAVE_TILE (kernel lab only - tools/rk4_lab.hip -DLAB_BLK=64; no shipped kernel instantiates it): the window is ONE wave (64
-    // cells, one per lane): neighbours come from the wave's own lanes by DPP, the two edge lanes are halo - a stage has no LDS
-    // exchange and no barrier.  Built for BASELINE configs[1] (N = 65 536: one or two waves per SIMD), measured, NOT faster: 3.3 -
-    // 3.8 us per additional step at 1.3 - 2 waves per SIMD against 3.64 us for the shipped 256-thread / 16-step kernel - a lone wave
-    // of this instruction stream issues one VALU instruction per ~12 cycles with or without the exchange (profiles/r03_lab_n65536.log)
-    static constexpr bool WAVE_TILE = (BLK == 64 && CPT == 1);
-    static constexpr int EDGE_DOUBLES = WAVE_TILE ? 0 : 2 * NSIDE * NF * BLK;       // edges [parity][side][field][thread]
+    static constexpr int EDGE_DOUBLES = 2 * NF * BLK;       // edges [parity][field][thread]
     static constexpr bool CACHE_LDS = PC_LDS_SLOTS > 0;
-    static constexpr bool CACHE = REUSE && (EDGE_DOUBLES + TABLE_DOUBLES + PC_LDS_SLOTS * WIN) * 8 <= 60 * 1024;
-    static constexpr int CACHE_DOUBLES = CACHE ? PC_LDS_SLOTS * WIN : 0;
-    static constexpr int LDS_DOUBLES = EDGE_DOUBLES + TABLE_DOUBLES + CACHE_DOUBLES;  // edges, log/exp tables, cache slots [slot][cell][thread]
+    static constexpr bool CACHE = REUSE && (EDGE_DOUBLES + TABLE_DOUBLES + PC_LDS_SLOTS * BLK) * 8 <= 60 * 1024;
+    static constexpr int CACHE_DOUBLES = CACHE ? PC_LDS_SLOTS * BLK : 0;
+    static constexpr int LDS_DOUBLES = EDGE_DOUBLES + TABLE_DOUBLES + CACHE_DOUBLES;  // edges, log/exp tables, cache slots [slot][thread]
 
     double* lds;
     Tables T;
@@ -108,27 +109,26 @@ struct StencilBlock {
     const DevConsts* C;          // full constant block (cold members are read on rare paths only)
     int tid;
     int parity;
-    // the thread's c-th cell is global cell 0 (bit c) / global cell N-1 (bit 8 + c) / in the dissolution zone (bit 16 + c): ONE register
+    // the thread's cell is global cell 0 (bit 0) / global cell N-1 (bit 8) / in the dissolution zone (bit 16): ONE register
     // instead of three (it lives across every stage, and the fused integrators sit at their register cap)
-    static_assert(CPT <= 8, "three 8-bit fields");
     unsigned masks;
-    // wave-uniform: bit c is set when the c-th cell of SOME lane of the wave is global cell 0 or N-1 (the ballot of is_edge(c), taken
+    // wave-uniform: set when the cell of SOME lane of the wave is global cell 0 or N-1 (the ballot of is_edge(), taken
     // once per window: re-taken in every evaluation it rebuilt a lane mask in vector registers - two VALU instructions per stage).
     // Only where the transcendental cache is (the fine-grid kernels): in the 1024-thread one-workgroup sweeps, one more value carried
     // through the kernel grows the scratch spill of rk45_sweep_kernel (184 -> 192 B); they keep the ballot per evaluation
     static constexpr bool EDGE_ONCE = CACHE;
     unsigned edge_cells;
-    __device__ __forceinline__ bool edge_wave(int c) const
+    __device__ __forceinline__ bool edge_wave() const
     {
-        if constexpr (EDGE_ONCE) return (edge_cells >> c) & 1u;
-        else return __builtin_amdgcn_ballot_w64(is_edge(c) != 0) != 0;
+        if constexpr (EDGE_ONCE) return edge_cells & 1u;
+        else return __builtin_amdgcn_ballot_w64(is_edge() != 0) != 0;
     }
-    __device__ __forceinline__ unsigned is_first(int c) const { return (masks >> c) & 1u; }
-    __device__ __forceinline__ unsigned is_last(int c) const { return (masks >> (8 + c)) & 1u; }
-    __device__ __forceinline__ unsigned in_zone(int c) const { return (masks >> (16 + c)) & 1u; }
-    __device__ __forceinline__ unsigned is_edge(int c) const { return (masks >> c) & 0x101u; }   // first or last: non-zero
-    PointCache<(CACHE && CACHE_LDS) ? WIN : 0> cache[CACHE ? CPT : 1];  // centre of the transcendental expansions (TR_FILL / TR_REUSE / TR_AUTO)
-    bool reuse_live[CPT] = {};   // wave-uniform, per cell: the centre is filled and no evaluation since has fallen out of range
+    __device__ __forceinline__ unsigned is_first() const { return masks & 1u; }
+    __device__ __forceinline__ unsigned is_last() const { return (masks >> 8) & 1u; }
+    __device__ __forceinline__ unsigned in_zone() const { return (masks >> 16) & 1u; }
+    __device__ __forceinline__ unsigned is_edge() const { return masks & 0x101u; }   // first or last: non-zero
+    PointCache<(CACHE && CACHE_LDS) ? BLK : 0> cache;  // centre of the transcendental expansions (TR_FILL / TR_REUSE / TR_AUTO)
+    bool reuse_live = false;     // wave-uniform: the centre is filled and no evaluation since has fallen out of range
 #ifdef MARL_LAB_PHASE_CLOCK
     unsigned long long ph_acc[6] = {0, 0, 0, 0, 0, 0}, ph_last = __builtin_amdgcn_s_memtime();
     __device__ __forceinline__ void phase_flush()
@@ -139,15 +139,12 @@ struct StencilBlock {
 #endif
 
     // lds: LDS_DOUBLES doubles = edge exchange buffers followed by the log/exp tables (copied here; barrier inside).
-    // g0: global index of this thread's first cell.
+    // g0: global index of this thread's cell.
     __device__ __forceinline__ StencilBlock(double* lds_, int64_t g0, const DevConsts* __restrict__ c)
         : lds(lds_), T(load_tables(lds_ + EDGE_DOUBLES, BLK)), K(load_hot(c)), C(c), tid(threadIdx.x), parity(0)
     {
         set_window(g0);
-        if constexpr (CACHE && CACHE_LDS) {
-#pragma unroll
-            for (int c = 0; c < CPT; c++) cache[c].s = lds_ + EDGE_DOUBLES + TABLE_DOUBLES + c * BLK + tid;
-        }
+        if constexpr (CACHE && CACHE_LDS) cache.s = lds_ + EDGE_DOUBLES + TABLE_DOUBLES + tid;
     }
 
     // Persistent kernels: the per-thread members again, from an index the caller has made opaque inside its work loop - everything
@@ -156,75 +153,32 @@ struct StencilBlock {
     __device__ __forceinline__ void rebind(int t)
     {
         tid = t;
-        if constexpr (CACHE && CACHE_LDS) {
-#pragma unroll
-            for (int c = 0; c < CPT; c++) cache[c].s = lds + EDGE_DOUBLES + TABLE_DOUBLES + c * BLK + t;
-        }
+        if constexpr (CACHE && CACHE_LDS) cache.s = lds + EDGE_DOUBLES + TABLE_DOUBLES + t;
     }
 
-    // (Re)position the window.
-    __device__ __forceinline__ void set_window(int64_t g0)
+    // (Re)position the window: g = global index of this thread's cell.
+    __device__ __forceinline__ void set_window(int64_t g)
     {
         const int64_t N = C->N, mlo = C->mask_lo, mhi = C->mask_hi;
-        masks = 0;
-#pragma unroll
-        for (int i = 0; i < CPT; i++) {
-            const int64_t g = g0 + i;
-            masks |= ((g == 0) ? (1u << i) : 0u) | ((g == N - 1) ? (0x100u << i) : 0u) | ((g >= mlo && g < mhi) ? (0x10000u << i) : 0u);
-        }
+        masks = ((g == 0) ? 1u : 0u) | ((g == N - 1) ? 0x100u : 0u) | ((g >= mlo && g < mhi) ? 0x10000u : 0u);
         edge_cells = 0;
-        if constexpr (EDGE_ONCE) {
-#pragma unroll
-            for (int i = 0; i < CPT; i++) edge_cells |= (__builtin_amdgcn_ballot_w64(is_edge(i) != 0) != 0) ? (1u << i) : 0u;
-        }
+        if constexpr (EDGE_ONCE) edge_cells = (__builtin_amdgcn_ballot_w64(is_edge() != 0) != 0) ? 1u : 0u;
     }
 
-    // k[c] = RHS(stage state ys) for the thread's CPT cells.  Contains exactly one __syncthreads(): the own-cell phase
+    // k = RHS(stage state ys) for the thread's cell.  Contains exactly one __syncthreads(): the own-cell phase
     // of the evaluation (marl_math.h, point_local) runs between the edge writes and the barrier, the stencil phase
     // after it - the neighbour values are not live during the transcendental part.
     // MODE: see marl_math.h (TR_FILL / TR_AUTO for a first stage, TR_REUSE for the following ones, TR_PLAIN otherwise).
     template <int MODE = TR_PLAIN>
-    __device__ __forceinline__ void eval(const double (&ys)[CPT][NF], double (&k)[CPT][NF], PointAux (&aux)[CPT])
+    __device__ __forceinline__ void eval(const double (&ys)[NF], double (&k)[NF], PointAux& aux)
     {
-        if constexpr (WAVE_TILE) {
-            PointLocal pl;
-            point_local<CACHE ? MODE : TR_PLAIN, (CACHE && CACHE_LDS) ? WIN : 0, VD>(ys[0], in_zone(0), K, C, T, pl, aux[0], cache[0], reuse_live[0]);
-            double um[NF], up[NF];
-#pragma unroll
-            for (int f = 0; f < NF; f++) um[f] = wave_from_left(ys[0][f]);
-            const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl.upw) != 0;
-#pragma unroll
-            for (int f = 0; f < NF; f++) up[f] = (f >= 2 || need_right_solids) ? wave_from_right(ys[0][f]) : 0.0;
-            if (edge_wave(0)) {   // physical boundaries: two cells of the whole grid
-                if (is_last(0)) {
-#pragma unroll
-                    for (int f = 0; f < NF; f++) up[f] = ghost_upper(f, ys[0][f], um[f]);
-                }
-                if (is_first(0)) {
-#pragma unroll
-                    for (int f = 0; f < NF; f++) um[f] = ghost_lower(C->bc[f], ys[0][f]);
-                }
-            }
-            point_rates<VD, true, !CACHE>(ys[0], um, up, K, T, pl, k[0], need_right_solids);
-            return;
-        }
         MARL_PHASE_MARK(4);
-        double* e = lds + parity * (NSIDE * NF * BLK);
+        double* e = lds + parity * (NF * BLK);
 #pragma unroll
-        for (int f = 0; f < NF; f++) {
-            e[f * BLK + tid] = ys[0][f];
-            if constexpr (CPT > 1) e[(NF + f) * BLK + tid] = ys[CPT - 1][f];
-        }
+        for (int f = 0; f < NF; f++) e[f * BLK + tid] = ys[f];
         MARL_PHASE_MARK(0);
-        PointLocal pl[CPT];
-#pragma unroll
-        for (int c = 0; c < CPT; c++) {
-            point_local<CACHE ? MODE : TR_PLAIN, (CACHE && CACHE_LDS) ? WIN : 0, VD>(ys[c], in_zone(c), K, C, T, pl[c], aux[c], cache[CACHE ? c : 0], reuse_live[c]);
-            // one cell at a time: interleaving the cells' evaluations doubles the live temporaries (spills at CPT >= 2)
-#ifndef MARL_LAB_INTERLEAVE_CELLS   // (kernel-lab switch: let the scheduler interleave the cells of a thread - ILP instead of registers)
-            if constexpr (CPT > 1) __builtin_amdgcn_sched_barrier(0);
-#endif
-        }
+        PointLocal pl;
+        MARL_ONCE point_local<CACHE ? MODE : TR_PLAIN, (CACHE && CACHE_LDS) ? BLK : 0, VD>(ys, in_zone(), K, C, T, pl, aux, cache, reuse_live);
         MARL_PHASE_MARK(1);
         __syncthreads();
         MARL_PHASE_MARK(2);
@@ -232,13 +186,13 @@ struct StencilBlock {
         const int tr = tid < BLK - 1 ? tid + 1 : BLK - 1;
         double left[NF], right[NF];
 #pragma unroll
-        for (int f = 0; f < NF; f++) left[f] = e[((NSIDE - 1) * NF + f) * BLK + tl];  // left neighbour's LAST cell
+        for (int f = 0; f < NF; f++) left[f] = e[f * BLK + tl];
         // the solids are differenced against the upwind neighbour only: with U > 0 in every lane (burial - the normal
         // case) the right-hand values of CA and CC are never used and their two LDS reads are skipped
-        const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl[CPT - 1].upw) != 0;
-        if constexpr (CPT == 1 && CACHE) {
+        const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl.upw) != 0;
+        if constexpr (CACHE) {
 #pragma unroll
-            for (int f = 2; f < NF; f++) right[f] = e[f * BLK + tr];   // right neighbour's FIRST cell
+            for (int f = 2; f < NF; f++) right[f] = e[f * BLK + tr];
             // a wave-uniform branch around the two reads; without them right[0], right[1] hold whatever their registers held: point_rates,
             // told that no lane mixes upwind directions, does not read them (a 0.0 put there instead costs a v_mov_b64 each, every stage;
             // so does a plain unset value, which the compiler materialises as 0 - the empty asm defines them without an instruction)
@@ -249,32 +203,28 @@ struct StencilBlock {
             }
         } else {   // (the one-workgroup sweeps keep the select form: the branch grows rk45_sweep_kernel's scratch)
 #pragma unroll
-            for (int f = 0; f < NF; f++) right[f] = (f >= 2 || need_right_solids) ? e[f * BLK + tr] : 0.0;  // right neighbour's FIRST cell
+            for (int f = 0; f < NF; f++) right[f] = (f >= 2 || need_right_solids) ? e[f * BLK + tr] : 0.0;
         }
         parity ^= 1;
-#pragma unroll
-        for (int c = 0; c < CPT; c++) {
+        MARL_ONCE {   // the stencil phase: the neighbours as read, or the ghost cells in their place
             double um[NF], up[NF];
 #pragma unroll
-            for (int f = 0; f < NF; f++) {
-                um[f] = (c == 0) ? left[f] : ys[c > 0 ? c - 1 : 0][f];
-                up[f] = (c == CPT - 1) ? right[f] : ys[c < CPT - 1 ? c + 1 : c][f];
-            }
+            for (int f = 0; f < NF; f++) { um[f] = left[f]; up[f] = right[f]; }
             // physical boundaries: two cells of the whole grid - a wave-uniform branch, skipped by every other wave
-            if (edge_wave(c)) {
-                if (is_last(c)) {
+            if (edge_wave()) {
+                if (is_last()) {
 #pragma unroll
-                    for (int f = 0; f < NF; f++) up[f] = ghost_upper(f, ys[c][f], um[f]);
+                    for (int f = 0; f < NF; f++) up[f] = ghost_upper(f, ys[f], um[f]);
                 }
-                if (is_first(c)) {
+                if (is_first()) {
 #pragma unroll
-                    for (int f = 0; f < NF; f++) um[f] = ghost_lower(C->bc[f], ys[c][f]);
+                    for (int f = 0; f < NF; f++) um[f] = ghost_lower(C->bc[f], ys[f]);
                 }
             }
-            point_rates<VD, true, !CACHE>(ys[c], um, up, K, T, pl[c], k[c], CPT == 1 ? need_right_solids : true);
+            point_rates<VD, true, !CACHE>(ys, um, up, K, T, pl, k, need_right_solids);
         }
 #ifdef MARL_LAB_PHASE_CLOCK
-        asm volatile("" :: "v"(k[0][0]), "v"(k[0][4]));   // (the rates are complete before the mark)
+        asm volatile("" :: "v"(k[0]), "v"(k[4]));   // (the rates are complete before the mark)
         MARL_PHASE_MARK(3);
         ph_acc[5]++;
 #endif
@@ -523,19 +473,14 @@ __global__ void __launch_bounds__(256) reduce_chunks_kernel(const double* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// Shared load / store of a thread's cells
+// Shared load of a thread's cell
 // ---------------------------------------------------------------------------------------------
-template <int CPT, int LAYOUT>
-__device__ __forceinline__ void load_cells(const double* __restrict__ y, int64_t l0, const Slab& S, const DevConsts& C,
-                                           double (&u)[CPT][NF])
+template <int LAYOUT>
+__device__ __forceinline__ void load_cells(const double* __restrict__ y, int64_t l, const Slab& S, const DevConsts& C, double (&u)[NF])
 {
+    const bool in = l >= 0 && l < S.n_buf;
 #pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        const int64_t l = l0 + c;
-        const bool in = l >= 0 && l < S.n_buf;
-#pragma unroll
-        for (int f = 0; f < NF; f++) u[c][f] = in ? y[at<LAYOUT>(f, l, S.ld)] : C.bc[f];
-    }
+    for (int f = 0; f < NF; f++) u[f] = in ? y[at<LAYOUT>(f, l, S.ld)] : C.bc[f];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -546,45 +491,32 @@ __device__ __forceinline__ void load_cells(const double* __restrict__ y, int64_t
 #ifdef MARL_LAB_CLOCK  // kernel-lab diagnostic build only: in-kernel shader clock (s_memtime) vs 100 MHz s_memrealtime
 __device__ unsigned long long marl_lab_clock[3 * 16384];
 #endif
-// NSTEPS classical RK4 steps on the thread's cells (every evaluation invalidates one more cell per window edge).
-template <int NSTEPS, class SB, int CPT>
-__device__ __forceinline__ void rk4_advance(SB& sb, double (&y)[CPT][NF], double dt)
+// NSTEPS classical RK4 steps on the thread's cell (every evaluation invalidates one more cell per window edge).
+template <int NSTEPS, class SB>
+__device__ __forceinline__ void rk4_advance(SB& sb, double (&y)[NF], double dt)
 {
-    double ys[CPT][NF], k[CPT][NF], acc[CPT][NF];
-    PointAux aux[CPT];
+    double ys[NF], k[NF], acc[NF];
+    PointAux aux;
     const double h2 = 0.5 * dt, h6 = dt / 6.0;
 #pragma unroll 1
     for (int step = 0; step < NSTEPS; step++) {
         sb.template eval<TR_AUTO>(y, k, aux);   // the centre of the expansions survives from step to step
-#pragma unroll
-        for (int c = 0; c < CPT; c++)
-#pragma unroll
-            for (int f = 0; f < NF; f++) { acc[c][f] = k[c][f]; ys[c][f] = y[c][f] + h2 * k[c][f]; }
+        MARL_FIELDS { acc[f] = k[f]; ys[f] = y[f] + h2 * k[f]; }
         sb.template eval<TR_REUSE>(ys, k, aux);
-#pragma unroll
-        for (int c = 0; c < CPT; c++)
-#pragma unroll
-            for (int f = 0; f < NF; f++) { acc[c][f] = acc[c][f] + 2.0 * k[c][f]; ys[c][f] = y[c][f] + h2 * k[c][f]; }
+        MARL_FIELDS { acc[f] = acc[f] + 2.0 * k[f]; ys[f] = y[f] + h2 * k[f]; }
         sb.template eval<TR_REUSE>(ys, k, aux);
-#pragma unroll
-        for (int c = 0; c < CPT; c++)
-#pragma unroll
-            for (int f = 0; f < NF; f++) { acc[c][f] = acc[c][f] + 2.0 * k[c][f]; ys[c][f] = y[c][f] + dt * k[c][f]; }
+        MARL_FIELDS { acc[f] = acc[f] + 2.0 * k[f]; ys[f] = y[f] + dt * k[f]; }
         sb.template eval<TR_REUSE>(ys, k, aux);
-#pragma unroll
-        for (int c = 0; c < CPT; c++)
-#pragma unroll
-            for (int f = 0; f < NF; f++) y[c][f] = y[c][f] + h6 * (acc[c][f] + k[c][f]);
+        MARL_FIELDS y[f] = y[f] + h6 * (acc[f] + k[f]);
     }
 }
 
-// One cell per thread: 4 waves per SIMD (<= 128 VGPRs; 4 workgroups of 256 share the CU's 160 KB of LDS).
-// Variants with more cells per thread keep the compiler's own choice.
+// 4 waves per SIMD (<= 128 VGPRs; 4 workgroups of 256 share the CU's 160 KB of LDS).
 #ifndef MARL_LAB_RK4_WAVES_MIN   // kernel-lab switch: occupancy window the register allocator aims at
-#define MARL_LAB_RK4_WAVES_MIN (CPT == 1 ? 4 : 1)
+#define MARL_LAB_RK4_WAVES_MIN 4
 #define MARL_LAB_RK4_WAVES_MAX 8
 #endif
-template <int BLK, int CPT, int LAYOUT, int NSTEPS, bool VD = false>
+template <int BLK, int LAYOUT, int NSTEPS, bool VD = false>
 __global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(MARL_LAB_RK4_WAVES_MIN, MARL_LAB_RK4_WAVES_MAX))) rk4_fused_kernel(const double* __restrict__ yin, double* __restrict__ yout,
                                                         const DevConsts* __restrict__ consts, Slab S, double dt)
 {
@@ -592,28 +524,25 @@ __global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(MARL_L
     const unsigned long long lab_t0 = __builtin_amdgcn_s_memtime(), lab_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
     constexpr int H = 4 * NSTEPS;
-    constexpr int WIN = BLK * CPT;
-    constexpr int V = WIN - 2 * H;
+    constexpr int V = BLK - 2 * H;
     static_assert(V > 0, "window too small for the fused halo");
-    using SB = StencilBlock<BLK, CPT, true, VD>;
+    using SB = StencilBlock<BLK, true, VD>;
     __shared__ double lds[SB::LDS_DOUBLES];
     const DevConsts& C = consts[0];
 
     const int64_t w0 = S.out_lo + (int64_t)blockIdx.x * V - H;  // window start, local index
-    const int64_t l0 = w0 + (int64_t)threadIdx.x * CPT;
-    double y[CPT][NF];
-    load_cells<CPT, LAYOUT>(yin, l0, S, C, y);              // in flight while the tables are staged
-    SB sb(lds, l0 + S.goff, consts);   // (table copy + barrier inside)
+    const int64_t l = w0 + (int64_t)threadIdx.x;
+    double y[NF];
+    load_cells<LAYOUT>(yin, l, S, C, y);              // in flight while the tables are staged
+    SB sb(lds, l + S.goff, consts);   // (table copy + barrier inside)
     rk4_advance<NSTEPS>(sb, y, dt);
 
+    const int wi = threadIdx.x;
+    // (MARL_ONCE: see its definition - here it keeps the prologue's scalar loads and spills where they were; without it the 16-step
+    // kernel of marl_rk4_small.hip, opcode for opcode the same in its stages, ran 2.1 % slower at N = 65 536)
+    MARL_ONCE if (wi >= H && wi < BLK - H && l >= S.out_lo && l < S.out_hi) {
 #pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        const int wi = threadIdx.x * CPT + c;
-        const int64_t l = l0 + c;
-        if (wi >= H && wi < WIN - H && l >= S.out_lo && l < S.out_hi) {
-#pragma unroll
-            for (int f = 0; f < NF; f++) yout[at<LAYOUT>(f, l, S.ld)] = y[c][f];
-        }
+        for (int f = 0; f < NF; f++) yout[at<LAYOUT>(f, l, S.ld)] = y[f];
     }
 #ifdef MARL_LAB_PHASE_CLOCK
     sb.phase_flush();
@@ -663,10 +592,9 @@ rk4_stream_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ cons
     // caller's buffer and the whole-state copy that an odd level count used to need afterwards (42 MB at N = 2^20: 12 us of a 20-step
     // call) goes away.  The write-after-read distance is that of the two-buffer scheme (a level writes what the level before reads, and
     // done[tile +- 1] orders it); the last level writes A, which only level 0 reads - five or more tiles of dependency away.
-    constexpr int CPT = 1;
     constexpr int H = 4 * NSTEPS;
     constexpr int V = BLK - 2 * H;
-    using SB = StencilBlock<BLK, CPT, true, VD>;
+    using SB = StencilBlock<BLK, true, VD>;
     __shared__ double lds[SB::LDS_DOUBLES];
     __shared__ unsigned s_item, s_abort;
     const DevConsts& C = consts[0];
@@ -721,16 +649,16 @@ rk4_stream_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ cons
         double* dst = bufC ? (level + 1 == levels ? bufA : ((level & 1u) ? bufC : bufB)) : ((level & 1u) ? bufA : bufB);
         const int64_t l = S.out_lo + (int64_t)tile * V - H + threadIdx.x;
         const bool in = l >= 0 && l < S.n_buf;
-        double y[CPT][NF];
+        double y[NF];
 #pragma unroll
         for (int f = 0; f < NF; f++)
-            y[0][f] = in ? __hip_atomic_load(src + at<LAYOUT>(f, l, S.ld), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : C.bc[f];
+            y[f] = in ? __hip_atomic_load(src + at<LAYOUT>(f, l, S.ld), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : C.bc[f];
         sb.set_window(l + S.goff);
-        sb.reuse_live[0] = false;
+        sb.reuse_live = false;
         rk4_advance<NSTEPS>(sb, y, dt);
         if ((int)threadIdx.x >= H && (int)threadIdx.x < BLK - H && l >= S.out_lo && l < S.out_hi) {
 #pragma unroll
-            for (int f = 0; f < NF; f++) __hip_atomic_store(dst + at<LAYOUT>(f, l, S.ld), y[0][f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int f = 0; f < NF; f++) __hip_atomic_store(dst + at<LAYOUT>(f, l, S.ld), y[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
         __builtin_amdgcn_s_waitcnt(0);   // this thread's stores have been acknowledged (vmcnt = expcnt = lgkmcnt = 0)
@@ -1037,49 +965,46 @@ __global__ void __launch_bounds__(CONTROL_THREADS) rk45_control_kernel(const dou
 struct DenseWeights { double w[7]; };
 
 // PARK = number of fields (0..5) of the step's first state y that are NOT held in registers but in this thread's LDS column
-// `pk` (pk[(c*NF + f) * BLK], f < PARK) and re-read where a stage state is formed - up to five live doubles less across every
+// `pk` (pk[f * BLK], f < PARK) and re-read where a stage state is formed - up to five live doubles less across every
 // evaluation (kernels that sit just above a register cap: 128 VGPRs = 4 waves per SIMD).
-template <int BLK, int CPT, bool DENSE = false, class SB = StencilBlock<BLK, CPT>, int PARK = 0>
-__device__ __forceinline__ void dp45_attempt(SB& sb, double h,
-                                             const double (&y)[CPT][NF], const double (&k1)[CPT][NF],
-                                             double (&yn)[CPT][NF], double (&k7)[CPT][NF], double (&esum)[CPT][NF],
-                                             PointAux (&aux)[CPT], const DenseWeights& dw = DenseWeights{}, const double* pk = nullptr)
+template <int BLK, bool DENSE = false, class SB = StencilBlock<BLK>, int PARK = 0>
+__device__ __forceinline__ void dp45_attempt(SB& sb, double h, const double (&y)[NF], const double (&k1)[NF],
+                                             double (&yn)[NF], double (&k7)[NF], double (&esum)[NF],
+                                             PointAux& aux, const DenseWeights& dw = DenseWeights{}, const double* pk = nullptr)
 {
     const double e1 = DENSE ? dw.w[0] : dp::E1, e3 = DENSE ? dw.w[2] : dp::E3, e4 = DENSE ? dw.w[3] : dp::E4;
     const double e5 = DENSE ? dw.w[4] : dp::E5, e6 = DENSE ? dw.w[5] : dp::E6, e7 = DENSE ? dw.w[6] : dp::E7;
     // K1..K4 are folded into the partial sums of everything that still needs them as soon as K4 exists, so that at
     // most five vectors (instead of seven) are live across an evaluation.  The order of every
     // sum is the left-to-right order of np.dot(K[:s].T, a[:s]) (rk.py:61-69).
-    double ys[CPT][NF], k2[CPT][NF], k3[CPT][NF], k4[CPT][NF], kk[CPT][NF], s6[CPT][NF], bn[CPT][NF];
-#define MARL_CELLS _Pragma("unroll") for (int c = 0; c < CPT; c++) _Pragma("unroll") for (int f = 0; f < NF; f++)
-#define MARL_Y(c, f) ((f) < PARK ? pk[((c) * NF + (f)) * BLK] : y[c][f])
-    MARL_CELLS ys[c][f] = MARL_Y(c, f) + (k1[c][f] * dp::A21) * h;
+    double ys[NF], k2[NF], k3[NF], k4[NF], kk[NF], s6[NF], bn[NF];
+#define MARL_Y(f) ((f) < PARK ? pk[(f) * BLK] : y[f])
+    MARL_FIELDS ys[f] = MARL_Y(f) + (k1[f] * dp::A21) * h;
     sb.template eval<TR_FILL>(ys, k2, aux);
-    MARL_CELLS ys[c][f] = MARL_Y(c, f) + (k1[c][f] * dp::A31 + k2[c][f] * dp::A32) * h;
+    MARL_FIELDS ys[f] = MARL_Y(f) + (k1[f] * dp::A31 + k2[f] * dp::A32) * h;
     sb.template eval<TR_REUSE>(ys, k3, aux);
-    MARL_CELLS ys[c][f] = MARL_Y(c, f) + (k1[c][f] * dp::A41 + k2[c][f] * dp::A42 + k3[c][f] * dp::A43) * h;
+    MARL_FIELDS ys[f] = MARL_Y(f) + (k1[f] * dp::A41 + k2[f] * dp::A42 + k3[f] * dp::A43) * h;
     sb.template eval<TR_REUSE>(ys, k4, aux);
-    MARL_CELLS {
-        ys[c][f] = MARL_Y(c, f) + (k1[c][f] * dp::A51 + k2[c][f] * dp::A52 + k3[c][f] * dp::A53 + k4[c][f] * dp::A54) * h;
-        s6[c][f] = k1[c][f] * dp::A61 + k2[c][f] * dp::A62 + k3[c][f] * dp::A63 + k4[c][f] * dp::A64;
-        bn[c][f] = k1[c][f] * dp::B1 + k3[c][f] * dp::B3 + k4[c][f] * dp::B4;
-        esum[c][f] = k1[c][f] * e1 + k3[c][f] * e3 + k4[c][f] * e4;
+    MARL_FIELDS {
+        ys[f] = MARL_Y(f) + (k1[f] * dp::A51 + k2[f] * dp::A52 + k3[f] * dp::A53 + k4[f] * dp::A54) * h;
+        s6[f] = k1[f] * dp::A61 + k2[f] * dp::A62 + k3[f] * dp::A63 + k4[f] * dp::A64;
+        bn[f] = k1[f] * dp::B1 + k3[f] * dp::B3 + k4[f] * dp::B4;
+        esum[f] = k1[f] * e1 + k3[f] * e3 + k4[f] * e4;
     }
     sb.template eval<TR_REUSE>(ys, kk, aux);   // K5
-    MARL_CELLS {
-        ys[c][f] = MARL_Y(c, f) + (s6[c][f] + kk[c][f] * dp::A65) * h;
-        bn[c][f] = bn[c][f] + kk[c][f] * dp::B5;
-        esum[c][f] = esum[c][f] + kk[c][f] * e5;
+    MARL_FIELDS {
+        ys[f] = MARL_Y(f) + (s6[f] + kk[f] * dp::A65) * h;
+        bn[f] = bn[f] + kk[f] * dp::B5;
+        esum[f] = esum[f] + kk[f] * e5;
     }
     sb.template eval<TR_REUSE>(ys, kk, aux);   // K6
-    MARL_CELLS {
-        yn[c][f] = MARL_Y(c, f) + h * (bn[c][f] + kk[c][f] * dp::B6);
-        esum[c][f] = esum[c][f] + kk[c][f] * e6;
+    MARL_FIELDS {
+        yn[f] = MARL_Y(f) + h * (bn[f] + kk[f] * dp::B6);
+        esum[f] = esum[f] + kk[f] * e6;
     }
     sb.template eval<TR_REUSE>(yn, k7, aux);
-    MARL_CELLS esum[c][f] = esum[c][f] + k7[c][f] * e7;
+    MARL_FIELDS esum[f] = esum[f] + k7[f] * e7;
 #undef MARL_Y
-#undef MARL_CELLS
 }
 
 // (err/scale)^2 of one component; scale = atol + max(|y|, |y_new|) * rtol  (rk.py:146-147)
@@ -1138,27 +1063,26 @@ __device__ __forceinline__ double tile_reduce_halfwaves(const double (&q)[NQ], d
 // (y, f) from buffer `cur`, writes (y_new, f_new) into the other buffer and one reduction record per
 // block; rk45_control_kernel then accepts (flips `cur`) or rejects.  FSAL: f_new becomes K1.
 // ---------------------------------------------------------------------------------------------
-// One cell per thread in 256-thread blocks: 4 waves per SIMD (<= 128 VGPRs) with ATTEMPT_PARK fields of y parked in LDS
+// 256-thread blocks: 4 waves per SIMD (<= 128 VGPRs) with ATTEMPT_PARK fields of y parked in LDS
 // (4 blocks per CU leave 9 KB of LDS per block beside the edge buffers, tables and cache slots; three parked doubles = 6 KB suffice: 128 VGPRs, no scratch).
 #ifndef MARL_ATTEMPT_PARK
 #define MARL_ATTEMPT_PARK 3
 #endif
-template <int BLK, int CPT>
-constexpr int ATTEMPT_PARK = (BLK == 256 && CPT == 1) ? MARL_ATTEMPT_PARK : 0;
+template <int BLK>
+constexpr int ATTEMPT_PARK = (BLK == 256) ? MARL_ATTEMPT_PARK : 0;
 
-template <int BLK, int CPT, int LAYOUT, bool VD = false>
-__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu((BLK == 256 && CPT == 1 && MARL_ATTEMPT_PARK > 0) ? 4 : 1, 8)))
+template <int BLK, int LAYOUT, bool VD = false>
+__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu((BLK == 256 && MARL_ATTEMPT_PARK > 0) ? 4 : 1, 8)))
 rk45_attempt_kernel(double* __restrict__ Y0, double* __restrict__ Y1,
                                                            double* __restrict__ F0, double* __restrict__ F1,
                                                            const DevConsts* __restrict__ consts, Slab S,
                                                            const Rk45Ctrl* __restrict__ ctrl, double* __restrict__ part)
 {
     constexpr int H = 6;
-    constexpr int WIN = BLK * CPT;
-    constexpr int V = WIN - 2 * H;
-    constexpr int PARK = ATTEMPT_PARK<BLK, CPT>;
-    using SB = StencilBlock<BLK, CPT, true, VD>;
-    __shared__ double lds[SB::LDS_DOUBLES + PARK * CPT * BLK];
+    constexpr int V = BLK - 2 * H;
+    constexpr int PARK = ATTEMPT_PARK<BLK>;
+    using SB = StencilBlock<BLK, true, VD>;
+    __shared__ double lds[SB::LDS_DOUBLES + PARK * BLK];
     if (ctrl->status != ST_RUNNING) return;
     const DevConsts& C = consts[0];
     const int cur = ctrl->cur;
@@ -1169,46 +1093,36 @@ rk45_attempt_kernel(double* __restrict__ Y0, double* __restrict__ Y1,
     double* fout = cur ? F0 : F1;
 
     const int64_t w0 = S.out_lo + (int64_t)blockIdx.x * V - H;
-    const int64_t l0 = w0 + (int64_t)threadIdx.x * CPT;
+    const int64_t l = w0 + (int64_t)threadIdx.x;
 
-    double y[CPT][NF], k1[CPT][NF], yn[CPT][NF], k7[CPT][NF], esum[CPT][NF];
-    PointAux aux[CPT];
-    load_cells<CPT, LAYOUT>(yin, l0, S, C, y);              // in flight while the tables are staged
-#pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        const int64_t l = l0 + c;
+    double y[NF], k1[NF], yn[NF], k7[NF], esum[NF];
+    PointAux aux;
+    load_cells<LAYOUT>(yin, l, S, C, y);              // in flight while the tables are staged
+    MARL_ONCE {
         const bool in = l >= 0 && l < S.n_buf;
 #pragma unroll
-        for (int f = 0; f < NF; f++) k1[c][f] = in ? fin[at<LAYOUT>(f, l, S.ld)] : 0.0;
+        for (int f = 0; f < NF; f++) k1[f] = in ? fin[at<LAYOUT>(f, l, S.ld)] : 0.0;
     }
-    SB sb(lds, l0 + S.goff, consts);   // (table copy + barrier inside)
+    SB sb(lds, l + S.goff, consts);   // (table copy + barrier inside)
     double* pk = lds + SB::LDS_DOUBLES + threadIdx.x;
-    if constexpr (PARK > 0) {
 #pragma unroll
-        for (int c = 0; c < CPT; c++)
-#pragma unroll
-            for (int f = 0; f < PARK; f++) pk[(c * NF + f) * BLK] = y[c][f];
-    }
-    dp45_attempt<BLK, CPT, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+    for (int f = 0; f < PARK; f++) pk[f * BLK] = y[f];
+    dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
 
     double q[NQ];
     monitors_init(q);
+    const int wi = threadIdx.x;
+    MARL_ONCE if (wi >= H && wi < BLK - H && l >= S.out_lo && l < S.out_hi) {
 #pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        const int wi = threadIdx.x * CPT + c;
-        const int64_t l = l0 + c;
-        if (wi >= H && wi < WIN - H && l >= S.out_lo && l < S.out_hi) {
-#pragma unroll
-            for (int f = 0; f < NF; f++) {
-                yout[at<LAYOUT>(f, l, S.ld)] = yn[c][f];
-                fout[at<LAYOUT>(f, l, S.ld)] = k7[c][f];
-                q[0] += dp45_err2(esum[c][f], h, f < PARK ? pk[(c * NF + f) * BLK] : y[c][f], yn[c][f], rtol, atol);
-            }
-            monitors_accumulate<true>(q, yn[c], aux[c].U, aux[c].W);   // (the controller reads the extrema of ACCEPTED attempts only: all finite)
+        for (int f = 0; f < NF; f++) {
+            yout[at<LAYOUT>(f, l, S.ld)] = yn[f];
+            fout[at<LAYOUT>(f, l, S.ld)] = k7[f];
+            q[0] += dp45_err2(esum[f], h, f < PARK ? pk[f * BLK] : y[f], yn[f], rtol, atol);
         }
+        monitors_accumulate<true>(q, yn, aux.U, aux.W);   // (the controller reads the extrema of ACCEPTED attempts only: all finite)
     }
 #ifndef MARL_LAB_ATTEMPT_BLOCK_REDUCE   // (kernel-lab switch: the round-1 four-barrier reduction)
-    if constexpr (BLK == 256 && CPT == 1 && PARK >= 3 && SB::CACHE && PC_LDS_SLOTS >= 4) {
+    if constexpr (BLK == 256 && PARK >= 3 && SB::CACHE && PC_LDS_SLOTS >= 4) {
         // one barrier instead of four: columns in LDS areas this thread / every wave has finished with (tile_reduce_halfwaves)
         const double r = tile_reduce_halfwaves<BLK, SB>(q, lds, threadIdx.x);
         if ((threadIdx.x & 31) == 0) {
@@ -1317,7 +1231,6 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
     // barrier's last workgroup, instead of deciding, writes the rank's message [record (8) | lower strip | upper strip] (what
     // reduce_chunks_kernel + slab_reduce_pack_kernel did) and re-arms the counters; the all-gather and slab_unpack_control_kernel
     // follow, and the next launch reads the common decision out of *ctrl.
-    constexpr int CPT = 1;
     constexpr int H = 6;
     constexpr int V = BLK - 2 * H;
     constexpr int PARK = MARL_STREAM_PARK;
@@ -1325,8 +1238,8 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
     constexpr int CTRL_WORDS = (int)(sizeof(Rk45Ctrl) / 8);
     static_assert(sizeof(Rk45Ctrl) % 8 == 0 && CTRL_WORDS <= BLK, "the controller moves as 64-bit words, one per thread");
     static_assert(PARK >= 3, "the reduction columns of a tile use three park columns");
-    using SB = StencilBlock<BLK, CPT, true, VD>;
-    __shared__ double lds[SB::LDS_DOUBLES + PARK * CPT * BLK];
+    using SB = StencilBlock<BLK, true, VD>;
+    __shared__ double lds[SB::LDS_DOUBLES + PARK * BLK];
     __shared__ double s_acc[NQ];         // this workgroup's record of the attempt (maxima negated), slot j touched by thread 32 j only
     __shared__ double s_wsum[NW];
     __shared__ double s_rec[NQ];         // last workgroup of a barrier: the grid's record {-, seven extrema of y_new}
@@ -1359,7 +1272,7 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
             marl_lab_clock45t[2048 * 8 * 8 - 4 + (a == 8 ? 1 : 3)] = __builtin_amdgcn_s_memrealtime();
         }
 #endif
-        double y[CPT][NF], k1[CPT][NF];
+        double y[NF], k1[NF];
         // (a thread's cell of tile t: local index l = out_lo + t V - H + tid; lanes outside the buffer - beyond a physical boundary, where the
         // ghost-cell rules apply and nothing reads them - load a copy of the edge cell: no predicate, no branch, finite values)
 #define MARL_LOAD_TILE(t, tid_)                                                                                                        \
@@ -1367,9 +1280,9 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
             int64_t l_ = S.out_lo + (int64_t)(t) * V - H + (tid_);                                                                     \
             l_ = l_ < 0 ? 0 : (l_ < S.n_buf ? l_ : S.n_buf - 1);                                                                       \
             _Pragma("unroll") for (int f = 0; f < NF; f++)                                                                             \
-                y[0][f] = MARL_STREAM_LOAD(yin + at<LAYOUT>(f, l_, S.ld));                                                             \
+                y[f] = MARL_STREAM_LOAD(yin + at<LAYOUT>(f, l_, S.ld));                                                                \
             _Pragma("unroll") for (int f = 0; f < NF; f++)                                                                             \
-                k1[0][f] = MARL_STREAM_LOAD(fin + at<LAYOUT>(f, l_, S.ld));                                                            \
+                k1[f] = MARL_STREAM_LOAD(fin + at<LAYOUT>(f, l_, S.ld));                                                               \
         } while (0)
         {
             int tid0 = threadIdx.x;
@@ -1401,17 +1314,17 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
             }
             sb.rebind(tid);
             double* pk = lds + SB::LDS_DOUBLES + tid;
-            double yn[CPT][NF], k7[CPT][NF], esum[CPT][NF];
-            PointAux aux[CPT];
+            double yn[NF], k7[NF], esum[NF];
+            PointAux aux;
             {
                 const int64_t l = S.out_lo + (int64_t)tile * V - H + tid;
                 sb.set_window(l + S.goff);
             }
-            sb.reuse_live[0] = false;
+            sb.reuse_live = false;
 #pragma unroll
-            for (int f = 0; f < PARK; f++) pk[f * BLK] = y[0][f];
+            for (int f = 0; f < PARK; f++) pk[f * BLK] = y[f];
             MARL_STAMP45T(1);
-            dp45_attempt<BLK, CPT, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
             MARL_STAMP45T(2);
             // everything below is recomputed from the thread index again (nothing but the results is carried across the stages)
             int tid2 = threadIdx.x;
@@ -1423,8 +1336,8 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
             if (owned) {
                 const double* pk2 = lds + SB::LDS_DOUBLES + tid2;
 #pragma unroll
-                for (int f = 0; f < NF; f++) q[0] += dp45_err2(esum[0][f], h, f < PARK ? pk2[f * BLK] : y[0][f], yn[0][f], rtol, atol);
-                monitors_accumulate<true>(q, yn[0], aux[0].U, aux[0].W);
+                for (int f = 0; f < NF; f++) q[0] += dp45_err2(esum[f], h, f < PARK ? pk2[f * BLK] : y[f], yn[f], rtol, atol);
+                monitors_accumulate<true>(q, yn, aux.U, aux.W);
             }
             // the next tile's loads first, the stores behind them: vector memory operations return in order, so waiting for
             // those loads does not wait for the stores' acknowledgements (write-through to memory: ~2 us)
@@ -1434,8 +1347,8 @@ rk45_stream_kernel(double* Y0, double* Y1, double* F0, double* F1, const DevCons
             if (owned) {
 #pragma unroll
                 for (int f = 0; f < NF; f++) {
-                    MARL_STREAM_STORE(yout + at<LAYOUT>(f, l2, S.ld), yn[0][f]);
-                    MARL_STREAM_STORE(fout + at<LAYOUT>(f, l2, S.ld), k7[0][f]);
+                    MARL_STREAM_STORE(yout + at<LAYOUT>(f, l2, S.ld), yn[f]);
+                    MARL_STREAM_STORE(fout + at<LAYOUT>(f, l2, S.ld), k7[f]);
                 }
             }
             MARL_STAMP45T(3);
@@ -1607,48 +1520,41 @@ __device__ __forceinline__ void uw_point(double Phi, const DevConsts& C, const T
 // Dense output of the step that starts at (yold, fold) with size h: replays the step's stages and
 // writes  y(t_old + x h) = y_old + h sum_j w_j(x) K_j  (t_eval samples, ivp.py:706-723) and/or the
 // monitors record of that state (event root finding, ivp.py:51-76).  yout may be NULL.
-template <int BLK, int CPT, int LAYOUT, bool VD = false>
+template <int BLK, int LAYOUT, bool VD = false>
 __global__ void __launch_bounds__(BLK) rk45_dense_kernel(const double* __restrict__ yold, const double* __restrict__ fold,
                                                          const DevConsts* __restrict__ consts, Slab S, double h,
                                                          DenseWeights dw, double* __restrict__ yout, double* __restrict__ part)
 {
     constexpr int H = 6;
-    constexpr int WIN = BLK * CPT;
-    constexpr int V = WIN - 2 * H;
-    using SB = StencilBlock<BLK, CPT, true, VD>;
+    constexpr int V = BLK - 2 * H;
+    using SB = StencilBlock<BLK, true, VD>;
     __shared__ double lds[SB::LDS_DOUBLES];
     const DevConsts& C = consts[0];
     const int64_t w0 = S.out_lo + (int64_t)blockIdx.x * V - H;
-    const int64_t l0 = w0 + (int64_t)threadIdx.x * CPT;
-    SB sb(lds, l0 + S.goff, consts);
-    double y[CPT][NF], k1[CPT][NF], yn[CPT][NF], k7[CPT][NF], dsum[CPT][NF];
-    PointAux aux[CPT];
-    load_cells<CPT, LAYOUT>(yold, l0, S, C, y);
-#pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        const int64_t l = l0 + c;
+    const int64_t l = w0 + (int64_t)threadIdx.x;
+    SB sb(lds, l + S.goff, consts);
+    double y[NF], k1[NF], yn[NF], k7[NF], dsum[NF];
+    PointAux aux;
+    load_cells<LAYOUT>(yold, l, S, C, y);
+    MARL_ONCE {
         const bool in = l >= 0 && l < S.n_buf;
 #pragma unroll
-        for (int f = 0; f < NF; f++) k1[c][f] = in ? fold[at<LAYOUT>(f, l, S.ld)] : 0.0;
+        for (int f = 0; f < NF; f++) k1[f] = in ? fold[at<LAYOUT>(f, l, S.ld)] : 0.0;
     }
-    dp45_attempt<BLK, CPT, true, SB>(sb, h, y, k1, yn, k7, dsum, aux, dw);
+    dp45_attempt<BLK, true, SB>(sb, h, y, k1, yn, k7, dsum, aux, dw);
     double q[NQ];
     monitors_init(q);
+    const int wi = threadIdx.x;
+    MARL_ONCE if (wi >= H && wi < BLK - H && l >= S.out_lo && l < S.out_hi) {
+        double d[NF];
 #pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        const int wi = threadIdx.x * CPT + c;
-        const int64_t l = l0 + c;
-        if (wi >= H && wi < WIN - H && l >= S.out_lo && l < S.out_hi) {
-            double d[NF];
-#pragma unroll
-            for (int f = 0; f < NF; f++) {
-                d[f] = h * dsum[c][f] + y[c][f];
-                if (yout) yout[at<LAYOUT>(f, l, S.ld)] = d[f];
-            }
-            double U, W;
-            uw_point(d[4], C, sb.T, U, W);
-            monitors_accumulate(q, d, U, W);
+        for (int f = 0; f < NF; f++) {
+            d[f] = h * dsum[f] + y[f];
+            if (yout) yout[at<LAYOUT>(f, l, S.ld)] = d[f];
         }
+        double U, W;
+        uw_point(d[4], C, sb.T, U, W);
+        monitors_accumulate(q, d, U, W);
     }
     block_reduce<BLK, NQ, NQMIN>(q, lds);   // the edge-exchange buffers are free now
     if (threadIdx.x == 0) {
@@ -1797,7 +1703,7 @@ __global__ void __launch_bounds__(256) slab_copy_kernel(double* __restrict__ Y0,
 
 // ---------------------------------------------------------------------------------------------
 // Batched parameter sweep (BASELINE configs 3-4): ONE workgroup integrates ONE instance
-// (N <= BLK*CPT cells) for all its steps.  State, stage vectors and the step controller stay
+// (N <= BLK cells) for all its steps.  State, stage vectors and the step controller stay
 // on-chip for the whole integration; global memory is touched at entry and exit only.
 //   Y: [batch][5][N] field-major per instance (the reference's layout, one instance after another).
 // ---------------------------------------------------------------------------------------------
@@ -1830,65 +1736,56 @@ __device__ __forceinline__ void ctrl_to_sgpr(Rk45Ctrl& c)
 #ifndef MARL_SWEEP_PARK
 #define MARL_SWEEP_PARK 2
 #endif
-template <int BLK, int CPT, bool VD, bool FAST>
+template <int BLK, bool VD, bool FAST>
 __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls, int64_t N,
                                                 double* __restrict__ Yold, double* __restrict__ Fold)
 {
-    using SB = StencilBlock<BLK, CPT, false, VD>;
+    using SB = StencilBlock<BLK, false, VD>;
     constexpr int NW = BLK / 64;
     constexpr int NMON = NQ - 1;                                  // the seven monitor extrema (record slots 1..7)
     constexpr int FAST_DOUBLES = FAST ? NMON * BLK + NW + NQ : 0; // monitor columns [slot][thread], per-wave sums, the reduced record
     // PARK fields of the step's first state y live in the thread's LDS column instead of registers (dp45_attempt): the 1024-thread
     // shape is capped at 128 VGPRs and every scratch reload in the stage loop stalls all 16 waves in front of their barrier
     // (measured: 6.6 -> 21.7 reloads per attempt = -17 %); two columns are what the 160 KB of LDS still hold beside the monitor columns
-    constexpr int PARK = (FAST && BLK == 1024 && CPT == 1) ? MARL_SWEEP_PARK : 0;
-    __shared__ double lds[SB::LDS_DOUBLES + FAST_DOUBLES + PARK * CPT * BLK];
+    constexpr int PARK = (FAST && BLK == 1024) ? MARL_SWEEP_PARK : 0;
+    __shared__ double lds[SB::LDS_DOUBLES + FAST_DOUBLES + PARK * BLK];
     __shared__ Rk45Ctrl sc;
     const DevConsts& C = consts[blockIdx.x];
     double* yg = Y + (int64_t)blockIdx.x * NF * N;
     Slab S = {N, 0, N, 0, N};
-    const int64_t l0 = (int64_t)threadIdx.x * CPT;
+    const int64_t l0 = threadIdx.x;
     SB sb(lds, l0, consts + blockIdx.x);
     if (threadIdx.x == 0) sc = ctrls[blockIdx.x];
     __syncthreads();
     if (sc.status != ST_RUNNING) return;
     const double rtol = FAST ? to_sgpr(sc.rtol) : sc.rtol, atol = FAST ? to_sgpr(sc.atol) : sc.atol;
 
-    double y[CPT][NF], k1[CPT][NF], yn[CPT][NF], k7[CPT][NF], esum[CPT][NF];
-    PointAux aux[CPT];
-    load_cells<CPT, LAYOUT_FIELD_MAJOR>(yg, l0, S, C, y);
+    double y[NF], k1[NF], yn[NF], k7[NF], esum[NF];
+    PointAux aux;
+    load_cells<LAYOUT_FIELD_MAJOR>(yg, l0, S, C, y);
     sb.eval(y, k1, aux);  // f(t, y): RungeKutta.__init__ (first launch) or re-derived on resume
     double* pk = lds + SB::LDS_DOUBLES + FAST_DOUBLES + threadIdx.x;
-    if constexpr (PARK > 0) {
 #pragma unroll
-        for (int c = 0; c < CPT; c++)
-#pragma unroll
-            for (int f = 0; f < PARK; f++) pk[(c * NF + f) * BLK] = y[c][f];
-    }
-#define MARL_Y(c, f) ((f) < PARK ? pk[((c) * NF + (f)) * BLK] : y[c][f])
-#define MARL_KEEP_OLD_STEP()                                                                                               \
-    _Pragma("unroll") for (int c = 0; c < CPT; c++) {                                                                      \
-        if (l0 + c < N) {                                                                                                  \
-            _Pragma("unroll") for (int f = 0; f < NF; f++) {                                                               \
-                Yold[(int64_t)blockIdx.x * NF * N + at<LAYOUT_FIELD_MAJOR>(f, l0 + c, N)] = MARL_Y(c, f);                  \
-                Fold[(int64_t)blockIdx.x * NF * N + at<LAYOUT_FIELD_MAJOR>(f, l0 + c, N)] = k1[c][f];                      \
-            }                                                                                                              \
-        }                                                                                                                  \
+    for (int f = 0; f < PARK; f++) pk[f * BLK] = y[f];
+#define MARL_Y(f) ((f) < PARK ? pk[(f) * BLK] : y[f])
+#define MARL_KEEP_OLD_STEP()                                                                                           \
+    MARL_ONCE if (l0 < N) {                                                                                            \
+        _Pragma("unroll") for (int f = 0; f < NF; f++) {                                                               \
+            Yold[(int64_t)blockIdx.x * NF * N + at<LAYOUT_FIELD_MAJOR>(f, l0, N)] = MARL_Y(f);                         \
+            Fold[(int64_t)blockIdx.x * NF * N + at<LAYOUT_FIELD_MAJOR>(f, l0, N)] = k1[f];                             \
+        }                                                                                                              \
     }
 
     if constexpr (!FAST) {
         while (true) {
             const double h = sc.h_try;
-            dp45_attempt<BLK, CPT, false, SB>(sb, h, y, k1, yn, k7, esum, aux);
+            dp45_attempt<BLK, false, SB>(sb, h, y, k1, yn, k7, esum, aux);
             double q[NQ];
             monitors_init(q);
+            MARL_ONCE if (l0 < N) {
 #pragma unroll
-            for (int c = 0; c < CPT; c++) {
-                if (l0 + c < N) {
-#pragma unroll
-                    for (int f = 0; f < NF; f++) q[0] += dp45_err2(esum[c][f], h, MARL_Y(c, f), yn[c][f], rtol, atol);
-                    monitors_accumulate(q, yn[c], aux[c].U, aux[c].W);
-                }
+                for (int f = 0; f < NF; f++) q[0] += dp45_err2(esum[f], h, MARL_Y(f), yn[f], rtol, atol);
+                monitors_accumulate(q, yn, aux.U, aux.W);
             }
             block_reduce<BLK, NQ, NQMIN>(q, lds);   // the edge-exchange buffers are free now
             if (threadIdx.x == 0) rk45_finish_attempt(sc, q, &sb.T);
@@ -1900,12 +1797,10 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                     MARL_KEEP_OLD_STEP()
                 }
 #pragma unroll
-                for (int c = 0; c < CPT; c++)
-#pragma unroll
-                    for (int f = 0; f < NF; f++) {
-                        y[c][f] = yn[c][f];
-                        k1[c][f] = k7[c][f];
-                    }
+                for (int f = 0; f < NF; f++) {
+                    y[f] = yn[f];
+                    k1[f] = k7[f];
+                }
             }
             __syncthreads();  // everyone has read sc before thread 0 may touch it again
             if (status != ST_RUNNING) break;
@@ -1930,20 +1825,17 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
             // (the first evaluation's exchange barrier also orders the monitor reduction of the previous attempt before the
             // event bookkeeping below; dp45_attempt is opaque, so the bookkeeping follows the whole attempt's evaluations -
             // still before this attempt's own decision changes c.t_old / c.h_prev / c.t)
-            dp45_attempt<BLK, CPT, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
             if (events_pending) {                    // wave-uniform
                 event_bookkeeping();
                 events_pending = false;
             }
             double q[NQ];
             monitors_init(q);
+            MARL_ONCE if (l0 < N) {
 #pragma unroll
-            for (int cc = 0; cc < CPT; cc++) {
-                if (l0 + cc < N) {
-#pragma unroll
-                    for (int f = 0; f < NF; f++) q[0] += dp45_err2(esum[cc][f], h, MARL_Y(cc, f), yn[cc][f], rtol, atol);
-                    monitors_accumulate<true>(q, yn[cc], aux[cc].U, aux[cc].W);   // (only read for accepted attempts: all finite)
-                }
+                for (int f = 0; f < NF; f++) q[0] += dp45_err2(esum[f], h, MARL_Y(f), yn[f], rtol, atol);
+                monitors_accumulate<true>(q, yn, aux.U, aux.W);   // (only read for accepted attempts: all finite)
             }
             double e2 = q[0];
 #pragma unroll
@@ -1986,12 +1878,10 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                     MARL_KEEP_OLD_STEP()
                 }
 #pragma unroll
-                for (int cc = 0; cc < CPT; cc++)
-#pragma unroll
-                    for (int f = 0; f < NF; f++) {
-                        if (f < PARK) pk[(cc * NF + f) * BLK] = yn[cc][f]; else y[cc][f] = yn[cc][f];
-                        k1[cc][f] = k7[cc][f];
-                    }
+                for (int f = 0; f < NF; f++) {
+                    if (f < PARK) pk[f * BLK] = yn[f]; else y[f] = yn[f];
+                    k1[f] = k7[f];
+                }
             }
             if (status != ST_RUNNING) break;
         }
@@ -2005,12 +1895,9 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
             sc.status = c.status; sc.rejected = c.rejected; sc.accepted_last = c.accepted_last; sc.cur = c.cur;
         }
     }
+    MARL_ONCE if (l0 < N) {
 #pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        if (l0 + c < N) {
-#pragma unroll
-            for (int f = 0; f < NF; f++) yg[at<LAYOUT_FIELD_MAJOR>(f, l0 + c, N)] = MARL_Y(c, f);
-        }
+        for (int f = 0; f < NF; f++) yg[at<LAYOUT_FIELD_MAJOR>(f, l0, N)] = MARL_Y(f);
     }
 #undef MARL_Y
 #undef MARL_KEEP_OLD_STEP
@@ -2021,58 +1908,53 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
 }
 
 // sweeps and single small runs that never pause on a monitor sign change
-template <int BLK, int CPT, bool VD = false>
+template <int BLK, bool VD = false>
 __global__ void __launch_bounds__(BLK) rk45_sweep_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
                                                          Rk45Ctrl* __restrict__ ctrls, int64_t N,
                                                          double* __restrict__ Yold, double* __restrict__ Fold)
 {
-    rk45_sweep_body<BLK, CPT, VD, true>(Y, consts, ctrls, N, Yold, Fold);
+    rk45_sweep_body<BLK, VD, true>(Y, consts, ctrls, N, Yold, Fold);
 }
 
 // single small runs with event root finding (Rk45Ctrl.pause_on_event): the decision to pause needs this step's events
-template <int BLK, int CPT, bool VD = false>
+template <int BLK, bool VD = false>
 __global__ void __launch_bounds__(BLK) rk45_sweep_events_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
                                                                 Rk45Ctrl* __restrict__ ctrls, int64_t N,
                                                                 double* __restrict__ Yold, double* __restrict__ Fold)
 {
-    rk45_sweep_body<BLK, CPT, VD, false>(Y, consts, ctrls, N, Yold, Fold);
+    rk45_sweep_body<BLK, VD, false>(Y, consts, ctrls, N, Yold, Fold);
 }
 
-template <int BLK, int CPT, bool VD = false>
+template <int BLK, bool VD = false>
 __global__ void __launch_bounds__(BLK) rk4_sweep_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
                                                         const double* __restrict__ dts, int64_t N, int64_t nsteps)
 {
-    using SB = StencilBlock<BLK, CPT, false, VD>;
+    using SB = StencilBlock<BLK, false, VD>;
     __shared__ double lds[SB::LDS_DOUBLES];
     const DevConsts& C = consts[blockIdx.x];
     double* yg = Y + (int64_t)blockIdx.x * NF * N;
     Slab S = {N, 0, N, 0, N};
-    const int64_t l0 = (int64_t)threadIdx.x * CPT;
+    const int64_t l0 = threadIdx.x;
     SB sb(lds, l0, consts + blockIdx.x);
     const double dt = dts[blockIdx.x];
     const double h2 = 0.5 * dt, h6 = dt / 6.0;
-    double y[CPT][NF], ys[CPT][NF], k[CPT][NF], acc[CPT][NF];
-    PointAux aux[CPT];
-    load_cells<CPT, LAYOUT_FIELD_MAJOR>(yg, l0, S, C, y);
-#define MARL_CELLS _Pragma("unroll") for (int c = 0; c < CPT; c++) _Pragma("unroll") for (int f = 0; f < NF; f++)
+    double y[NF], ys[NF], k[NF], acc[NF];
+    PointAux aux;
+    load_cells<LAYOUT_FIELD_MAJOR>(yg, l0, S, C, y);
 #pragma unroll 1
     for (int64_t s = 0; s < nsteps; s++) {
         sb.template eval<TR_FILL>(y, k, aux);
-        MARL_CELLS { acc[c][f] = k[c][f]; ys[c][f] = y[c][f] + h2 * k[c][f]; }
+        MARL_FIELDS { acc[f] = k[f]; ys[f] = y[f] + h2 * k[f]; }
         sb.template eval<TR_REUSE>(ys, k, aux);
-        MARL_CELLS { acc[c][f] = acc[c][f] + 2.0 * k[c][f]; ys[c][f] = y[c][f] + h2 * k[c][f]; }
+        MARL_FIELDS { acc[f] = acc[f] + 2.0 * k[f]; ys[f] = y[f] + h2 * k[f]; }
         sb.template eval<TR_REUSE>(ys, k, aux);
-        MARL_CELLS { acc[c][f] = acc[c][f] + 2.0 * k[c][f]; ys[c][f] = y[c][f] + dt * k[c][f]; }
+        MARL_FIELDS { acc[f] = acc[f] + 2.0 * k[f]; ys[f] = y[f] + dt * k[f]; }
         sb.template eval<TR_REUSE>(ys, k, aux);
-        MARL_CELLS y[c][f] = y[c][f] + h6 * (acc[c][f] + k[c][f]);
+        MARL_FIELDS y[f] = y[f] + h6 * (acc[f] + k[f]);
     }
-#undef MARL_CELLS
+    MARL_ONCE if (l0 < N) {
 #pragma unroll
-    for (int c = 0; c < CPT; c++) {
-        if (l0 + c < N) {
-#pragma unroll
-            for (int f = 0; f < NF; f++) yg[at<LAYOUT_FIELD_MAJOR>(f, l0 + c, N)] = y[c][f];
-        }
+        for (int f = 0; f < NF; f++) yg[at<LAYOUT_FIELD_MAJOR>(f, l0, N)] = y[f];
     }
 }
 

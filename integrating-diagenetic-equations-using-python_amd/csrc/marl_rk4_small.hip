@@ -27,8 +27,8 @@ extern "C" __attribute__((visibility("hidden"))) int marl_small_rk4_16(int tiled
     const Slab S{slab5[0], slab5[1], slab5[2], slab5[3], slab5[4]};
     const DevConsts* c = static_cast<const DevConsts*>(consts);
     if (tiled)
-        hipLaunchKernelGGL((rk4_fused_kernel<256, 1, LAYOUT_TILED, 16>), dim3(grid), dim3(256), 0, stream, yin, yout, c, S, dt);
+        hipLaunchKernelGGL((rk4_fused_kernel<256, LAYOUT_TILED, 16>), dim3(grid), dim3(256), 0, stream, yin, yout, c, S, dt);
     else
-        hipLaunchKernelGGL((rk4_fused_kernel<256, 1, LAYOUT_FIELD_MAJOR, 16>), dim3(grid), dim3(256), 0, stream, yin, yout, c, S, dt);
+        hipLaunchKernelGGL((rk4_fused_kernel<256, LAYOUT_FIELD_MAJOR, 16>), dim3(grid), dim3(256), 0, stream, yin, yout, c, S, dt);
     return (int)hipGetLastError();
 }

@@ -1,6 +1,6 @@
 """Guard rails on the instruction stream of the headline kernels, read from the code object that ships (CPU suite).
 
-The fixed-step fine-grid path (rk4_stream_kernel<256, 1, 4, false>, and the per-level rk4_fused_kernel<256, 1, 1, 4> that computes the
+The fixed-step fine-grid path (rk4_stream_kernel<256, 1, 4, false>, and the per-level rk4_fused_kernel<256, 1, 4> that computes the
 same bits) is bound by fp64 VALU issue, so every vector instruction that is not arithmetic costs time.  Two kinds used to sit on the
 path taken by 15 of every 16 evaluations: wave-uniform conditions turned into a lane mask in vector registers (`v_cndmask_b32 vN, 0, 1, s[..]`
 followed by `v_cmp`) and fp64 literals copied into vector registers with `v_mov_b32` pairs.  Removing them took the dynamic VALU count
@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from check_stream_isa import DEFAULT_SO, disassemble_so, functions  # noqa: E402
 
 STREAM = "rk4_stream_kernelILi256ELi1ELi4ELb0EE"      # the headline kernel (tiled layout, 4 steps per level)
-FUSED = "rk4_fused_kernelILi256ELi1ELi1ELi4ELb0EE"    # the same evaluations, one launch per level
+FUSED = "rk4_fused_kernelILi256ELi1ELi4ELb0EE"        # the same evaluations, one launch per level
 
 # kernel -> (literal v_mov_b32, v_cndmask_b32 vN, 0, 1, ...): the counts of the build that removed them from the evaluation
 BOUNDS = {STREAM: (575, 20), FUSED: (563, 20)}

@@ -4,5 +4,5 @@
 #include "../../integrating-diagenetic-equations-using-python_amd/csrc/marl_kernels.h"
 template __global__ void marl::rk45_stream_kernel<256, marl::LAYOUT_TILED, false, false>(double*, double*, double*, double*, const marl::DevConsts*, marl::Slab,
                                                                                    marl::Rk45Ctrl*, double*, marl::Rk45Stream*, unsigned, unsigned, unsigned, unsigned, unsigned, double*, int);
-template __global__ void marl::rk45_attempt_kernel<256, 1, marl::LAYOUT_TILED, false>(double*, double*, double*, double*, const marl::DevConsts*, marl::Slab,
+template __global__ void marl::rk45_attempt_kernel<256, marl::LAYOUT_TILED, false>(double*, double*, double*, double*, const marl::DevConsts*, marl::Slab,
                                                                                        const marl::Rk45Ctrl*, double*);

@@ -14,9 +14,6 @@
 #ifndef LAB_BLK
 #define LAB_BLK 256
 #endif
-#ifndef LAB_CPT
-#define LAB_CPT 1
-#endif
 #ifndef LAB_NSTEPS
 #define LAB_NSTEPS 1
 #endif
@@ -45,10 +42,10 @@ int main(int argc, char** argv)
     hipMalloc(&d1, sizeof(double) * 5 * N);
     hipMemcpy(d0, y.data(), sizeof(double) * 5 * N, hipMemcpyHostToDevice);
     const double dx = L / N, dt = 0.25 * dx * dx;
-    constexpr int V = LAB_BLK * LAB_CPT - 8 * LAB_NSTEPS;
+    constexpr int V = LAB_BLK - 8 * LAB_NSTEPS;
     const dim3 grid((unsigned)((N + V - 1) / V));
     auto launch = [&](double* a, double* b) {
-        hipLaunchKernelGGL((rk4_fused_kernel<LAB_BLK, LAB_CPT, LAYOUT_FIELD_MAJOR, LAB_NSTEPS>), grid, dim3(LAB_BLK), 0, 0, a, b, ctx->dconsts, ctx->slab, dt);
+        hipLaunchKernelGGL((rk4_fused_kernel<LAB_BLK, LAYOUT_FIELD_MAJOR, LAB_NSTEPS>), grid, dim3(LAB_BLK), 0, 0, a, b, ctx->dconsts, ctx->slab, dt);
     };
     for (int i = 0; i < 10; i++) { launch(d0, d1); std::swap(d0, d1); }
     hipDeviceSynchronize();
@@ -100,7 +97,7 @@ int main(int argc, char** argv)
     }
 #endif
     const int done = (steps / LAB_NSTEPS) * LAB_NSTEPS;
-    printf("BLK=%d CPT=%d NSTEPS=%d N=%lld: %.3f us/step, %.3e gp-steps/s (%.1f%% of 1e11), checksum %.15g\n", LAB_BLK, LAB_CPT, LAB_NSTEPS,
+    printf("BLK=%d NSTEPS=%d N=%lld: %.3f us/step, %.3e gp-steps/s (%.1f%% of 1e11), checksum %.15g\n", LAB_BLK, LAB_NSTEPS,
            (long long)N, best * 1e3 / done, (double)N * done / (best * 1e-3), (double)N * done / (best * 1e-3) / 1e9, chk);
     return 0;
 }

@@ -114,8 +114,8 @@ hbm = {"command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (one counter per pass
                   "(tools/profile_round.sh)", "units": __doc__.split("\n\n")[3].replace("\n", " "), "kernels": {}}
 # (the streamed RK4 kernel: one launch per bench call - bench.py's settle call of 2000 steps, then calls of 400 steps:
 #  tools/profile_round.sh passes --steps 400 --warmup 400 - so the counters are summed over the dispatches and divided by the steps)
-for wl, pick, alg, spl in (("default", "rk4_stream_kernel<256, 1, 4", 80 * N * 400, 400), ("default", "rk4_fused_kernel<256, 1, 1, 4", 80 * N * 4, 4),
-                           ("rk45_single", "rk45_attempt_kernel<256, 1, 1", 160 * N, 1)):
+for wl, pick, alg, spl in (("default", "rk4_stream_kernel<256, 1, 4", 80 * N * 400, 400), ("default", "rk4_fused_kernel<256, 1, 4", 80 * N * 4, 4),
+                           ("rk45_single", "rk45_attempt_kernel<256, 1", 160 * N, 1)):
     fe, wr = counter_table(f"pmc_{wl}_FETCH_SIZE"), counter_table(f"pmc_{wl}_WRITE_SIZE")
     cal = None
     for k, v in fe.items():
@@ -148,7 +148,7 @@ sq = {"command": "rocprofv3 --pmc <SQ set> -- python3 bench.py --no-cpu-baseline
 # sweeps: one warm-up call of 5 and one timed call of 200 attempts over 4096 x 1024 cells)
 UNITS = {("default", "rk4_stream_kernel<256, 1, 4"): lambda n: N * (2000 + 400 * (n - 1)),
          ("default_no_reuse", "rk4_stream_kernel<256, 1, 4"): lambda n: N * (2000 + 400 * (n - 1)),
-         ("n65536", "rk4_fused_kernel<256, 1, 1, 16"): lambda n: 65536 * 16 * n,
+         ("n65536", "rk4_fused_kernel<256, 1, 16"): lambda n: 65536 * 16 * n,
          ("n65536", "rk4_stream_kernel"): lambda n: 65536 * (2000 + 800 * (n - 1)),
          ("rk45_single", "rk45_attempt_kernel"): lambda n: N * n,
          ("sweep_rk45", "rk45_sweep_kernel"): lambda n: 4096 * 1024 * 205 if n == 2 else None,
