@@ -141,6 +141,17 @@ int marl_integrate_rk45_dev(marl_ctx* ctx, double* y_dev, int layout, double t0,
  * stats: host array of n_instances entries.  FIELD-MAJOR device state.  Synchronises. */
 int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol,
                         double atol, int64_t max_attempts, marl_stats* stats);
+/* the sweep with t_eval: what the reference stores of every run is the time series that solve_ivp(..., t_eval=) fills
+ * (marlpde/Evolve_scenario.py:104-109).  As in scipy the samples never change the steps (ivp.py:706-723): after every
+ * accepted step the kernel writes the samples inside it by dense output (rk.py:560-574) - no function evaluation is
+ * counted, and state and statistics are those of marl_sweep_rk45_dev.
+ * t_eval: host, n_eval times shared by all instances, strictly increasing within [t0, t1].
+ * y_eval_dev: device, [n_instances][n_eval][5N], each frame field-major.  n_done: host, n_instances entries: the frames
+ * written for that instance (the samples up to the time it reached); its later frames are not touched.
+ * n_eval = 0 is marl_sweep_rk45_dev.  t1 == t0: no step; a sample at t0 receives y0.  Synchronises. */
+int marl_sweep_rk45_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                             int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                             int64_t* n_done, marl_stats* stats);
 
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,

@@ -69,6 +69,10 @@ struct marl_ctx {
     double* hrec = nullptr;     // pinned [batch][NQ]
     double* ddt = nullptr;      // [batch] per-instance dt
     double* hdt = nullptr;      // pinned [batch]: staging of the caller's dt array (the caller's buffer may die before the copy runs)
+    // sweeps with t_eval (rk45_sweep_eval_kernel): the sample times and the frames written per instance, allocated on first use
+    double* sw_teval = nullptr;
+    size_t sw_teval_cap = 0;
+    int64_t* sw_ndone = nullptr;   // [batch]
     // domain decomposition: this rank's message / the gathered messages (device), and the RCCL communicator (dlopen'ed API)
     double* dd_send = nullptr;
     double* dd_gathered = nullptr;
@@ -338,6 +342,8 @@ void marl_ctx_destroy(marl_ctx* ctx)
     if (ctx->hctrl) (void)hipHostFree(ctx->hctrl);
     if (ctx->hrec) (void)hipHostFree(ctx->hrec);
     if (ctx->hdt) (void)hipHostFree(ctx->hdt);
+    if (ctx->sw_teval) (void)hipFree(ctx->sw_teval);
+    if (ctx->sw_ndone) (void)hipFree(ctx->sw_ndone);
     if (ctx->rccl_comm && ctx->rccl_destroy) (void)ctx->rccl_destroy(ctx->rccl_comm);
     if (ctx->dd_send) (void)hipFree(ctx->dd_send);
     if (ctx->dd_gathered) (void)hipFree(ctx->dd_gathered);
@@ -891,15 +897,8 @@ static void launch_dense_t(marl_ctx* ctx, int64_t nb, int layout, const double* 
                            ctx->dconsts, ctx->slab, h, dw, yout, ctx->part);
 }
 
-// Dense output P (scipy/integrate/_ivp/rk.py:393-407): w_j(x) = sum_m P[j][m] x^(m+1)
-static const double kDpP[7][4] = {
-    {1, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
-    {0, 0, 0, 0},
-    {0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
-    {0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
-    {0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408, 701980252875.0 / 199316789632},
-    {0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
-    {0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
+// Dense output P (dp::P, marl_kernels.h): w_j(x) = sum_m P[j][m] x^(m+1)
+static constexpr auto& kDpP = dp::P;
 
 // Evaluate the dense output of the LAST accepted step at time t: state into yout (may be NULL) and the
 // seven monitors into g (may be NULL; synchronises when given).
@@ -1226,6 +1225,56 @@ int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, doub
     HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
+    return 0;
+}
+
+int marl_sweep_rk45_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                             int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                             marl_stats* stats)
+{
+    if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
+        return ctx ? fail(ctx, -1, "marl_sweep_rk45_eval_dev: invalid argument") : -1;
+    if (n_eval == 0) {   // nothing to sample: the plain sweep itself
+        if (n_done) memset(n_done, 0, sizeof(int64_t) * ctx->batch);
+        return marl_sweep_rk45_dev(ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, stats);
+    }
+    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
+    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
+    for (int64_t i = 0; i < n_eval; i++)
+        if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
+            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    const int blk = sweep_block(ctx);
+    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
+    if (ctx->sw_teval_cap < (size_t)n_eval) {
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->sw_teval) HIP_OK(ctx, hipFree(ctx->sw_teval));
+        ctx->sw_teval = nullptr;
+        ctx->sw_teval_cap = 0;
+        HIP_OK(ctx, hipMalloc((void**)&ctx->sw_teval, sizeof(double) * n_eval));
+        ctx->sw_teval_cap = (size_t)n_eval;
+    }
+    if (!ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
+    // (pageable host memory: the copy has left the caller's array when the call returns)
+    HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, t_eval, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
+    if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
+    hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
+                       atol, (int64_t)NF * ctx->N, max_attempts, 0);
+    LAUNCH_OK(ctx);
+    const dim3 grid((unsigned)ctx->batch);
+    SWEEP_DISPATCH(rk45_sweep_eval_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone)
+    LAUNCH_OK(ctx);
+    HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
+    if (t1 == t0 && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as rk45_run gives it to single runs
+        const size_t row = sizeof(double) * NF * ctx->N;
+        HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * n_eval, y_dev, row, row, (size_t)ctx->batch, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t b = 0; b < ctx->batch; b++) n_done[b] = 1;
+    }
     return 0;
 }
 

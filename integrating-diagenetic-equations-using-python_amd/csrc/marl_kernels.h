@@ -686,6 +686,15 @@ constexpr double A61 = 9017.0 / 3168, A62 = -355.0 / 33, A63 = 46732.0 / 5247, A
 constexpr double B1 = 35.0 / 384, B3 = 500.0 / 1113, B4 = 125.0 / 192, B5 = -2187.0 / 6784, B6 = 11.0 / 84;
 constexpr double E1 = -71.0 / 57600, E3 = 71.0 / 16695, E4 = -71.0 / 1920, E5 = 17253.0 / 339200, E6 = -22.0 / 525, E7 = 1.0 / 40;
 constexpr double SAFETY = 0.9, MIN_FACTOR = 0.2, MAX_FACTOR = 10.0;
+// Dense output P (scipy/integrate/_ivp/rk.py:393-407): w_j(x) = sum_m P[j][m] x^(m+1); host (dense_eval) and device (dense_weights)
+constexpr double P[7][4] = {
+    {1, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
+    {0, 0, 0, 0},
+    {0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
+    {0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
+    {0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408, 701980252875.0 / 199316789632},
+    {0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
+    {0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
 }  // namespace dp
 
 
@@ -967,11 +976,21 @@ struct DenseWeights { double w[7]; };
 // PARK = number of fields (0..5) of the step's first state y that are NOT held in registers but in this thread's LDS column
 // `pk` (pk[f * BLK], f < PARK) and re-read where a stage state is formed - up to five live doubles less across every
 // evaluation (kernels that sit just above a register cap: 128 VGPRs = 4 waves per SIMD).
-template <int BLK, bool DENSE = false, class SB = StencilBlock<BLK>, int PARK = 0>
+// EITHER (rk45_sweep_eval_kernel; DENSE = false): one call site serves attempts and dense-output replays - `esum` is summed with the
+// weights `dw` when `dense_now` (workgroup-uniform) and with the constants E_j otherwise, in two separate blocks.  The constant block
+// is the statement of the plain attempt, so that it is compiled as there (with E_j as run-time values the compiler rounds other
+// products of  k1 E1 + k3 E3 + ...: E1, E4, E6 are negative, and  a + x (-c)  becomes  a - x c  before the multiply-adds are formed);
+// the run-time block hands its sums through an empty asm, which keeps the optimiser from merging the two blocks into one with selected
+// operands (phi of two sums -> sum of phis: the weights would be run-time values again, and the multiply and the add end up in
+// different blocks, unfused).
+template <int BLK, bool DENSE = false, class SB = StencilBlock<BLK>, int PARK = 0, bool EITHER = false>
 __device__ __forceinline__ void dp45_attempt(SB& sb, double h, const double (&y)[NF], const double (&k1)[NF],
                                              double (&yn)[NF], double (&k7)[NF], double (&esum)[NF],
-                                             PointAux& aux, const DenseWeights& dw = DenseWeights{}, const double* pk = nullptr)
+                                             PointAux& aux, const DenseWeights& dw = DenseWeights{}, const double* pk = nullptr,
+                                             bool dense_now = false)
 {
+    static_assert(!(EITHER && DENSE), "EITHER chooses at run time");
+#define MARL_SEPARATE_BLOCKS() MARL_FIELDS asm volatile("" : "+v"(esum[f]))
     const double e1 = DENSE ? dw.w[0] : dp::E1, e3 = DENSE ? dw.w[2] : dp::E3, e4 = DENSE ? dw.w[3] : dp::E4;
     const double e5 = DENSE ? dw.w[4] : dp::E5, e6 = DENSE ? dw.w[5] : dp::E6, e7 = DENSE ? dw.w[6] : dp::E7;
     // K1..K4 are folded into the partial sums of everything that still needs them as soon as K4 exists, so that at
@@ -989,21 +1008,55 @@ __device__ __forceinline__ void dp45_attempt(SB& sb, double h, const double (&y)
         ys[f] = MARL_Y(f) + (k1[f] * dp::A51 + k2[f] * dp::A52 + k3[f] * dp::A53 + k4[f] * dp::A54) * h;
         s6[f] = k1[f] * dp::A61 + k2[f] * dp::A62 + k3[f] * dp::A63 + k4[f] * dp::A64;
         bn[f] = k1[f] * dp::B1 + k3[f] * dp::B3 + k4[f] * dp::B4;
-        esum[f] = k1[f] * e1 + k3[f] * e3 + k4[f] * e4;
+        if constexpr (!EITHER) esum[f] = k1[f] * e1 + k3[f] * e3 + k4[f] * e4;
+    }
+    if constexpr (EITHER) {
+        if (dense_now) {
+            MARL_FIELDS esum[f] = k1[f] * dw.w[0] + k3[f] * dw.w[2] + k4[f] * dw.w[3];
+            MARL_SEPARATE_BLOCKS();
+        } else {
+            MARL_FIELDS esum[f] = k1[f] * dp::E1 + k3[f] * dp::E3 + k4[f] * dp::E4;
+        }
     }
     sb.template eval<TR_REUSE>(ys, kk, aux);   // K5
     MARL_FIELDS {
         ys[f] = MARL_Y(f) + (s6[f] + kk[f] * dp::A65) * h;
         bn[f] = bn[f] + kk[f] * dp::B5;
-        esum[f] = esum[f] + kk[f] * e5;
+        if constexpr (!EITHER) esum[f] = esum[f] + kk[f] * e5;
+    }
+    if constexpr (EITHER) {
+        if (dense_now) {
+            MARL_FIELDS esum[f] = esum[f] + kk[f] * dw.w[4];
+            MARL_SEPARATE_BLOCKS();
+        } else {
+            MARL_FIELDS esum[f] = esum[f] + kk[f] * dp::E5;
+        }
     }
     sb.template eval<TR_REUSE>(ys, kk, aux);   // K6
     MARL_FIELDS {
         yn[f] = MARL_Y(f) + h * (bn[f] + kk[f] * dp::B6);
-        esum[f] = esum[f] + kk[f] * e6;
+        if constexpr (!EITHER) esum[f] = esum[f] + kk[f] * e6;
+    }
+    if constexpr (EITHER) {
+        if (dense_now) {
+            MARL_FIELDS esum[f] = esum[f] + kk[f] * dw.w[5];
+            MARL_SEPARATE_BLOCKS();
+        } else {
+            MARL_FIELDS esum[f] = esum[f] + kk[f] * dp::E6;
+        }
     }
     sb.template eval<TR_REUSE>(yn, k7, aux);
-    MARL_FIELDS esum[f] = esum[f] + k7[f] * e7;
+    if constexpr (EITHER) {
+        if (dense_now) {
+            MARL_FIELDS esum[f] = esum[f] + k7[f] * dw.w[6];
+            MARL_SEPARATE_BLOCKS();
+        } else {
+            MARL_FIELDS esum[f] = esum[f] + k7[f] * dp::E7;
+        }
+    } else {
+        MARL_FIELDS esum[f] = esum[f] + k7[f] * e7;
+    }
+#undef MARL_SEPARATE_BLOCKS
 #undef MARL_Y
 }
 
@@ -1736,10 +1789,30 @@ __device__ __forceinline__ void ctrl_to_sgpr(Rk45Ctrl& c)
 #ifndef MARL_SWEEP_PARK
 #define MARL_SWEEP_PARK 2
 #endif
-template <int BLK, bool VD, bool FAST>
-__device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls, int64_t N,
-                                                double* __restrict__ Yold, double* __restrict__ Fold)
+// the dense-output weights w_j(x) of a Dormand-Prince step, summed as the host's dense_eval sums them
+__device__ __forceinline__ DenseWeights dense_weights(double x)
 {
+    const double pw[4] = {x, x * x, x * x * x, x * x * x * x};
+    DenseWeights dw;
+#pragma unroll
+    for (int j = 0; j < 7; j++) {
+        double a = 0;
+#pragma unroll
+        for (int m = 0; m < 4; m++) a += dp::P[j][m] * pw[m];
+        dw.w[j] = a;
+    }
+    return dw;
+}
+
+// EVAL (FAST only; rk45_sweep_eval_kernel): the t_eval samples that fall into an accepted step are written by dense-output replays of
+// that step inside the loop (see there); without it the four trailing arguments are unused and the code is what it was without them.
+template <int BLK, bool VD, bool FAST, bool EVAL = false>
+__device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls, int64_t N,
+                                                double* __restrict__ Yold, double* __restrict__ Fold,
+                                                const double* __restrict__ t_eval = nullptr, int64_t n_eval = 0,
+                                                double* __restrict__ Yeval = nullptr, int64_t* __restrict__ n_done = nullptr)
+{
+    static_assert(FAST || !EVAL, "the sampling loop is built on the replicated controller");
     using SB = StencilBlock<BLK, false, VD>;
     constexpr int NW = BLK / 64;
     constexpr int NMON = NQ - 1;                                  // the seven monitor extrema (record slots 1..7)
@@ -1817,15 +1890,66 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         ctrl_to_sgpr(c);
         const double inv_n = to_sgpr(1.0 / (double)c.n_total);
         bool events_pending = false;                 // an accepted step whose monitors (rec) have not been compared with sc.g yet
+        // EVAL: t_eval samples inside an accepted step, (t_old, t] (ivp.py:706-723), are written BEFORE the step is committed, while
+        // (y, k1) still describe it: the loop runs once more per sample with `sampling` set - the SAME dp45_attempt call (EITHER), with h = h_prev
+        // and the dense-output weights w_j(x) in place of the error weights E_j, so that `esum` returns  sum_j w_j K_j  and
+        // y + h esum  is the sample (rk.py:560-574).  One call site for attempts and replays is what keeps the ordinary path at the plain
+        // kernel's register pressure (a second inlined copy of the six evaluations: 184 -> 540 B of scratch at 1024 threads, spill
+        // stores inside the stage sequence; profiles/r07_sweep_frames_isa.log), and it answers where y_new / k7 wait during a replay:
+        // nowhere.  The replay executes the instructions of the accepted attempt on the same (y, k1, h), so it leaves the same y_new,
+        // k7 (and aux) in the same registers, bit for bit, and the commit that follows the last replay finds them there.
+        //   - uniformity: whether to replay follows from c (replicated, SGPRs), ie, and t_eval[ie], which every wave reads from the same
+        //     address - the exchange barriers of a replay are reached by every wave or by none;
+        //   - a replay is no attempt: it skips the error norm, the ONE barrier, the decision and the monitors, and touches neither c
+        //     (nfev included: scipy's dense output costs no evaluation) nor sc, rec or the monitor columns (the evaluations write the
+        //     edge buffers and read the park columns only);
+        //   - event bookkeeping: the ordering argument at the head of the loop asks that rec / sc.t_old / sc.h_prev / sc.t of an accepted
+        //     step are read after one more workgroup barrier and before the next DECISION replaces them.  Replays sit between that decision
+        //     and the next attempt, add barriers and decide nothing; events_pending stays set through them, so the bookkeeping still
+        //     follows the evaluations of the next attempt - or the loop, when the step was the last.
+        int64_t ie = 0;                              // the next sample, t_eval[ie]; the same in every lane (SGPRs)
+        bool sampling = false;                       // this trip of the loop replays the step just accepted for sample ie
+        double te = 0.0;                             // t_eval[ie] of that replay
+        DenseWeights dw = {};                        // w_j(x) of that replay (SGPRs)
+        auto next_sample = [&]() -> bool {           // is sample ie inside the step just accepted?  then dw = its weights
+            if (!(ie < n_eval)) return false;
+            te = to_sgpr(t_eval[ie]);
+            if (!(te <= c.t)) return false;
+            const DenseWeights w = dense_weights((te - c.t_old) / c.h_prev);
+#pragma unroll
+            for (int j = 0; j < 7; j++) dw.w[j] = to_sgpr(w.w[j]);
+            return true;
+        };
         auto event_bookkeeping = [&]() {             // lanes 0..6 of wave 0: one monitor each; sc.t_old / sc.h_prev / sc.t describe that step
             if (threadIdx.x < 7) rk45_event_one(sc, threadIdx.x, rk45_monitor_of_record(rec, threadIdx.x));
         };
         while (true) {
-            const double h = c.h_try;
+            const double h = (EVAL && sampling) ? c.h_prev : c.h_try;
             // (the first evaluation's exchange barrier also orders the monitor reduction of the previous attempt before the
             // event bookkeeping below; dp45_attempt is opaque, so the bookkeeping follows the whole attempt's evaluations -
             // still before this attempt's own decision changes c.t_old / c.h_prev / c.t)
-            dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            if constexpr (EVAL) dp45_attempt<BLK, false, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, sampling);
+            else dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            if constexpr (EVAL) {
+                if (sampling) {                      // workgroup-uniform
+                    double* fr = Yeval + ((int64_t)blockIdx.x * n_eval + ie) * (NF * N);
+                    MARL_ONCE if (l0 < N) {
+#pragma unroll
+                        for (int f = 0; f < NF; f++)   // (x = 0, a sample at t0: y_old itself, whatever 0 * K_j gives)
+                            fr[at<LAYOUT_FIELD_MAJOR>(f, l0, N)] = (te == c.t_old) ? MARL_Y(f) : h * esum[f] + MARL_Y(f);
+                    }
+                    ie = to_sgpr(ie + 1);
+                    if (next_sample()) continue;     // another sample in the same step
+                    sampling = false;
+#pragma unroll
+                    for (int f = 0; f < NF; f++) {   // the commit the accepted attempt postponed: y_new, k7 as the replay left them
+                        if (f < PARK) pk[f * BLK] = yn[f]; else y[f] = yn[f];
+                        k1[f] = k7[f];
+                    }
+                    if (c.status != ST_RUNNING) break;
+                    continue;
+                }
+            }
             if (events_pending) {                    // wave-uniform
                 event_bookkeeping();
                 events_pending = false;
@@ -1877,6 +2001,12 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                 if (status != ST_RUNNING && Yold) {
                     MARL_KEEP_OLD_STEP()
                 }
+                if constexpr (EVAL) {
+                    if (next_sample()) {             // samples inside this step: replay it first, commit afterwards
+                        sampling = true;
+                        continue;
+                    }
+                }
 #pragma unroll
                 for (int f = 0; f < NF; f++) {
                     if (f < PARK) pk[f * BLK] = yn[f]; else y[f] = yn[f];
@@ -1893,6 +2023,7 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
             sc.err_norm = sqrt(c.err_norm);          // (rk45_decide_lean keeps the mean square)
             sc.nfev = c.nfev; sc.n_acc = c.n_acc; sc.n_rej = c.n_rej; sc.attempts = c.attempts;
             sc.status = c.status; sc.rejected = c.rejected; sc.accepted_last = c.accepted_last; sc.cur = c.cur;
+            if constexpr (EVAL) n_done[blockIdx.x] = ie;   // frames written; the rest of the instance's frame memory is untouched
         }
     }
     MARL_ONCE if (l0 < N) {
@@ -1923,6 +2054,18 @@ __global__ void __launch_bounds__(BLK) rk45_sweep_events_kernel(double* __restri
                                                                 double* __restrict__ Yold, double* __restrict__ Fold)
 {
     rk45_sweep_body<BLK, VD, false>(Y, consts, ctrls, N, Yold, Fold);
+}
+
+// sweeps with t_eval: the loop of rk45_sweep_kernel, and after every accepted step the samples inside it by dense output.
+//   t_eval: n_eval sorted times, shared by all instances; Yeval: [instance][n_eval][5][N]; n_done: [instance] frames written
+//   (an instance that stops early leaves the later frames alone; one that is not running at entry writes nothing, n_done included).
+template <int BLK, bool VD = false>
+__global__ void __launch_bounds__(BLK) rk45_sweep_eval_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
+                                                              Rk45Ctrl* __restrict__ ctrls, int64_t N,
+                                                              const double* __restrict__ t_eval, int64_t n_eval,
+                                                              double* __restrict__ Yeval, int64_t* __restrict__ n_done)
+{
+    rk45_sweep_body<BLK, VD, true, true>(Y, consts, ctrls, N, nullptr, nullptr, t_eval, n_eval, Yeval, n_done);
 }
 
 template <int BLK, bool VD = false>

@@ -85,10 +85,20 @@ class HipSweepEngine:
             self._model.use_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
         return self._model
 
-    def integrate_rk45(self, y0, t_span, first_step, rtol, atol, max_attempts):
-        """y0: (n_local, 5N) host array.  Returns (y_final (n_local, 5N), list of RK45Result)."""
+    def integrate_rk45(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None):
+        """y0: (n_local, 5N) host array.  Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries
+        the samples that instance reached, as a single run's does: ``t`` (n_t,) and ``y`` (5N, n_t)."""
         yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
-        res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+        if t_eval is None:
+            res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+            return yd.cpu().numpy(), res
+        n_eval = int(np.size(t_eval))
+        frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
+        res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
+                                           y_eval_dev_ptr=frames.data_ptr())
+        frames = frames.cpu().numpy()
+        for b, r in enumerate(res):
+            r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
     def integrate_radau(self, y0, t_span, first_step, rtol, atol, max_attempts):
@@ -178,18 +188,22 @@ def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_att
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None):
+                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None):
     """Integrate every instance with adaptive RK45; ranks of ``group`` each take a contiguous shard (``balance``: see :func:`assign`).
 
     Returns ``(y_final, status, n_accepted, n_rejected, t_reached)`` - for ALL instances, in their order, when ``gather``,
     otherwise for the rank's own instances (``assign(...)`` order).  ``engine_factory(base_parms, local_instances) -> engine`` is
-    the test hook; the default is :class:`HipSweepEngine` on ``cuda:rank``."""
+    the test hook; the default is :class:`HipSweepEngine` on ``cuda:rank``.
+
+    With ``t_eval`` (sorted sample times within ``t_span``, the same for every instance) two more elements follow: ``n_frames``, the
+    number of samples each instance reached, and ``y_eval`` of shape (instances, len(t_eval), 5N), the time series
+    ``solve_ivp(..., t_eval=)`` returns (Evolve_scenario.py:104-109) - NaN beyond an instance's ``n_frames``; ordered like the states."""
     return _run_sweep("integrate_rk45", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost)
+                      balance, cost, t_eval)
 
 
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-               balance="contiguous", cost=None):
+               balance="contiguous", cost=None, t_eval=None):
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -204,20 +218,34 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
         dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device   # one process per GPU
         engine_factory = lambda bp, inst: HipSweepEngine(bp, inst, dev)  # noqa: E731
     y0 = np.asarray(y0)
+    sampled = t_eval is not None   # (RK45 only: the drivers of the implicit sweeps pass none)
+    if sampled:
+        t_eval = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
     if local:
         engine = engine_factory(base_parms, local)
-        y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts)
+        more = {"t_eval": t_eval} if sampled else {}
+        y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()
     else:   # (more ranks than instances)
         y, res = np.empty((0,) + y0.shape[1:]), []
     summary = np.array([[r.status, r.n_accepted, r.n_rejected, r.t_reached] for r in res], dtype=float).reshape(len(local), 4)
+    frames = None
+    if sampled:   # the rank's time series: column 4 of the summary counts an instance's frames, the rest of its rows stay NaN
+        frames = np.full((len(local), t_eval.size) + y0.shape[1:], np.nan)
+        for b, r in enumerate(res):
+            frames[b, :len(r.t)] = np.asarray(r.y).T
+        summary = np.concatenate([summary, np.array([len(r.t) for r in res], dtype=float).reshape(len(local), 1)], axis=1)
     if gather and world > 1:
         parts = [None] * world
-        dist.all_gather_object(parts, (mine, y, summary), group=group)
+        dist.all_gather_object(parts, (mine, y, summary, frames), group=group)
         y_all = np.empty((len(instances),) + y0.shape[1:])
-        s_all = np.empty((len(instances), 4))
-        for idx, yy, ss in parts:   # back into the order of `instances`
+        s_all = np.empty((len(instances), summary.shape[1]))
+        f_all = np.full((len(instances), t_eval.size) + y0.shape[1:], np.nan) if sampled else None
+        for idx, yy, ss, ff in parts:   # back into the order of `instances`
             y_all[idx] = yy
             s_all[idx] = ss
-        y, summary = y_all, s_all
-    return y, summary[:, 0].astype(int), summary[:, 1].astype(int), summary[:, 2].astype(int), summary[:, 3]
+            if sampled:
+                f_all[idx] = ff
+        y, summary, frames = y_all, s_all, f_all
+    out = (y, summary[:, 0].astype(int), summary[:, 1].astype(int), summary[:, 2].astype(int), summary[:, 3])
+    return out + (summary[:, 4].astype(int), frames) if sampled else out
