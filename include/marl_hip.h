@@ -84,6 +84,9 @@ int marl_synchronize(marl_ctx* ctx);
  *   one workgroup; 0: one RHS launch, one linear-algebra launch and one wait per Newton iteration - bit-identical),
  *   rk4_stream (fixed-step RK4 of one grid as ONE dataflow launch over (level, tile) work items instead of one launch per
  *   fused level: 0 never, 1 - the default - for grids of 196 608 cells or more, 2 always; results are bit-identical),
+ *   rk4_chain (the streamed loop with 4 steps per level and constant porosity diffusion: work items that are chains of K windows, of
+ *   which only the first recomputes a left halo - rk4_chain_kernel; 0 never, 1 - the default - the longest chain of at most 8 windows
+ *   that leaves every resident workgroup two items per level, which is none on grids under ~950 000 cells; 2 ... 8: chains of that many windows),
  *   rk4_stream_third (1, the default: a streamed call with an odd number of levels runs through a third state buffer instead of
  *   copying the state back afterwards; 0: copy - bit-identical),
  *   rk4_stream_test_raise (test hook: the next streamed run starts with its give-up flag raised - marl_synchronize must

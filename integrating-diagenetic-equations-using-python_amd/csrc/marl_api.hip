@@ -24,6 +24,7 @@
 using namespace marl;
 
 static_assert(MARL_NFIELDS == NF, "field count");
+constexpr int64_t kChainMax = 8;   // longest chain of windows: what automatic mode may pick, option rk4_chain may force and the tests run
 static thread_local std::string g_create_error;   // marl_ctx_create failures, per calling thread (contexts are created from worker threads too)
 
 struct marl_ctx {
@@ -97,6 +98,9 @@ struct marl_ctx {
     int64_t rk4_variant = -1, sweep_variant = -1, host_layout = LAYOUT_TILED, poll = 64;
     int64_t rk4_stream = 1;     // the fixed-step loop of one grid as ONE dataflow launch (rk4_stream_kernel): 0 never, 1 large grids, 2 always
     int64_t rk4_small = 1;      // grids of up to two workgroups per CU at 16 steps per launch: the build of marl_rk4_small.hip (0: the common one)
+    // chained windows in the streamed loop (rk4_chain_kernel; 4 steps per level, constant porosity diffusion): 0 never, 1 automatic
+    // (rk4_chain_auto below), K >= 2: chains of K windows whenever that path is taken
+    int64_t rk4_chain = 1;
     int64_t rk4_stream_third = 1;   // an odd number of levels goes through a third state buffer, so that no whole-state copy follows (0: copy)
     double* stream_c = nullptr;
     size_t stream_c_cap = 0;
@@ -418,6 +422,7 @@ int marl_set_option(marl_ctx* ctx, const char* name, int64_t value)
     else if (n == "dd_stream") ctx->dd_stream = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (n == "rk45_stream_attempts") ctx->rk45_stream_attempts = value < 1 ? 1 : std::min<int64_t>(value, 1 << 20);
     else if (n == "rk4_small") ctx->rk4_small = value ? 1 : 0;
+    else if (n == "rk4_chain") ctx->rk4_chain = value < 0 ? 0 : std::min<int64_t>(value, kChainMax);
     else if (n == "rk4_stream_third") ctx->rk4_stream_third = value ? 1 : 0;
     else if (n == "rk4_stream_test_raise") ctx->sq_test_raise = value != 0;
     else if (n == "rk4_stream_max_items") ctx->sq_max_items = value > 0 ? std::min<int64_t>(value, 0x7fffffff) : 0x7fffffff;
@@ -602,15 +607,63 @@ static void launch_stream_t(marl_ctx* ctx, double* a, double* b, int layout, dou
                            dt, levels, tiles, ctx->sq, ctx->sq + 2, ctx->sq_sticky, ctx->sq_item_base, ctx->sq_level_base, c);
 }
 
+// The chained decomposition of a level (rk4_chain_kernel): the grid's last tile of the unchained decomposition, [bound, n) with
+// bound = V * floor((n - 1) / V), stays an item of its own; `chains` chains of K windows, V + (K - 1) W cells each, tile [0, bound), the
+// last one clipped there and `nsub_last` windows long.  V, W and therefore every chain start and the bound are multiples of the halo
+// H = 16, so no chain is narrower than H cells: the last tile's left halo ends inside the last chain, and an item's producers stay
+// "t-1, t, t+1 of the level before".
+struct ChainShape {
+    int64_t items, bound;
+    unsigned K, nsub_last;
+};
+static ChainShape chain_shape(int64_t n, int64_t K)
+{
+    constexpr int64_t H = 16, V = 256 - 2 * H, W = 256 - H;
+    static_assert(V % H == 0 && W % H == 0, "a clipped chain could be narrower than the halo");
+    const int64_t bound = V * ((n - 1) / V), L = V + W * (K - 1);
+    const int64_t chains = (bound + L - 1) / L;
+    int64_t nsub_last = 0;
+    if (chains > 0) {
+        const int64_t R = bound - (chains - 1) * L;   // cells of the last chain
+        nsub_last = R <= V ? 1 : 1 + (R - V + W - 1) / W;
+    }
+    return {chains + 1, bound, (unsigned)K, (unsigned)nsub_last};
+}
+
+// Automatic chain length: the longest chain (at most 8 windows) that still leaves every resident workgroup TWO items per level.  With
+// fewer the dataflow waits for its producers and loses far more than the shorter halo gains (profiles/r08_lab_rk4_chain.log section 1,
+// 1024 resident workgroups: N = 2^20 gains 2.7 % at K = 2, 2.2 items per workgroup, and loses 4 % at K = 3, 1.46 items, and 20 % at
+// K = 4, 1.09 items; N = 2^21 is best at K = 4, 2.17 items; N = 2^22 gains 5.6 % at K = 8, 2.15 items).  Grids under ~950 000 cells keep
+// rk4_stream_kernel.
+static int64_t rk4_chain_auto(int64_t n, int64_t resident)
+{
+    for (int64_t K = 8; K >= 2; K--)
+        if (chain_shape(n, K).items >= 2 * resident) return K;
+    return 1;
+}
+
+template <int LAYOUT>
+static void launch_chain_t(marl_ctx* ctx, double* a, double* b, double dt, unsigned levels, const ChainShape& sh, unsigned blocks, double* c)
+{
+    hipLaunchKernelGGL((rk4_chain_kernel<256, LAYOUT, 4>), dim3(blocks), dim3(256), 0, ctx->stream, a, b, ctx->dconsts, ctx->slab, dt, levels,
+                       (unsigned)sh.items, ctx->sq, ctx->sq + 2, ctx->sq_sticky, ctx->sq_item_base, ctx->sq_level_base, c, sh.K, sh.nsub_last, sh.bound);
+}
+
 // *result: where the state is afterwards (a or b)
 static int rk4_stream(marl_ctx* ctx, double* a, double* b, int layout, double dt, int per, int64_t levels, double** result)
 {
-    const int64_t n = ctx->slab.out_hi - ctx->slab.out_lo, V = MARL_LAB_STREAM_BLK - 8 * per, tiles = (n + V - 1) / V;
+    const int64_t n = ctx->slab.out_hi - ctx->slab.out_lo, V = MARL_LAB_STREAM_BLK - 8 * per;
     if (!ctx->cus) {
         hipDeviceProp_t prop;
         HIP_OK(ctx, hipGetDeviceProperties(&prop, ctx->device));
         ctx->cus = prop.multiProcessorCount;
     }
+    // items of a level: the tiles of rk4_stream_kernel, or the chains of rk4_chain_kernel + the last tile (`tiles` is that number below)
+    int64_t K = 1;
+    if (per == 4 && !ctx->var_dphi && MARL_LAB_STREAM_BLK == 256 && ctx->rk4_chain > 0)
+        K = ctx->rk4_chain == 1 ? rk4_chain_auto(n, 4 * (int64_t)ctx->cus) : ctx->rk4_chain;
+    const ChainShape shape = chain_shape(n, K);
+    const int64_t tiles = K >= 2 ? shape.items : (n + V - 1) / V;
     if (!ctx->sq_host) HIP_OK(ctx, hipHostMalloc((void**)&ctx->sq_host, sizeof(unsigned), hipHostMallocDefault));
     if (!ctx->sq_sticky) {
         HIP_OK(ctx, hipMalloc((void**)&ctx->sq_sticky, sizeof(unsigned)));
@@ -649,7 +702,10 @@ static int rk4_stream(marl_ctx* ctx, double* a, double* b, int layout, double dt
             }
             c = ctx->stream_c;
         }
-        switch (per) {
+        if (K >= 2) {
+            if (layout == LAYOUT_TILED) launch_chain_t<LAYOUT_TILED>(ctx, a, b, dt, (unsigned)lv, shape, blocks, c);
+            else launch_chain_t<LAYOUT_FIELD_MAJOR>(ctx, a, b, dt, (unsigned)lv, shape, blocks, c);
+        } else switch (per) {
             case 1: if (ctx->var_dphi) launch_stream_t<1, true>(ctx, a, b, layout, dt, (unsigned)lv, (unsigned)tiles, blocks, c);
                     else launch_stream_t<1>(ctx, a, b, layout, dt, (unsigned)lv, (unsigned)tiles, blocks, c);
                     break;

@@ -95,7 +95,9 @@ __device__ unsigned long long marl_lab_phase[8];
 // the five fields of a cell, unrolled (the Runge-Kutta combinations)
 #define MARL_FIELDS _Pragma("unroll") for (int f = 0; f < NF; f++)
 
-template <int BLK, bool REUSE = true, bool VD = false>
+// SEAM (rk4_chain_kernel only; 0 = none, and then nothing of it exists): the lane whose stage state is recorded at every evaluation
+// for the next window of a chain, whose thread 0 takes its left neighbour from that record instead of from a recomputed halo.
+template <int BLK, bool REUSE = true, bool VD = false, int SEAM = 0>
 struct StencilBlock {
     static constexpr int EDGE_DOUBLES = 2 * NF * BLK;       // edges [parity][field][thread]
     static constexpr bool CACHE_LDS = PC_LDS_SLOTS > 0;
@@ -129,6 +131,14 @@ struct StencilBlock {
     __device__ __forceinline__ unsigned is_edge() const { return masks & 0x101u; }   // first or last: non-zero
     PointCache<(CACHE && CACHE_LDS) ? BLK : 0> cache;  // centre of the transcendental expansions (TR_FILL / TR_REUSE / TR_AUTO)
     bool reuse_live = false;     // wave-uniform: the centre is filled and no evaluation since has fallen out of range
+    // SEAM: the record in LDS, [evaluation][parity][8 doubles, NF used], and - ONE scalar register, the loop sits at its cap of those too -
+    // where the current evaluation writes in it (bits 0-15: 16 * evaluation + 8 * parity; the other parity is what it reads) and whether
+    // it reads at all (SEAM_READS: not in a window with a left halo of its own), and whether this is the workgroup's wave 0 (SEAM_WAVE0:
+    // its thread 0 reads) or the recording lane's wave (SEAM_WAVEW)
+    static constexpr int SEAM_STRIDE = 16, SEAM_READS = 0x10000, SEAM_WAVE0 = 0x20000, SEAM_WAVEW = 0x40000;
+    static_assert(SEAM < BLK, "the recording lane is a lane of the window");
+    double* seam = nullptr;
+    int seam_pos = 0;
 #ifdef MARL_LAB_PHASE_CLOCK
     unsigned long long ph_acc[6] = {0, 0, 0, 0, 0, 0}, ph_last = __builtin_amdgcn_s_memtime();
     __device__ __forceinline__ void phase_flush()
@@ -176,6 +186,21 @@ struct StencilBlock {
         double* e = lds + parity * (NF * BLK);
 #pragma unroll
         for (int f = 0; f < NF; f++) e[f * BLK + tid] = ys[f];
+        if constexpr (SEAM > 0) {
+            // The recording lane also writes its stage state into the seam record - here, in front of the own-cell phase, so that nothing
+            // of the seam lies between the barrier and the stencil phase of its wave.  A scalar branch: three waves of four skip it, no
+            // wave executes a select.  (The lane mask is rebuilt from an opaque copy, one v_cmp in that one wave: held across the
+            // evaluations it costs a scalar pair, and the loop sits at its cap of those: profiles/r08_lab_rk4_chain.log, section 6.)
+            if (seam_pos & SEAM_WAVEW) {
+                int tw = tid;
+                asm volatile("" : "+v"(tw));
+                if (tw == SEAM) {
+                    double* rec = seam + (seam_pos & 0xffff);
+#pragma unroll
+                    for (int f = 0; f < NF; f++) rec[f] = ys[f];
+                }
+            }
+        }
         MARL_PHASE_MARK(0);
         PointLocal pl;
         MARL_ONCE point_local<CACHE ? MODE : TR_PLAIN, (CACHE && CACHE_LDS) ? BLK : 0, VD>(ys, in_zone(), K, C, T, pl, aux, cache, reuse_live);
@@ -187,6 +212,21 @@ struct StencilBlock {
         double left[NF], right[NF];
 #pragma unroll
         for (int f = 0; f < NF; f++) left[f] = e[f * BLK + tl];
+        if constexpr (SEAM > 0) {
+            // Thread 0 of a chained window takes its left neighbour from what the recording lane of the window before wrote at the same
+            // evaluation (the other parity; 4 * NSTEPS barriers ago, and the slot is next written 4 * NSTEPS barriers from now).  Wave 0
+            // only, and only in a window that reads: one scalar test.
+            if ((seam_pos & (SEAM_WAVE0 | SEAM_READS)) == (SEAM_WAVE0 | SEAM_READS)) {
+                int t0 = tid;
+                asm volatile("" : "+v"(t0));
+                if (t0 == 0) {
+                    const double* prev = seam + ((seam_pos & 0xffff) ^ 8);
+#pragma unroll
+                    for (int f = 0; f < NF; f++) left[f] = prev[f];
+                }
+            }
+            seam_pos += SEAM_STRIDE;
+        }
         // the solids are differenced against the upwind neighbour only: with U > 0 in every lane (burial - the normal
         // case) the right-hand values of CA and CC are never used and their two LDS reads are skipped
         const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl.upw) != 0;
@@ -671,6 +711,119 @@ rk4_stream_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ cons
             s_abort = 0;
 #endif
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The streamed loop with CHAINED windows: a work item is `nsub` windows processed left to right by the same workgroup.
+//
+// A window of rk4_stream_kernel recomputes a halo of H = 4 * NSTEPS cells on each side and writes BLK - 2 H cells: one lane in
+// eight (BLK = 256, NSTEPS = 4) works for nothing.  Here only the first window of an item has a left halo.  While a window
+// runs, the stage state that lane BLK - H - 1 - the last cell it writes - passes to each of the 4 * NSTEPS evaluations is
+// recorded (StencilBlock, SEAM).  The next window starts with thread 0 on the first cell its predecessor did not write, and thread 0
+// takes its left neighbour at evaluation e from that record: it needs no left halo and writes BLK - H cells.
+//   * Validity: thread BLK - 1 - m has a valid state up to evaluation m + 1, so lane BLK - H - 1 is valid through all of them,
+//     and so is every value it records.  Thread 0's cell itself is loaded from the level's input like every other cell.
+//   * The record has two parities that alternate by window: the lane's write at evaluation e (in front of the exchange barrier), the
+//     successor's read of it (behind the barrier of its evaluation e) and the next write to the same slot are 4 * NSTEPS barriers
+//     apart each - the chain needs no barrier of its own.
+//   * Stores of a window are not waited for before the next one starts; the item ends as in rk4_stream_kernel.
+// Items of a level (host: rk4_stream): `items - 1` chains tile [out_lo, out_lo + bound), each V + (K - 1) (BLK - H) cells, the last
+// one `nsub_last` windows and clipped at the bound; the LAST item is the grid's last tile of the unchained decomposition,
+// [bound, out_hi), as ONE plain window with both halos - so the waves that hold the two physical boundary cells consist of the
+// same cells as in rk4_stream_kernel and in the per-level launches, and take the same tier of the transcendental reuse.
+// Everything else - queue, done[], sticky flag, ping-pong / third buffer, the shape of the work loop and why it has that shape -
+// is rk4_stream_kernel's; an item still depends on items t-1, t, t+1 of the level before (host, chain_shape: no item but the
+// last is narrower than H cells).  tools/check_stream_isa.py checks I1-I5 on this kernel too (tests/test_chain_isa.py).
+// ---------------------------------------------------------------------------------------------
+template <int BLK, int LAYOUT, int NSTEPS>
+__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4, 8)))
+rk4_chain_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ consts, Slab S, double dt, unsigned levels, unsigned items,
+                 unsigned* queue, unsigned* done, unsigned* sticky, unsigned item_base, unsigned level_base, double* bufC,
+                 unsigned K, unsigned nsub_last, int64_t bound)
+{
+    constexpr int H = 4 * NSTEPS;
+    constexpr int V = BLK - 2 * H;     // cells the first window of an item writes
+    constexpr int W = BLK - H;         // ... and every later one
+    static_assert(V > 0, "window too small for the fused halo");
+    using SB = StencilBlock<BLK, true, false, BLK - H - 1>;
+    __shared__ double lds[SB::LDS_DOUBLES];
+    __shared__ double seam[H * SB::SEAM_STRIDE];
+    __shared__ unsigned s_item, s_abort;
+    const DevConsts& C = consts[0];
+    SB sb(lds, 0, consts);   // tables once per workgroup (barrier inside)
+    sb.seam = seam;
+    const unsigned total = levels * items;   // (host: < 2^31)
+    const unsigned chains = items - 1;
+
+    while (true) {
+        // (the shape of this loop: see rk4_stream_kernel)
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s_item = __hip_atomic_fetch_add(&queue[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - item_base;
+            s_abort = 0;
+        }
+        __syncthreads();
+        const unsigned item = __builtin_amdgcn_readfirstlane(s_item);   // (in a scalar register: the trip count below derives from it)
+        if (item >= total) break;
+        const unsigned level = item / items, tile = item - level * items;
+        if (level > 0) {
+            if (threadIdx.x < 3) {
+                const int64_t t = (int64_t)tile - 1 + threadIdx.x;
+                if (t >= 0 && t < (int64_t)items) {
+                    unsigned spins = 0;
+                    while ((int)(__hip_atomic_load(&done[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (level_base + level)) < 0) {
+                        __builtin_amdgcn_s_sleep(4);
+                        if (++spins > STREAM_SPIN_LIMIT ||
+                            ((spins & 255u) == 0 && __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                            __hip_atomic_store(sticky, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            s_abort = 1;
+                            break;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (s_abort) break;
+        }
+        const double* src = bufC ? (level == 0 ? bufA : ((level & 1u) ? bufB : bufC)) : ((level & 1u) ? bufB : bufA);
+        double* dst = bufC ? (level + 1 == levels ? bufA : ((level & 1u) ? bufC : bufB)) : ((level & 1u) ? bufA : bufB);
+        // the item's windows (all wave-uniform): window j has its thread 0 on local cell first + j W
+        const bool chain = tile < chains;
+        const unsigned nsub = chain ? (tile + 1 == chains ? nsub_last : K) : 1u;
+        const int64_t first = S.out_lo - H + (chain ? (int64_t)tile * (V + (int64_t)W * (K - 1)) : bound);
+        const int64_t clip = chain ? S.out_lo + bound : S.out_hi;
+#pragma unroll 1
+        for (unsigned j = 0; j < nsub; j++) {
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));   // opaque: what derives from the thread index is recomputed per window, not carried across the loops
+            sb.rebind(tid);
+            const int64_t l = first + (int64_t)j * W + tid;
+            const bool in = l >= 0 && l < S.n_buf;
+            double y[NF];
+#pragma unroll
+            for (int f = 0; f < NF; f++)
+                y[f] = in ? __hip_atomic_load(src + at<LAYOUT>(f, l, S.ld), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : C.bc[f];
+            sb.set_window(l + S.goff);
+            sb.reuse_live = false;   // every window fills its own expansion centre, as an item of rk4_stream_kernel does
+            // (readfirstlane: in a scalar register; left to itself the compiler builds it per lane from a lane mask)
+            sb.seam_pos = __builtin_amdgcn_readfirstlane((int)(j & 1u) * 8 + (j ? SB::SEAM_READS : 0) + (tid < 64 ? SB::SEAM_WAVE0 : 0)
+                                                         + (tid / 64 == (BLK - H - 1) / 64 ? SB::SEAM_WAVEW : 0));
+            rk4_advance<NSTEPS>(sb, y, dt);
+            const int lo = j ? 0 : H;
+            int ts = threadIdx.x;
+            asm volatile("" : "+v"(ts));    // (the cell index again: two registers less across the evaluations)
+            const int64_t ls = first + (int64_t)j * W + ts;
+            if (ts >= lo && ts < BLK - H && ls < clip) {
+#pragma unroll
+                for (int f = 0; f < NF; f++) __hip_atomic_store(dst + at<LAYOUT>(f, ls, S.ld), y[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        __builtin_amdgcn_s_waitcnt(0);   // this thread's stores - of every window of the item - have been acknowledged
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        __syncthreads();                 // ... and everybody else's (and everybody has read s_item, s_abort)
+        if (threadIdx.x == 0) __hip_atomic_store(&done[tile], level_base + level + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
