@@ -155,6 +155,18 @@ int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, doub
 int marl_sweep_rk45_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                              int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                              int64_t* n_done, marl_stats* stats);
+/* the sweep with t_eval and the monitors' root times: the reference prints and stores the roots of its seven monitors for every
+ * run (marlpde/Evolve_scenario.py:118-145, 175-177; solve_ivp(..., events=[7]), non-terminal, both directions).  Located inside
+ * the sweep kernel as scipy locates them (ivp.py:673-694, solve_event_equation :51-76): Brent's method, xtol = rtol = 4 eps, on
+ * the dense output of the accepted step in which a monitor changes sign.  Steps, state, frames and statistics are those of
+ * marl_sweep_rk45_eval_dev (nfev included).
+ * t_events: host, [n_instances][7][max_events]; entry k of monitor e is its k-th root, NaN beyond min(n_events[e], max_events);
+ * stats[b].n_events[e] counts every sign change, located or not.  t_events == NULL or max_events <= 0 is
+ * marl_sweep_rk45_eval_dev.  n_eval = 0 is allowed here (t_eval, y_eval_dev, n_done may then be NULL).  t1 == t0: no step, no
+ * roots.  Synchronises. */
+int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                               int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,

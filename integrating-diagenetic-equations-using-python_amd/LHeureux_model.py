@@ -434,30 +434,41 @@ class LMAHeureuxPorosityDiff:
         return [RK45Result(s, t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
                 for b, s in enumerate(stats)]
 
-    def sweep_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None):
+    def sweep_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
+                          events=False, max_events=64):
         """Every instance integrated with adaptive RK45, one workgroup each (marl_sweep_rk45_dev); device states [instances][5N]
         in place.  Returns one :class:`RK45Result` per instance.
 
         With ``t_eval`` (sorted sample times within ``t_span``, shared by all instances) the sweep also writes the time series
         that ``solve_ivp(..., t_eval=)`` returns (marl_sweep_rk45_eval_dev): ``y_eval_dev_ptr`` is device memory
         [instances][len(t_eval)][5N]; each result carries ``t = t_eval[:n_frames]``, the samples up to the time that instance
-        reached, and the frames stay on the device - frames beyond ``n_frames`` are not written."""
+        reached, and the frames stay on the device - frames beyond ``n_frames`` are not written.
+
+        ``events=True``: the monitors' root times are located inside the sweep (marl_sweep_rk45_events_dev) and returned as
+        ``t_events`` - a list of 7 arrays per instance, ``min(n_events[e], max_events)`` long, what the reference prints and stores
+        for every run (Evolve_scenario.py:118-145, 175-177); otherwise sign changes are only counted.  Combinable with ``t_eval``."""
         stats = (MarlStats * self.n_instances)()
-        if t_eval is None:
+        locate = bool(events) and int(max_events) > 0
+        if t_eval is None and not locate:
             rc = self._lib.marl_sweep_rk45_dev(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]),
                                                float(first_step), float(rtol), float(atol), int(max_attempts), stats)
             self._check(rc, "marl_sweep_rk45_dev")
             return [RK45Result(s) for s in stats]
-        te = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
+        te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
         if te.size and not y_eval_dev_ptr:
             raise ValueError("sweep_rk45_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
         n_done = np.zeros(self.n_instances, dtype=np.int64)
-        rc = self._lib.marl_sweep_rk45_eval_dev(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]),
-                                                float(first_step), float(rtol), float(atol), int(max_attempts),
-                                                _as_ptr(te) if te.size else None, te.size,
-                                                C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done), stats)
-        self._check(rc, "marl_sweep_rk45_eval_dev")
-        return [RK45Result(s, t=te[:int(k)].copy()) for s, k in zip(stats, n_done)]
+        args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
+                int(max_attempts), _as_ptr(te) if te.size else None, te.size, C.c_void_p(y_eval_dev_ptr) if te.size else None,
+                _as_ptr(n_done))
+        if not locate:
+            self._check(self._lib.marl_sweep_rk45_eval_dev(*args, stats), "marl_sweep_rk45_eval_dev")
+            return [RK45Result(s, t=te[:int(k)].copy()) for s, k in zip(stats, n_done)]
+        tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan)
+        self._check(self._lib.marl_sweep_rk45_events_dev(*args, _as_ptr(tev), int(max_events), stats), "marl_sweep_rk45_events_dev")
+        return [RK45Result(s, t=None if t_eval is None else te[:int(k)].copy(),
+                           t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
+                for b, (s, k) in enumerate(zip(stats, n_done))]
 
 
 __all__ = ["LMAHeureuxPorosityDiff", "DepthGrid", "RK45Result", "FIELD_NAMES", "LAYOUT_FIELD_MAJOR", "LAYOUT_TILED"]

@@ -88,6 +88,7 @@ PROTOTYPES = {
     "marl_integrate_rk45_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
     "marl_sweep_rk45_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
     "marl_sweep_rk45_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, C.POINTER(MarlStats)]),
+    "marl_sweep_rk45_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
     "marl_integrate_radau": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_integrate_bdf": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_sweep_radau_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, C.POINTER(MarlStats)]),

@@ -74,6 +74,9 @@ struct marl_ctx {
     double* sw_teval = nullptr;
     size_t sw_teval_cap = 0;
     int64_t* sw_ndone = nullptr;   // [batch]
+    // sweeps that locate the monitors' roots (rk45_sweep_roots_kernel): the root times [batch][7][max_events], allocated on first use or growth
+    double* sw_tev = nullptr;
+    size_t sw_tev_cap = 0;
     // domain decomposition: this rank's message / the gathered messages (device), and the RCCL communicator (dlopen'ed API)
     double* dd_send = nullptr;
     double* dd_gathered = nullptr;
@@ -348,6 +351,7 @@ void marl_ctx_destroy(marl_ctx* ctx)
     if (ctx->hdt) (void)hipHostFree(ctx->hdt);
     if (ctx->sw_teval) (void)hipFree(ctx->sw_teval);
     if (ctx->sw_ndone) (void)hipFree(ctx->sw_ndone);
+    if (ctx->sw_tev) (void)hipFree(ctx->sw_tev);
     if (ctx->rccl_comm && ctx->rccl_destroy) (void)ctx->rccl_destroy(ctx->rccl_comm);
     if (ctx->dd_send) (void)hipFree(ctx->dd_send);
     if (ctx->dd_gathered) (void)hipFree(ctx->dd_gathered);
@@ -1326,6 +1330,65 @@ int marl_sweep_rk45_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1,
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
     if (t1 == t0 && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as rk45_run gives it to single runs
+        const size_t row = sizeof(double) * NF * ctx->N;
+        HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * n_eval, y_dev, row, row, (size_t)ctx->batch, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t b = 0; b < ctx->batch; b++) n_done[b] = 1;
+    }
+    return 0;
+}
+
+int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                               double* t_events, int64_t max_events, marl_stats* stats)
+{
+    if (!t_events || max_events <= 0)   // no roots asked for: the sweep with t_eval itself
+        return marl_sweep_rk45_eval_dev(ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done, stats);
+    if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
+        return ctx ? fail(ctx, -1, "marl_sweep_rk45_events_dev: invalid argument") : -1;
+    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
+    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
+    for (int64_t i = 0; i < n_eval; i++)
+        if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
+            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    const int blk = sweep_block(ctx);
+    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
+    if (n_eval > 0 && ctx->sw_teval_cap < (size_t)n_eval) {
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->sw_teval) HIP_OK(ctx, hipFree(ctx->sw_teval));
+        ctx->sw_teval = nullptr;
+        ctx->sw_teval_cap = 0;
+        HIP_OK(ctx, hipMalloc((void**)&ctx->sw_teval, sizeof(double) * n_eval));
+        ctx->sw_teval_cap = (size_t)n_eval;
+    }
+    if (!ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
+    const size_t n_tev = (size_t)ctx->batch * 7 * (size_t)max_events;
+    if (ctx->sw_tev_cap < n_tev) {
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->sw_tev) HIP_OK(ctx, hipFree(ctx->sw_tev));
+        ctx->sw_tev = nullptr;
+        ctx->sw_tev_cap = 0;
+        HIP_OK(ctx, hipMalloc((void**)&ctx->sw_tev, sizeof(double) * n_tev));
+        ctx->sw_tev_cap = n_tev;
+    }
+    HIP_OK(ctx, hipMemsetAsync(ctx->sw_tev, 0xff, sizeof(double) * n_tev, ctx->stream));   // NaN beyond the roots found (all bits set is a quiet NaN)
+    if (n_eval > 0) HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, t_eval, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
+    if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
+    hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
+                       atol, (int64_t)NF * ctx->N, max_attempts, 0);
+    LAUNCH_OK(ctx);
+    const dim3 grid((unsigned)ctx->batch);
+    SWEEP_DISPATCH(rk45_sweep_roots_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone,
+                   ctx->sw_tev, max_events)
+    LAUNCH_OK(ctx);
+    HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_done) HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(t_events, ctx->sw_tev, sizeof(double) * n_tev, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
+    if (t1 == t0 && n_eval > 0 && t_eval[0] == t0) {   // no step is taken (base.py:189-194), so no roots; the sample at t0 is y0, as in the eval entry
         const size_t row = sizeof(double) * NF * ctx->N;
         HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * n_eval, y_dev, row, row, (size_t)ctx->batch, hipMemcpyDeviceToDevice, ctx->stream));
         HIP_OK(ctx, hipStreamSynchronize(ctx->stream));

@@ -1012,6 +1012,40 @@ __device__ __forceinline__ double rk45_monitor_of_record(const double* rec, int 
     return (e == 3 || e == 4) ? rec[slot] - 1.0 : rec[slot];
 }
 
+// the record slot (1..7) behind monitor e, as rk45_monitor_of_record reads it; monitors 3 and 4 are that slot minus one
+__device__ __forceinline__ int rk45_monitor_slot(int e)
+{
+    return (e < 3) ? e + 1 : (e == 3 ? 5 : (e == 4 ? 6 : (e == 5 ? 4 : 7)));
+}
+
+// One pass of Brent's method (scipy.optimize.brentq as solve_event_equation calls it, ivp.py:51-76: xtol = rtol = 4 eps, at most 100
+// iterations) from the top of its loop to the next function evaluation.  Returns true when the root is final (c.xcur); false: evaluate
+// at c.xcur.  BS: any structure with the fields below - the Radau sweeps' controller (RadauCtl), the RK45 sweep's BrentState.
+struct BrentState { double xpre, xcur, xblk, fpre, fcur, fblk, spre, scur; };
+template <class BS>
+__device__ __forceinline__ bool brent_advance(BS& c)
+{
+    const double xtol = 4 * 2.220446049250313e-16, rtol = xtol;
+    if (c.fpre != 0 && c.fcur != 0 && ((c.fpre < 0) != (c.fcur < 0))) { c.xblk = c.xpre; c.fblk = c.fpre; c.spre = c.scur = c.xcur - c.xpre; }
+    if (fabs(c.fblk) < fabs(c.fcur)) { c.xpre = c.xcur; c.xcur = c.xblk; c.xblk = c.xpre; c.fpre = c.fcur; c.fcur = c.fblk; c.fblk = c.fpre; }
+    const double delta = (xtol + rtol * fabs(c.xcur)) / 2, sbis = (c.xblk - c.xcur) / 2;
+    if (c.fcur == 0 || fabs(sbis) < delta) return true;
+    if (fabs(c.spre) > delta && fabs(c.fcur) < fabs(c.fpre)) {
+        double stry;
+        if (c.xpre == c.xblk) stry = -c.fcur * (c.xcur - c.xpre) / (c.fcur - c.fpre);
+        else {
+            const double dpre = (c.fpre - c.fcur) / (c.xpre - c.xcur), dblk = (c.fblk - c.fcur) / (c.xblk - c.xcur);
+            stry = -c.fcur * (c.fblk * dblk - c.fpre * dpre) / (dblk * dpre * (c.fblk - c.fpre));
+        }
+        const double lim = fmin(fabs(c.spre), 3 * fabs(sbis) - delta);
+        if (2 * fabs(stry) < lim) { c.spre = c.scur; c.scur = stry; }
+        else { c.spre = sbis; c.scur = sbis; }
+    } else { c.spre = sbis; c.scur = sbis; }
+    c.xpre = c.xcur; c.fpre = c.fcur;
+    if (fabs(c.scur) > delta) c.xcur += c.scur; else c.xcur += (sbis > 0 ? delta : -delta);
+    return false;
+}
+
 __device__ __forceinline__ int rk45_events(Rk45Ctrl& c, const double (&rec)[NQ])
 {
     int fired = 0;
@@ -1959,13 +1993,17 @@ __device__ __forceinline__ DenseWeights dense_weights(double x)
 
 // EVAL (FAST only; rk45_sweep_eval_kernel): the t_eval samples that fall into an accepted step are written by dense-output replays of
 // that step inside the loop (see there); without it the four trailing arguments are unused and the code is what it was without them.
-template <int BLK, bool VD, bool FAST, bool EVAL = false>
+// ROOTS (FAST and EVAL only; rk45_sweep_roots_kernel): the root times of the monitors that change sign in an accepted step are located
+// by Brent's method on dense-output replays of that step, before its samples and its commit (see there); two more arguments.
+template <int BLK, bool VD, bool FAST, bool EVAL = false, bool ROOTS = false>
 __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls, int64_t N,
                                                 double* __restrict__ Yold, double* __restrict__ Fold,
                                                 const double* __restrict__ t_eval = nullptr, int64_t n_eval = 0,
-                                                double* __restrict__ Yeval = nullptr, int64_t* __restrict__ n_done = nullptr)
+                                                double* __restrict__ Yeval = nullptr, int64_t* __restrict__ n_done = nullptr,
+                                                double* __restrict__ t_events = nullptr, int64_t max_events = 0)
 {
     static_assert(FAST || !EVAL, "the sampling loop is built on the replicated controller");
+    static_assert((FAST && EVAL) || !ROOTS, "a Brent function evaluation is a dense-output replay");
     using SB = StencilBlock<BLK, false, VD>;
     constexpr int NW = BLK / 64;
     constexpr int NMON = NQ - 1;                                  // the seven monitor extrema (record slots 1..7)
@@ -2076,13 +2114,119 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         auto event_bookkeeping = [&]() {             // lanes 0..6 of wave 0: one monitor each; sc.t_old / sc.h_prev / sc.t describe that step
             if (threadIdx.x < 7) rk45_event_one(sc, threadIdx.x, rk45_monitor_of_record(rec, threadIdx.x));
         };
+        // ROOTS: the roots of the monitors that changed sign in an accepted step (ivp.py:673-694, solve_event_equation :51-76) are
+        // located before its samples and its commit, by the same replays: one Brent function evaluation is one PROBE trip of the loop -
+        // the dp45_attempt call with h = h_prev and the weights of the abscissa, the monitors of  y + h esum  through the monitor columns,
+        // and one pass of the Brent state machine, replicated in every wave like the controller (its state in SGPRs).
+        //   - the sign test cannot wait for the next attempt: one barrier after the reduction into rec, then every wave forms the same mask
+        //     of monitors to locate from rec, sc.g and sc.n_events.  No monitor to locate (nearly every step): the bookkeeping stays
+        //     deferred as above - it writes sc.g, and the next attempt's barriers separate it from these reads.  Otherwise a second
+        //     barrier, the bookkeeping at once (g <- g_new for all seven, counts, ev_first / ev_last), and the probes: they overwrite the
+        //     monitor columns, which every wave has finished with, and leave rec alone;
+        //   - a probe decides no step: c (nfev included), sc, rec, y_new / k7, ie are untouched, and whether a trip is a probe follows
+        //     from replicated scalars only, so its barriers are reached by every wave or by none;
+        //   - order within a step: roots (monitors ascending), then samples, then the commit and, for the last step, the way out.
+        int ev_mask = 0;                             // monitors of the step just accepted still to be located (bit e)
+        int br_e = 0, br_phase = 0, br_iter = 0;     // the monitor being located; 0 no probe, 1 f(a) asked, 2 f(b) asked, 3 iterating
+        double br_fa = 0.0, br_t = 0.0;              // f(a); the time of the probe in flight
+        BrentState bs = {};
+        auto probe_at = [&](double tp) {             // the next trip evaluates the monitors at time tp of the step just accepted
+            br_t = to_sgpr(tp);
+            const DenseWeights w = dense_weights((br_t - c.t_old) / c.h_prev);
+#pragma unroll
+            for (int j = 0; j < 7; j++) dw.w[j] = to_sgpr(w.w[j]);
+        };
+        auto first_probe = [&]() {                   // Brent on the lowest monitor of ev_mask over [t_old, t]: f(a) first
+            br_e = to_sgpr((int32_t)__builtin_ctz((unsigned)ev_mask));
+            br_phase = 1;
+            br_iter = 0;
+            probe_at(c.t_old);
+        };
         while (true) {
-            const double h = (EVAL && sampling) ? c.h_prev : c.h_try;
+            bool replay = sampling;                  // workgroup-uniform: this trip is no attempt
+            if constexpr (ROOTS) replay = sampling || br_phase != 0;
+            const double h = (EVAL && replay) ? c.h_prev : c.h_try;
             // (the first evaluation's exchange barrier also orders the monitor reduction of the previous attempt before the
             // event bookkeeping below; dp45_attempt is opaque, so the bookkeeping follows the whole attempt's evaluations -
             // still before this attempt's own decision changes c.t_old / c.h_prev / c.t)
-            if constexpr (EVAL) dp45_attempt<BLK, false, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, sampling);
+            if constexpr (EVAL) dp45_attempt<BLK, false, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, replay);
             else dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            if constexpr (ROOTS) {
+                if (br_phase != 0) {                 // workgroup-uniform
+                    double q[NQ];
+                    monitors_init(q);
+                    MARL_ONCE if (l0 < N) {
+                        double d[NF];
+#pragma unroll
+                        for (int f = 0; f < NF; f++) d[f] = (br_t == c.t_old) ? MARL_Y(f) : h * esum[f] + MARL_Y(f);   // (x = 0: as the frames)
+                        double U, W;
+                        uw_point(d[4], C, sb.T, U, W);
+                        monitors_accumulate<true>(q, d, U, W);   // (a state inside an accepted step: all finite)
+                    }
+#pragma unroll
+                    for (int j = 1; j < NQ; j++) mon[(j - 1) * BLK + threadIdx.x] = q[j];
+                    __syncthreads();
+                    // monitor br_e of the probed state: EVERY wave reduces that one column, in the same order - the same value everywhere
+                    const int slot = rk45_monitor_slot(br_e);
+                    const double sgn = (slot <= NQMIN) ? 1.0 : -1.0;
+                    double a = sgn * mon[(slot - 1) * BLK + lane];
+#pragma unroll
+                    for (int i = 1; i < NW; i++) a = __builtin_fmin(a, sgn * mon[(slot - 1) * BLK + lane + 64 * i]);
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) a = __builtin_fmin(a, __shfl_xor(a, off, 64));
+                    const double val = to_sgpr((br_e == 3 || br_e == 4) ? sgn * a - 1.0 : sgn * a);
+                    // the order of radau_control_step's PC_BRENT: f(a), f(b), the early returns, then brent_advance until the root or 100 iterations
+                    if (br_phase == 1) {
+                        br_fa = val;
+                        br_phase = 2;
+                        probe_at(c.t);
+                        continue;
+                    }
+                    bool done = false;
+                    double root = 0.0;
+                    if (br_phase == 2) {
+                        if (br_fa == 0.0) { done = true; root = c.t_old; }
+                        else if (val == 0.0) { done = true; root = c.t; }
+                        else {
+                            bs.xpre = c.t_old; bs.xcur = c.t; bs.fpre = br_fa; bs.fcur = val;
+                            bs.xblk = 0.0; bs.fblk = 0.0; bs.spre = 0.0; bs.scur = 0.0;
+                            br_phase = 3;
+                        }
+                    } else {
+                        bs.fcur = val;
+                        br_iter++;
+                        if (br_iter >= 100) { done = true; root = bs.xcur; }
+                    }
+                    if (!done) {
+                        if (brent_advance(bs)) { done = true; root = bs.xcur; }
+                    }
+                    bs.xpre = to_sgpr(bs.xpre); bs.xcur = to_sgpr(bs.xcur); bs.xblk = to_sgpr(bs.xblk); bs.fpre = to_sgpr(bs.fpre);
+                    bs.fcur = to_sgpr(bs.fcur); bs.fblk = to_sgpr(bs.fblk); bs.spre = to_sgpr(bs.spre); bs.scur = to_sgpr(bs.scur);
+                    if (!done) {
+                        probe_at(bs.xcur);
+                        continue;
+                    }
+                    // (wave 0 did this step's bookkeeping before its first probe: n_events[br_e] - 1 is the count before the step, < max_events)
+                    if (threadIdx.x == 0) t_events[((int64_t)blockIdx.x * 7 + br_e) * max_events + (sc.n_events[br_e] - 1)] = root;
+                    ev_mask = to_sgpr((int32_t)(ev_mask & ~(1 << br_e)));
+                    if (ev_mask != 0) {
+                        first_probe();
+                        continue;
+                    }
+                    br_phase = 0;
+                    if (next_sample()) {             // then the step's samples
+                        sampling = true;
+                        continue;
+                    }
+#pragma unroll
+                    for (int f = 0; f < NF; f++) {   // the postponed commit, as after the last sample
+                        if (f < PARK) pk[f * BLK] = yn[f]; else y[f] = yn[f];
+                        k1[f] = k7[f];
+                    }
+                    if (c.status != ST_RUNNING) break;
+                    continue;
+                }
+            }
             if constexpr (EVAL) {
                 if (sampling) {                      // workgroup-uniform
                     double* fr = Yeval + ((int64_t)blockIdx.x * n_eval + ie) * (NF * N);
@@ -2154,6 +2298,24 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                 if (status != ST_RUNNING && Yold) {
                     MARL_KEEP_OLD_STEP()
                 }
+                if constexpr (ROOTS) {
+                    __syncthreads();                 // rec is whole: the sign test of this step, the same in every wave
+                    int m = 0;
+#pragma unroll
+                    for (int e = 0; e < 7; e++) {    // ivp.py:149-151, as rk45_event_one; beyond max_events a sign change is only counted
+                        const double go = sc.g[e], gn = rk45_monitor_of_record(rec, e);
+                        const bool up = go <= 0.0 && gn >= 0.0, down = go >= 0.0 && gn <= 0.0;
+                        if ((up || down) && sc.n_events[e] < max_events) m |= 1 << e;
+                    }
+                    ev_mask = to_sgpr((int32_t)m);
+                    if (ev_mask != 0) {              // roots inside this step: locate them first
+                        __syncthreads();             // every wave has read sc.g / sc.n_events
+                        event_bookkeeping();
+                        events_pending = false;
+                        first_probe();
+                        continue;
+                    }
+                }
                 if constexpr (EVAL) {
                     if (next_sample()) {             // samples inside this step: replay it first, commit afterwards
                         sampling = true;
@@ -2219,6 +2381,21 @@ __global__ void __launch_bounds__(BLK) rk45_sweep_eval_kernel(double* __restrict
                                                               double* __restrict__ Yeval, int64_t* __restrict__ n_done)
 {
     rk45_sweep_body<BLK, VD, true, true>(Y, consts, ctrls, N, nullptr, nullptr, t_eval, n_eval, Yeval, n_done);
+}
+
+// sweeps that also locate the monitors' roots (the reference's events=[7], Evolve_scenario.py:118-145, 175-177): the loop of
+// rk45_sweep_eval_kernel with one more barrier per accepted step, and in a step in which a monitor changes sign Brent's method on
+// dense-output replays of that step (scipy ivp.py:673-694, solve_event_equation :51-76).
+//   t_events: [instance][7][max_events], filled by the caller (NaN); root k of monitor e of instance b at (b * 7 + e) * max_events + k,
+//   k < max_events - further sign changes are only counted (Rk45Ctrl.n_events).  n_eval may be 0 (t_eval, Yeval unused).
+template <int BLK, bool VD = false>
+__global__ void __launch_bounds__(BLK) rk45_sweep_roots_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
+                                                               Rk45Ctrl* __restrict__ ctrls, int64_t N,
+                                                               const double* __restrict__ t_eval, int64_t n_eval,
+                                                               double* __restrict__ Yeval, int64_t* __restrict__ n_done,
+                                                               double* __restrict__ t_events, int64_t max_events)
+{
+    rk45_sweep_body<BLK, VD, true, true, true>(Y, consts, ctrls, N, nullptr, nullptr, t_eval, n_eval, Yeval, n_done, t_events, max_events);
 }
 
 template <int BLK, bool VD = false>

@@ -34,31 +34,7 @@ __device__ __forceinline__ double predict_factor(double h_abs, double h_abs_old,
 enum : int { L_RHS1 = 0, L_ACCEPT, L_JAC, L_LU, L_NEWTON, L_ERR, L_RUNNING, L_DENSE, L_COUNT };
 
 // One instance's step logic from where it stopped to its next action (c.action, c.pc).  g_now: the seven monitors of the instance's y.
-// One pass of Brent's method (scipy.optimize.brentq as solve_event_equation calls it: xtol = rtol = 4 eps, at most 100 iterations)
-// from the top of its loop to the next function evaluation.  Returns true when the root is final (c.xcur); false: evaluate at c.xcur.
-__device__ __forceinline__ bool brent_advance(RadauCtl& c)
-{
-    const double xtol = 4 * EPS, rtol = xtol;
-    if (c.fpre != 0 && c.fcur != 0 && ((c.fpre < 0) != (c.fcur < 0))) { c.xblk = c.xpre; c.fblk = c.fpre; c.spre = c.scur = c.xcur - c.xpre; }
-    if (fabs(c.fblk) < fabs(c.fcur)) { c.xpre = c.xcur; c.xcur = c.xblk; c.xblk = c.xpre; c.fpre = c.fcur; c.fcur = c.fblk; c.fblk = c.fpre; }
-    const double delta = (xtol + rtol * fabs(c.xcur)) / 2, sbis = (c.xblk - c.xcur) / 2;
-    if (c.fcur == 0 || fabs(sbis) < delta) return true;
-    if (fabs(c.spre) > delta && fabs(c.fcur) < fabs(c.fpre)) {
-        double stry;
-        if (c.xpre == c.xblk) stry = -c.fcur * (c.xcur - c.xpre) / (c.fcur - c.fpre);
-        else {
-            const double dpre = (c.fpre - c.fcur) / (c.xpre - c.xcur), dblk = (c.fblk - c.fcur) / (c.xblk - c.xcur);
-            stry = -c.fcur * (c.fblk * dblk - c.fpre * dpre) / (dblk * dpre * (c.fblk - c.fpre));
-        }
-        const double lim = fmin(fabs(c.spre), 3 * fabs(sbis) - delta);
-        if (2 * fabs(stry) < lim) { c.spre = c.scur; c.scur = stry; }
-        else { c.spre = sbis; c.scur = sbis; }
-    } else { c.spre = sbis; c.scur = sbis; }
-    c.xpre = c.xcur; c.fpre = c.fcur;
-    if (fabs(c.scur) > delta) c.xcur += c.scur; else c.xcur += (sbis > 0 ? delta : -delta);
-    return false;
-}
-
+// (Brent's method: brent_advance, marl_kernels.h - shared with the RK45 sweep that locates roots, on RadauCtl's own fields here.)
 // g_dense: the seven monitors of the dense-output state the last A_DENSE action evaluated (event root finding); t_events: this
 // instance's root times [7][max_events] (NULL: sign changes are only counted).
 __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g_now)[7], int64_t n, const double* g_dense = nullptr, double* t_events = nullptr)

@@ -85,17 +85,19 @@ class HipSweepEngine:
             self._model.use_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
         return self._model
 
-    def integrate_rk45(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None):
+    def integrate_rk45(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64):
         """y0: (n_local, 5N) host array.  Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries
-        the samples that instance reached, as a single run's does: ``t`` (n_t,) and ``y`` (5N, n_t)."""
+        the samples that instance reached, as a single run's does: ``t`` (n_t,) and ``y`` (5N, n_t).  With ``events`` every result
+        carries ``t_events``, the root times of the seven monitors located inside the sweep (at most ``max_events`` each)."""
         yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
+        more = {"events": True, "max_events": max_events} if events else {}
         if t_eval is None:
-            res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+            res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
             return yd.cpu().numpy(), res
         n_eval = int(np.size(t_eval))
         frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
         res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
-                                           y_eval_dev_ptr=frames.data_ptr())
+                                           y_eval_dev_ptr=frames.data_ptr(), **more)
         frames = frames.cpu().numpy()
         for b, r in enumerate(res):
             r.y = frames[b, :len(r.t)].T.copy()
@@ -188,7 +190,7 @@ def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_att
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None):
+                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64):
     """Integrate every instance with adaptive RK45; ranks of ``group`` each take a contiguous shard (``balance``: see :func:`assign`).
 
     Returns ``(y_final, status, n_accepted, n_rejected, t_reached)`` - for ALL instances, in their order, when ``gather``,
@@ -197,13 +199,16 @@ def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_at
 
     With ``t_eval`` (sorted sample times within ``t_span``, the same for every instance) two more elements follow: ``n_frames``, the
     number of samples each instance reached, and ``y_eval`` of shape (instances, len(t_eval), 5N), the time series
-    ``solve_ivp(..., t_eval=)`` returns (Evolve_scenario.py:104-109) - NaN beyond an instance's ``n_frames``; ordered like the states."""
+    ``solve_ivp(..., t_eval=)`` returns (Evolve_scenario.py:104-109) - NaN beyond an instance's ``n_frames``; ordered like the states.
+
+    With ``events`` one last element follows: ``t_events``, per instance a list of 7 arrays - the root times of the reference's monitors
+    (Evolve_scenario.py:118-145, 175-177), at most ``max_events`` each, located inside the sweep; ordered like the states."""
     return _run_sweep("integrate_rk45", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, t_eval)
+                      balance, cost, t_eval, events, max_events)
 
 
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-               balance="contiguous", cost=None, t_eval=None):
+               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64):
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -224,6 +229,8 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
     if local:
         engine = engine_factory(base_parms, local)
         more = {"t_eval": t_eval} if sampled else {}
+        if events:   # (passed only when asked for: engines without root location keep working)
+            more |= {"events": True, "max_events": max_events}
         y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()
     else:   # (more ranks than instances)
@@ -235,17 +242,24 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
         for b, r in enumerate(res):
             frames[b, :len(r.t)] = np.asarray(r.y).T
         summary = np.concatenate([summary, np.array([len(r.t) for r in res], dtype=float).reshape(len(local), 1)], axis=1)
+    roots = [[np.asarray(t) for t in (r.t_events or [np.empty(0)] * 7)] for r in res] if events else None   # (max_events = 0: none located)
     if gather and world > 1:
         parts = [None] * world
-        dist.all_gather_object(parts, (mine, y, summary, frames), group=group)
+        dist.all_gather_object(parts, (mine, y, summary, frames, roots), group=group)
         y_all = np.empty((len(instances),) + y0.shape[1:])
         s_all = np.empty((len(instances), summary.shape[1]))
         f_all = np.full((len(instances), t_eval.size) + y0.shape[1:], np.nan) if sampled else None
-        for idx, yy, ss, ff in parts:   # back into the order of `instances`
+        r_all = [None] * len(instances) if events else None
+        for idx, yy, ss, ff, rr in parts:   # back into the order of `instances`
             y_all[idx] = yy
             s_all[idx] = ss
             if sampled:
                 f_all[idx] = ff
-        y, summary, frames = y_all, s_all, f_all
+            if events:
+                for i, r in zip(idx, rr):
+                    r_all[i] = r
+        y, summary, frames, roots = y_all, s_all, f_all, r_all
     out = (y, summary[:, 0].astype(int), summary[:, 1].astype(int), summary[:, 2].astype(int), summary[:, 3])
-    return out + (summary[:, 4].astype(int), frames) if sampled else out
+    if sampled:
+        out = out + (summary[:, 4].astype(int), frames)
+    return out + (roots,) if events else out
