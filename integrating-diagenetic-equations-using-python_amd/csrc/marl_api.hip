@@ -988,38 +988,6 @@ static int dense_eval(marl_ctx* ctx, int layout, bool small, const Rk45Ctrl& c, 
     return 0;
 }
 
-// Brent's method for monitor `e` on the last accepted step (solve_event_equation, ivp.py:51-76)
-static int brent_event(marl_ctx* ctx, int layout, bool small, const Rk45Ctrl& c, int e, double ga, double gb, double* root)
-{
-    const double xtol = 4 * 2.220446049250313e-16, rtol = xtol;
-    double a = c.t_old, b = c.t, fa = ga, fb = gb, g[7];
-    if (fa == 0) { *root = a; return 0; }
-    if (fb == 0) { *root = b; return 0; }
-    double xpre = a, xcur = b, fpre = fa, fcur = fb, xblk = 0, fblk = 0, spre = 0, scur = 0;
-    for (int it = 0; it < 100; it++) {
-        if (fpre != 0 && fcur != 0 && ((fpre < 0) != (fcur < 0))) { xblk = xpre; fblk = fpre; spre = scur = xcur - xpre; }
-        if (std::fabs(fblk) < std::fabs(fcur)) { xpre = xcur; xcur = xblk; xblk = xpre; fpre = fcur; fcur = fblk; fblk = fpre; }
-        const double delta = (xtol + rtol * std::fabs(xcur)) / 2, sbis = (xblk - xcur) / 2;
-        if (fcur == 0 || std::fabs(sbis) < delta) break;
-        if (std::fabs(spre) > delta && std::fabs(fcur) < std::fabs(fpre)) {
-            double stry;
-            if (xpre == xblk) stry = -fcur * (xcur - xpre) / (fcur - fpre);
-            else {
-                const double dpre = (fpre - fcur) / (xpre - xcur), dblk = (fblk - fcur) / (xblk - xcur);
-                stry = -fcur * (fblk * dblk - fpre * dpre) / (dblk * dpre * (fblk - fpre));
-            }
-            if (2 * std::fabs(stry) < std::fmin(std::fabs(spre), 3 * std::fabs(sbis) - delta)) { spre = scur; scur = stry; }
-            else { spre = sbis; scur = sbis; }
-        } else { spre = sbis; scur = sbis; }
-        xpre = xcur; fpre = fcur;
-        if (std::fabs(scur) > delta) xcur += scur; else xcur += (sbis > 0 ? delta : -delta);
-        if (int rc = dense_eval(ctx, layout, small, c, xcur, nullptr, g)) return rc;
-        fcur = g[e];
-    }
-    *root = xcur;
-    return 0;
-}
-
 static void ctrl_to_stats(const Rk45Ctrl& c, marl_stats* st)
 {
     memset(st, 0, sizeof *st);
@@ -1043,6 +1011,20 @@ static int64_t attempts_per_batch(int64_t poll, int64_t max_attempts, int64_t ex
     return left < 1 ? 1 : (left < poll ? left : poll);
 }
 
+// What every single run checks of its span, first step, tolerances and sample times before it starts; `name`: the solver, in front
+// of the message.
+static int check_ivp_args(marl_ctx* ctx, const char* name, double t0, double t1, double first_step, double rtol, double atol,
+                          const double* t_eval, int64_t n_eval)
+{
+    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "%s: need first_step > 0 and t1 >= t0 (forward integration)", name);
+    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "%s: `first_step` exceeds bounds", name);  // common.py:10-16
+    if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "%s: tolerances must be positive", name);
+    for (int64_t i = 0; i < n_eval; i++)
+        if (t_eval[i] < t0 || t_eval[i] > t1 || (i > 0 && t_eval[i] <= t_eval[i - 1]))
+            return fail(ctx, -1, "%s: `t_eval` must be sorted and within t_span", name);  // ivp.py:603-609
+    return 0;
+}
+
 // The adaptive loop on device buffers buf[0..3] (`layout`), state already in buf[0].
 // small = true: the grid fits one workgroup -> the persistent sweep kernel runs all attempts on-chip
 // (state in buf[0], FIELD-MAJOR; (y_old, f_old) of a paused step in buf[1], buf[3]).
@@ -1050,13 +1032,8 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
                     const double* t_eval, int64_t n_eval, double* y_eval_dev, double* t_events, int64_t max_events,
                     int64_t max_attempts, marl_stats* stats)
 {
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");  // common.py:10-16
-    if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "rk45: tolerances must be positive");
+    if (int rc = check_ivp_args(ctx, "rk45", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
     rtol = clamp_rtol(rtol);
-    for (int64_t i = 0; i < n_eval; i++)
-        if (t_eval[i] < t0 || t_eval[i] > t1 || (i > 0 && t_eval[i] <= t_eval[i - 1]))
-            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
     const int blk = small ? sweep_block(ctx) : 0;
     const int64_t nb = rk45_blocks(ctx);
     if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(nb + kReduceGroups, 1024))) return rc;
@@ -1117,7 +1094,13 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
                     double ga[7];
                     if (int rc = dense_eval(ctx, layout, small, hc, hc.t_old, nullptr, ga)) return rc;
                     double root = hc.ev_last[e];
-                    if (int rc = brent_event(ctx, layout, small, hc, e, ga[e], hc.g[e], &root)) return rc;
+                    auto monitor_at = [&](double tq, double* v) -> int {   // monitor e on the step's dense output (solve_event_equation, ivp.py:51-76)
+                        double gq[7];
+                        if (int rc = dense_eval(ctx, layout, small, hc, tq, nullptr, gq)) return rc;
+                        *v = gq[e];
+                        return 0;
+                    };
+                    if (int rc = brent_root(monitor_at, hc.t_old, ga[e], hc.t, hc.g[e], &root)) return rc;
                     for (int64_t k = seen_events[e]; k < hc.n_events[e]; k++)
                         if (k < max_events) t_events[e * max_events + k] = root;
                     seen_events[e] = hc.n_events[e];
@@ -1149,6 +1132,77 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
         HIP_OK(ctx, hipMemcpyAsync(ctx->buf[2], ctx->buf[3], sizeof(double) * sd, hipMemcpyDeviceToDevice, ctx->stream));
     }
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// A device buffer of *cap doubles to at least n (the contents are not kept; the stream is idle before the old one is freed)
+static int grow_dev(marl_ctx* ctx, double** buf, size_t* cap, size_t n)
+{
+    if (*cap >= n) return 0;
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    if (*buf) HIP_OK(ctx, hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    HIP_OK(ctx, hipMalloc((void**)buf, sizeof(double) * n));
+    *cap = n;
+    return 0;
+}
+
+// The RK45 sweep behind marl_sweep_rk45_dev / _eval_dev / _events_dev (`entry`: the one the caller used).  Neither samples (n_eval == 0)
+// nor roots (no t_events or max_events <= 0): rk45_sweep_kernel; samples only: rk45_sweep_eval_kernel; roots, with samples or
+// without: rk45_sweep_roots_kernel.
+static int sweep_rk45(const char* entry, marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                      int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, double* t_events,
+                      int64_t max_events, marl_stats* stats)
+{
+    if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
+        return ctx ? fail(ctx, -1, "%s: invalid argument", entry) : -1;
+    const bool frames = n_eval > 0, roots = t_events && max_events > 0;
+    if (!frames && !roots && n_done) memset(n_done, 0, sizeof(int64_t) * ctx->batch);   // nothing to sample: the plain sweep itself
+    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
+    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
+    for (int64_t i = 0; i < n_eval; i++)
+        if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
+            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    const int blk = sweep_block(ctx);
+    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
+    const size_t n_tev = roots ? (size_t)ctx->batch * 7 * (size_t)max_events : 0;
+    if (frames)
+        if (int rc = grow_dev(ctx, &ctx->sw_teval, &ctx->sw_teval_cap, (size_t)n_eval)) return rc;
+    if ((frames || roots) && !ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
+    if (roots) {
+        if (int rc = grow_dev(ctx, &ctx->sw_tev, &ctx->sw_tev_cap, n_tev)) return rc;
+        HIP_OK(ctx, hipMemsetAsync(ctx->sw_tev, 0xff, sizeof(double) * n_tev, ctx->stream));   // NaN beyond the roots found (all bits set is a quiet NaN)
+    }
+    // (pageable host memory: the copy has left the caller's array when the call returns)
+    if (frames) HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, t_eval, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
+    if (frames || roots) HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
+    if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
+    hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
+                       atol, (int64_t)NF * ctx->N, max_attempts, 0);
+    LAUNCH_OK(ctx);
+    const dim3 grid((unsigned)ctx->batch);
+    if (roots) {
+        SWEEP_DISPATCH(rk45_sweep_roots_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone,
+                       ctx->sw_tev, max_events)
+    } else if (frames) {
+        SWEEP_DISPATCH(rk45_sweep_eval_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone)
+    } else {
+        SWEEP_DISPATCH(rk45_sweep_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (double*)nullptr, (double*)nullptr)
+    }
+    LAUNCH_OK(ctx);
+    HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
+    if ((frames || roots) && n_done) HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
+    if (roots) HIP_OK(ctx, hipMemcpyAsync(t_events, ctx->sw_tev, sizeof(double) * n_tev, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
+    if (t1 == t0 && frames && t_eval[0] == t0) {   // no step is taken (base.py:189-194), so no roots; the sample at t0 is y0, as rk45_run gives it to single runs
+        const size_t row = sizeof(double) * NF * ctx->N;
+        HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * n_eval, y_dev, row, row, (size_t)ctx->batch, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t b = 0; b < ctx->batch; b++) n_done[b] = 1;
+    }
     return 0;
 }
 
@@ -1269,132 +1323,23 @@ int marl_integrate_rk4(marl_ctx* ctx, double* y, double dt, int64_t nsteps)
 int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                         int64_t max_attempts, marl_stats* stats)
 {
-    if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_rk45_dev: invalid argument") : -1;
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
-    HIP_OK(ctx, hipSetDevice(ctx->device));
-    const int blk = sweep_block(ctx);
-    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
-    if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
-    hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
-                       atol, (int64_t)NF * ctx->N, max_attempts, 0);
-    LAUNCH_OK(ctx);
-    const dim3 grid((unsigned)ctx->batch);
-    SWEEP_DISPATCH(rk45_sweep_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (double*)nullptr, (double*)nullptr)
-    LAUNCH_OK(ctx);
-    HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
-    return 0;
+    return sweep_rk45("marl_sweep_rk45_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
 }
 
 int marl_sweep_rk45_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                              int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
                              marl_stats* stats)
 {
-    if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
-        return ctx ? fail(ctx, -1, "marl_sweep_rk45_eval_dev: invalid argument") : -1;
-    if (n_eval == 0) {   // nothing to sample: the plain sweep itself
-        if (n_done) memset(n_done, 0, sizeof(int64_t) * ctx->batch);
-        return marl_sweep_rk45_dev(ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, stats);
-    }
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
-    for (int64_t i = 0; i < n_eval; i++)
-        if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
-            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
-    HIP_OK(ctx, hipSetDevice(ctx->device));
-    const int blk = sweep_block(ctx);
-    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
-    if (ctx->sw_teval_cap < (size_t)n_eval) {
-        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->sw_teval) HIP_OK(ctx, hipFree(ctx->sw_teval));
-        ctx->sw_teval = nullptr;
-        ctx->sw_teval_cap = 0;
-        HIP_OK(ctx, hipMalloc((void**)&ctx->sw_teval, sizeof(double) * n_eval));
-        ctx->sw_teval_cap = (size_t)n_eval;
-    }
-    if (!ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
-    // (pageable host memory: the copy has left the caller's array when the call returns)
-    HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, t_eval, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
-    HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
-    if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
-    hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
-                       atol, (int64_t)NF * ctx->N, max_attempts, 0);
-    LAUNCH_OK(ctx);
-    const dim3 grid((unsigned)ctx->batch);
-    SWEEP_DISPATCH(rk45_sweep_eval_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone)
-    LAUNCH_OK(ctx);
-    HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
-    if (t1 == t0 && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as rk45_run gives it to single runs
-        const size_t row = sizeof(double) * NF * ctx->N;
-        HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * n_eval, y_dev, row, row, (size_t)ctx->batch, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-        for (int64_t b = 0; b < ctx->batch; b++) n_done[b] = 1;
-    }
-    return 0;
+    return sweep_rk45("marl_sweep_rk45_eval_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                      nullptr, 0, stats);
 }
 
 int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
                                double* t_events, int64_t max_events, marl_stats* stats)
 {
-    if (!t_events || max_events <= 0)   // no roots asked for: the sweep with t_eval itself
-        return marl_sweep_rk45_eval_dev(ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done, stats);
-    if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
-        return ctx ? fail(ctx, -1, "marl_sweep_rk45_events_dev: invalid argument") : -1;
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
-    for (int64_t i = 0; i < n_eval; i++)
-        if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
-            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
-    HIP_OK(ctx, hipSetDevice(ctx->device));
-    const int blk = sweep_block(ctx);
-    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
-    if (n_eval > 0 && ctx->sw_teval_cap < (size_t)n_eval) {
-        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->sw_teval) HIP_OK(ctx, hipFree(ctx->sw_teval));
-        ctx->sw_teval = nullptr;
-        ctx->sw_teval_cap = 0;
-        HIP_OK(ctx, hipMalloc((void**)&ctx->sw_teval, sizeof(double) * n_eval));
-        ctx->sw_teval_cap = (size_t)n_eval;
-    }
-    if (!ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
-    const size_t n_tev = (size_t)ctx->batch * 7 * (size_t)max_events;
-    if (ctx->sw_tev_cap < n_tev) {
-        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->sw_tev) HIP_OK(ctx, hipFree(ctx->sw_tev));
-        ctx->sw_tev = nullptr;
-        ctx->sw_tev_cap = 0;
-        HIP_OK(ctx, hipMalloc((void**)&ctx->sw_tev, sizeof(double) * n_tev));
-        ctx->sw_tev_cap = n_tev;
-    }
-    HIP_OK(ctx, hipMemsetAsync(ctx->sw_tev, 0xff, sizeof(double) * n_tev, ctx->stream));   // NaN beyond the roots found (all bits set is a quiet NaN)
-    if (n_eval > 0) HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, t_eval, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
-    HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
-    if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
-    hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
-                       atol, (int64_t)NF * ctx->N, max_attempts, 0);
-    LAUNCH_OK(ctx);
-    const dim3 grid((unsigned)ctx->batch);
-    SWEEP_DISPATCH(rk45_sweep_roots_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone,
-                   ctx->sw_tev, max_events)
-    LAUNCH_OK(ctx);
-    HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_done) HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(ctx, hipMemcpyAsync(t_events, ctx->sw_tev, sizeof(double) * n_tev, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t b = 0; b < ctx->batch; b++) ctrl_to_stats(ctx->hctrl[b], &stats[b]);
-    if (t1 == t0 && n_eval > 0 && t_eval[0] == t0) {   // no step is taken (base.py:189-194), so no roots; the sample at t0 is y0, as in the eval entry
-        const size_t row = sizeof(double) * NF * ctx->N;
-        HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * n_eval, y_dev, row, row, (size_t)ctx->batch, hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-        for (int64_t b = 0; b < ctx->batch; b++) n_done[b] = 1;
-    }
-    return 0;
+    return sweep_rk45("marl_sweep_rk45_events_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                      t_events, max_events, stats);
 }
 
 int marl_integrate_rk45_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
@@ -2167,6 +2112,45 @@ int radau_monitors(marl_ctx* ctx, const double* y, double g[7])
     return 0;
 }
 
+// The tail of an accepted step in the solve_ivp loop of the implicit single runs: events (ivp.py:673-694), their roots by Brent's
+// method on the step's dense output (solve_event_equation, ivp.py:51-76), and the t_eval samples (ivp.py:706-723).  g: the monitors at
+// t_old, on return g_new, those at t; dense(tq, out): the state of the step's dense output at tq -> out (device).
+template <class Dense>
+int accepted_step_epilogue(marl_ctx* ctx, RadauWork& w, double g[7], const double g_new[7], double t_old, double t, Dense&& dense,
+                           const double* t_eval, int64_t n_eval, int64_t& eval_i, double* y_eval_host, double* t_events, int64_t max_events,
+                           marl_stats* st)
+{
+    const int64_t n = NF * ctx->N;
+    for (int e = 0; e < 7; e++) {
+        const bool up = g[e] <= 0 && g_new[e] >= 0, down = g[e] >= 0 && g_new[e] <= 0;
+        if (up || down) {
+            if (t_events && st->n_events[e] < max_events) {
+                auto monitor_at = [&](double tq, double* v) -> int {
+                    double gq[7];
+                    if (int rc = dense(tq, w.tmp)) return rc;
+                    if (int rc = radau_monitors(ctx, w.tmp, gq)) return rc;
+                    *v = gq[e];
+                    return 0;
+                };
+                double fa, fb, root;
+                if (int rc = monitor_at(t_old, &fa)) return rc;
+                if (int rc = monitor_at(t, &fb)) return rc;
+                if (int rc = brent_root(monitor_at, t_old, fa, t, fb, &root)) return rc;
+                t_events[e * max_events + st->n_events[e]] = root;
+            }
+            st->n_events[e]++;
+        }
+        g[e] = g_new[e];
+    }
+    while (t_eval && eval_i < n_eval && t_eval[eval_i] <= t) {
+        if (int rc = dense(t_eval[eval_i], w.tmp)) return rc;
+        HIP_OK(ctx, hipMemcpyAsync(y_eval_host + eval_i * n, w.tmp, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        eval_i++;
+    }
+    return 0;
+}
+
 struct RadauDense { double t_old, h; };
 
 // state of the dense output at time t -> out (device)
@@ -2176,46 +2160,6 @@ int radau_dense(marl_ctx* ctx, RadauWork& w, const RadauDense& d, double t, doub
     const int64_t n = NF * ctx->N;
     hipLaunchKernelGGL(radau::dense_eval_kernel, dim3(blocks256(n)), dim3(256), 0, ctx->stream, w.Q, w.yold, (const double*)nullptr, n, X, 1, out);
     LAUNCH_OK(ctx);
-    return 0;
-}
-
-// Brent's method for monitor e on [a, b] (solve_event_equation, ivp.py:51-76 -> scipy.optimize.brentq, xtol = rtol = 4 eps)
-int radau_brent(marl_ctx* ctx, RadauWork& w, const RadauDense& d, int e, double a, double b, double* root)
-{
-    const double xtol = 4 * 2.220446049250313e-16, rtol = xtol;
-    double g[7];
-    auto at = [&](double t, double* v) -> int {
-        if (int rc = radau_dense(ctx, w, d, t, w.tmp)) return rc;
-        if (int rc = radau_monitors(ctx, w.tmp, g)) return rc;
-        *v = g[e];
-        return 0;
-    };
-    double fa, fb;
-    if (int rc = at(a, &fa)) return rc;
-    if (int rc = at(b, &fb)) return rc;
-    if (fa == 0) { *root = a; return 0; }
-    if (fb == 0) { *root = b; return 0; }
-    double xpre = a, xcur = b, fpre = fa, fcur = fb, xblk = 0, fblk = 0, spre = 0, scur = 0;
-    for (int it = 0; it < 100; it++) {
-        if (fpre != 0 && fcur != 0 && ((fpre < 0) != (fcur < 0))) { xblk = xpre; fblk = fpre; spre = scur = xcur - xpre; }
-        if (std::fabs(fblk) < std::fabs(fcur)) { xpre = xcur; xcur = xblk; xblk = xpre; fpre = fcur; fcur = fblk; fblk = fpre; }
-        const double delta = (xtol + rtol * std::fabs(xcur)) / 2, sbis = (xblk - xcur) / 2;
-        if (fcur == 0 || std::fabs(sbis) < delta) break;
-        if (std::fabs(spre) > delta && std::fabs(fcur) < std::fabs(fpre)) {
-            double stry;
-            if (xpre == xblk) stry = -fcur * (xcur - xpre) / (fcur - fpre);
-            else {
-                const double dpre = (fpre - fcur) / (xpre - xcur), dblk = (fblk - fcur) / (xblk - xcur);
-                stry = -fcur * (fblk * dblk - fpre * dpre) / (dblk * dpre * (fblk - fpre));
-            }
-            if (2 * std::fabs(stry) < std::fmin(std::fabs(spre), 3 * std::fabs(sbis) - delta)) { spre = scur; scur = stry; }
-            else { spre = sbis; scur = sbis; }
-        } else { spre = sbis; scur = sbis; }
-        xpre = xcur; fpre = fcur;
-        if (std::fabs(scur) > delta) xcur += scur; else xcur += (sbis > 0 ? delta : -delta);
-        if (int rc = at(xcur, &fcur)) return rc;
-    }
-    *root = xcur;
     return 0;
 }
 
@@ -2449,24 +2393,9 @@ int radau_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_st
             if (int rc = radau_read(ctx, w, &marker, nullptr)) return rc;
             for (int e = 0; e < 7; e++) g_new[e] = const_cast<const volatile double*>(ctx->zc_h)[16 + e];
         } else if (int rc = radau_monitors(ctx, w.y, g_new)) return rc;
-        for (int e = 0; e < 7; e++) {
-            const bool up = g[e] <= 0 && g_new[e] >= 0, down = g[e] >= 0 && g_new[e] <= 0;
-            if (up || down) {
-                if (t_events && st->n_events[e] < max_events) {
-                    double root;
-                    if (int rc = radau_brent(ctx, w, dense, e, t_old, t, &root)) return rc;
-                    t_events[e * max_events + st->n_events[e]] = root;
-                }
-                st->n_events[e]++;
-            }
-            g[e] = g_new[e];
-        }
-        while (t_eval && eval_i < n_eval && t_eval[eval_i] <= t) {
-            if (int rc = radau_dense(ctx, w, dense, t_eval[eval_i], w.tmp)) return rc;
-            HIP_OK(ctx, hipMemcpyAsync(y_eval_host + eval_i * n, w.tmp, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-            eval_i++;
-        }
+        auto dense_at = [&](double tq, double* out) { return radau_dense(ctx, w, dense, tq, out); };
+        if (int rc = accepted_step_epilogue(ctx, w, g, g_new, t_old, t, dense_at, t_eval, n_eval, eval_i, y_eval_host, t_events, max_events, st))
+            return rc;
     }
     st->status = status;
     st->t = t;
@@ -2530,46 +2459,6 @@ int bdf_dense(marl_ctx* ctx, const BdfDense& d, double tq, double* out)
     const int64_t n = NF * ctx->N;
     hipLaunchKernelGGL(bdf::dense_kernel, dim3(blocks256(n)), dim3(256), 0, ctx->stream, d.D, n, d.order, p, out);
     LAUNCH_OK(ctx);
-    return 0;
-}
-
-// Brent on monitor e over the BDF dense output (as radau_brent)
-int bdf_brent(marl_ctx* ctx, RadauWork& w, const BdfDense& d, int e, double a, double b, double* root)
-{
-    const double xtol = 4 * 2.220446049250313e-16, rtol = xtol;
-    double g[7];
-    auto at = [&](double t, double* v) -> int {
-        if (int rc = bdf_dense(ctx, d, t, w.tmp)) return rc;
-        if (int rc = radau_monitors(ctx, w.tmp, g)) return rc;
-        *v = g[e];
-        return 0;
-    };
-    double fa, fb;
-    if (int rc = at(a, &fa)) return rc;
-    if (int rc = at(b, &fb)) return rc;
-    if (fa == 0) { *root = a; return 0; }
-    if (fb == 0) { *root = b; return 0; }
-    double xpre = a, xcur = b, fpre = fa, fcur = fb, xblk = 0, fblk = 0, spre = 0, scur = 0;
-    for (int it = 0; it < 100; it++) {
-        if (fpre != 0 && fcur != 0 && ((fpre < 0) != (fcur < 0))) { xblk = xpre; fblk = fpre; spre = scur = xcur - xpre; }
-        if (std::fabs(fblk) < std::fabs(fcur)) { xpre = xcur; xcur = xblk; xblk = xpre; fpre = fcur; fcur = fblk; fblk = fpre; }
-        const double delta = (xtol + rtol * std::fabs(xcur)) / 2, sbis = (xblk - xcur) / 2;
-        if (fcur == 0 || std::fabs(sbis) < delta) break;
-        if (std::fabs(spre) > delta && std::fabs(fcur) < std::fabs(fpre)) {
-            double stry;
-            if (xpre == xblk) stry = -fcur * (xcur - xpre) / (fcur - fpre);
-            else {
-                const double dpre = (fpre - fcur) / (xpre - xcur), dblk = (fblk - fcur) / (xblk - xcur);
-                stry = -fcur * (fblk * dblk - fpre * dpre) / (dblk * dpre * (fblk - fpre));
-            }
-            if (2 * std::fabs(stry) < std::fmin(std::fabs(spre), 3 * std::fabs(sbis) - delta)) { spre = scur; scur = stry; }
-            else { spre = sbis; scur = sbis; }
-        } else { spre = sbis; scur = sbis; }
-        xpre = xcur; fpre = fcur;
-        if (std::fabs(scur) > delta) xcur += scur; else xcur += (sbis > 0 ? delta : -delta);
-        if (int rc = at(xcur, &fcur)) return rc;
-    }
-    *root = xcur;
     return 0;
 }
 
@@ -2809,24 +2698,9 @@ int bdf_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_step
             for (int e = 0; e < 7; e++) g_new[e] = g_spec[e];
         } else if (int rc = radau_monitors(ctx, w.y, g_new)) return rc;
         have_g_spec = false;
-        for (int e = 0; e < 7; e++) {
-            const bool up = g[e] <= 0 && g_new[e] >= 0, down = g[e] >= 0 && g_new[e] <= 0;
-            if (up || down) {
-                if (t_events && st->n_events[e] < max_events) {
-                    double root;
-                    if (int rc = bdf_brent(ctx, w, dense, e, t_old, t, &root)) return rc;
-                    t_events[e * max_events + st->n_events[e]] = root;
-                }
-                st->n_events[e]++;
-            }
-            g[e] = g_new[e];
-        }
-        while (t_eval && eval_i < n_eval && t_eval[eval_i] <= t) {
-            if (int rc = bdf_dense(ctx, dense, t_eval[eval_i], w.tmp)) return rc;
-            HIP_OK(ctx, hipMemcpyAsync(y_eval_host + eval_i * n, w.tmp, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-            eval_i++;
-        }
+        auto dense_at = [&](double tq, double* out) { return bdf_dense(ctx, dense, tq, out); };
+        if (int rc = accepted_step_epilogue(ctx, w, g, g_new, t_old, t, dense_at, t_eval, n_eval, eval_i, y_eval_host, t_events, max_events, st))
+            return rc;
     }
     st->status = status;
     st->t = t;
@@ -2836,50 +2710,39 @@ int bdf_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_step
 }
 }  // namespace
 
-extern "C" int marl_integrate_radau(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
-                                    const int32_t* groups, const double* t_eval, int64_t n_eval, double* y_eval, double* t_events,
-                                    int64_t max_events, int64_t max_attempts, marl_stats* stats)
+// marl_integrate_radau / marl_integrate_bdf: `entry` and `solver` in front of the messages, `run` = radau_run or bdf_run
+static int integrate_implicit(const char* entry, const char* solver, decltype(radau_run)* run, marl_ctx* ctx, double* y, double t0, double t1,
+                              double first_step, double rtol, double atol, const int32_t* groups, const double* t_eval, int64_t n_eval,
+                              double* y_eval, double* t_events, int64_t max_events, int64_t max_attempts, marl_stats* stats)
 {
-    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_radau: invalid argument") : -1;
-    if (ctx->batch != 1 || ctx->halo > 0) return fail(ctx, -1, "marl_integrate_radau: single-instance, whole-grid context required");
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "radau: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "radau: `first_step` exceeds bounds");   // common.py:10-16
-    if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "radau: tolerances must be positive");
-    for (int64_t i = 0; i < n_eval; i++)
-        if (t_eval[i] < t0 || t_eval[i] > t1 || (i > 0 && t_eval[i] <= t_eval[i - 1]))
-            return fail(ctx, -1, "radau: `t_eval` must be sorted and within t_span");
+    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "%s: invalid argument", entry) : -1;
+    if (ctx->batch != 1 || ctx->halo > 0) return fail(ctx, -1, "%s: single-instance, whole-grid context required", entry);
+    if (int rc = check_ivp_args(ctx, solver, t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
     HIP_OK(ctx, hipSetDevice(ctx->device));
     RadauWork w;
     if (int rc = radau_alloc(ctx, w, groups)) return rc;
     const size_t n = (size_t)NF * ctx->N;
     HIP_OK(ctx, hipMemcpyAsync(w.y, y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = radau_run(ctx, w, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats)) return rc;
+    if (int rc = run(ctx, w, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(y, w.y, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+extern "C" int marl_integrate_radau(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                                    const int32_t* groups, const double* t_eval, int64_t n_eval, double* y_eval, double* t_events,
+                                    int64_t max_events, int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_implicit("marl_integrate_radau", "radau", radau_run, ctx, y, t0, t1, first_step, rtol, atol, groups, t_eval, n_eval, y_eval,
+                              t_events, max_events, max_attempts, stats);
 }
 
 extern "C" int marl_integrate_bdf(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
                                   const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events, int64_t max_attempts,
                                   marl_stats* stats)
 {
-    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_bdf: invalid argument") : -1;
-    if (ctx->batch != 1 || ctx->halo > 0) return fail(ctx, -1, "marl_integrate_bdf: single-instance, whole-grid context required");
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "bdf: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "bdf: `first_step` exceeds bounds");   // common.py:10-16
-    if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "bdf: tolerances must be positive");
-    for (int64_t i = 0; i < n_eval; i++)
-        if (t_eval[i] < t0 || t_eval[i] > t1 || (i > 0 && t_eval[i] <= t_eval[i - 1]))
-            return fail(ctx, -1, "bdf: `t_eval` must be sorted and within t_span");
-    HIP_OK(ctx, hipSetDevice(ctx->device));
-    RadauWork w;
-    if (int rc = radau_alloc(ctx, w, groups)) return rc;
-    const size_t n = (size_t)NF * ctx->N;
-    HIP_OK(ctx, hipMemcpyAsync(w.y, y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = bdf_run(ctx, w, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats)) return rc;
-    HIP_OK(ctx, hipMemcpyAsync(y, w.y, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return integrate_implicit("marl_integrate_bdf", "bdf", bdf_run, ctx, y, t0, t1, first_step, rtol, atol, groups, t_eval, n_eval, y_eval,
+                              t_events, max_events, max_attempts, stats);
 }
 
 // ---- a sweep of Radau instances (marl_radau_batch.h) -------------------------------------------------------------------------

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "marl_math.h"
+#include "marl_brent.h"
 
 namespace marl {
 
@@ -1016,34 +1017,6 @@ __device__ __forceinline__ double rk45_monitor_of_record(const double* rec, int 
 __device__ __forceinline__ int rk45_monitor_slot(int e)
 {
     return (e < 3) ? e + 1 : (e == 3 ? 5 : (e == 4 ? 6 : (e == 5 ? 4 : 7)));
-}
-
-// One pass of Brent's method (scipy.optimize.brentq as solve_event_equation calls it, ivp.py:51-76: xtol = rtol = 4 eps, at most 100
-// iterations) from the top of its loop to the next function evaluation.  Returns true when the root is final (c.xcur); false: evaluate
-// at c.xcur.  BS: any structure with the fields below - the Radau sweeps' controller (RadauCtl), the RK45 sweep's BrentState.
-struct BrentState { double xpre, xcur, xblk, fpre, fcur, fblk, spre, scur; };
-template <class BS>
-__device__ __forceinline__ bool brent_advance(BS& c)
-{
-    const double xtol = 4 * 2.220446049250313e-16, rtol = xtol;
-    if (c.fpre != 0 && c.fcur != 0 && ((c.fpre < 0) != (c.fcur < 0))) { c.xblk = c.xpre; c.fblk = c.fpre; c.spre = c.scur = c.xcur - c.xpre; }
-    if (fabs(c.fblk) < fabs(c.fcur)) { c.xpre = c.xcur; c.xcur = c.xblk; c.xblk = c.xpre; c.fpre = c.fcur; c.fcur = c.fblk; c.fblk = c.fpre; }
-    const double delta = (xtol + rtol * fabs(c.xcur)) / 2, sbis = (c.xblk - c.xcur) / 2;
-    if (c.fcur == 0 || fabs(sbis) < delta) return true;
-    if (fabs(c.spre) > delta && fabs(c.fcur) < fabs(c.fpre)) {
-        double stry;
-        if (c.xpre == c.xblk) stry = -c.fcur * (c.xcur - c.xpre) / (c.fcur - c.fpre);
-        else {
-            const double dpre = (c.fpre - c.fcur) / (c.xpre - c.xcur), dblk = (c.fblk - c.fcur) / (c.xblk - c.xcur);
-            stry = -c.fcur * (c.fblk * dblk - c.fpre * dpre) / (dblk * dpre * (c.fblk - c.fpre));
-        }
-        const double lim = fmin(fabs(c.spre), 3 * fabs(sbis) - delta);
-        if (2 * fabs(stry) < lim) { c.spre = c.scur; c.scur = stry; }
-        else { c.spre = sbis; c.scur = sbis; }
-    } else { c.spre = sbis; c.scur = sbis; }
-    c.xpre = c.xcur; c.fpre = c.fcur;
-    if (fabs(c.scur) > delta) c.xcur += c.scur; else c.xcur += (sbis > 0 ? delta : -delta);
-    return false;
 }
 
 __device__ __forceinline__ int rk45_events(Rk45Ctrl& c, const double (&rec)[NQ])

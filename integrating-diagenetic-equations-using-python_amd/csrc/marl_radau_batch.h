@@ -34,7 +34,7 @@ __device__ __forceinline__ double predict_factor(double h_abs, double h_abs_old,
 enum : int { L_RHS1 = 0, L_ACCEPT, L_JAC, L_LU, L_NEWTON, L_ERR, L_RUNNING, L_DENSE, L_COUNT };
 
 // One instance's step logic from where it stopped to its next action (c.action, c.pc).  g_now: the seven monitors of the instance's y.
-// (Brent's method: brent_advance, marl_kernels.h - shared with the RK45 sweep that locates roots, on RadauCtl's own fields here.)
+// (Brent's method: brent_advance, marl_brent.h - shared with the RK45 sweep that locates roots, on RadauCtl's own fields here.)
 // g_dense: the seven monitors of the dense-output state the last A_DENSE action evaluated (event root finding); t_events: this
 // instance's root times [7][max_events] (NULL: sign changes are only counted).
 __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g_now)[7], int64_t n, const double* g_dense = nullptr, double* t_events = nullptr)
