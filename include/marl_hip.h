@@ -205,6 +205,20 @@ int marl_sweep_radau_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, dou
  * monitor e of instance b is valid for k < stats[b].n_events[e], the rest is NaN; sign changes beyond max_events are counted only. */
 int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                 const int32_t* groups, int64_t max_attempts, double* t_events, int64_t max_events, marl_stats* stats);
+/* The same sweep with t_eval: what the reference keeps of every run is the time series that solve_ivp(..., t_eval=) fills with its
+ * default solver (marlpde/parameters.py:213; marlpde/Evolve_scenario.py:104-109), next to the root times (:118-145, 175-177).  As in
+ * scipy the samples never change the steps (ivp.py:706-723): after every accepted step, once its roots are located, the instance's
+ * controller asks for the samples inside the step one by one and the step's dense output (radau.py:557-572) is written into the
+ * frame - no function evaluation is counted; state, statistics and root times are those of the same call without samples.
+ * t_eval: host, n_eval times shared by all instances, strictly increasing within [t0, t1].
+ * y_eval_dev: device, [n_instances][n_eval][5N], each frame contiguous and field-major.  n_done: host, n_instances entries: the frames
+ * written for that instance (the samples with t_eval[k] <= the time it reached); its later frames are not touched.
+ * t_events, max_events: as for marl_sweep_radau_events_dev; may be NULL / 0 (sign changes are then only counted).
+ * n_eval = 0 (t_eval, y_eval_dev, n_done may then be NULL) is marl_sweep_radau_events_dev, or marl_sweep_radau_dev without t_events.
+ * t1 == t0: no step is taken; a sample at t0 receives y0.  Synchronises. */
+int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                              const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                              int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
 /* ---- 1-D domain decomposition of ONE large grid (BASELINE config 5; the reference never decomposes the depth
  * axis).  One process per GPU holds a slab [g_begin, g_end) of the N_global cells in a slab context; the host

@@ -416,16 +416,36 @@ class LMAHeureuxPorosityDiff:
         self._check(rc, "marl_integrate_rk45_dev")
         return RK45Result(stats)
 
-    def sweep_radau_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None, events=False, max_events=64):
+    def sweep_radau_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None, events=False, max_events=64,
+                           t_eval=None, y_eval_dev_ptr=None):
         """Every instance of the model integrated with the reference's default solver (scipy Radau semantics), all instances
         advanced together on the device (marl_sweep_radau_dev); device states [instances][5N] in place.  Returns one
         :class:`RK45Result` per instance (statistics).  ``events=True``: the monitors' root times are located inside the sweep
         (marl_sweep_radau_events_dev) and returned as ``t_events`` - a list of 7 arrays per instance, what the reference prints and
-        stores for every run (Evolve_scenario.py:118-145, 175-177); otherwise sign changes are only counted."""
+        stores for every run (Evolve_scenario.py:118-145, 175-177); otherwise sign changes are only counted.
+
+        With ``t_eval`` (sorted sample times within ``t_span``, shared by all instances) the sweep also writes the time series that
+        ``solve_ivp(..., t_eval=)`` returns (marl_sweep_radau_eval_dev), as :meth:`sweep_rk45_device` does: ``y_eval_dev_ptr`` is device
+        memory [instances][len(t_eval)][5N]; each result carries ``t = t_eval[:n_frames]``, the frames stay on the device, and frames
+        beyond ``n_frames`` are not written.  Combinable with ``events``."""
         grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
         stats = (MarlStats * self.n_instances)()
         args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
                 _as_ptr(grp) if grp is not None else None, int(max_attempts))
+        if t_eval is not None:
+            te = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
+            if te.size and not y_eval_dev_ptr:
+                raise ValueError("sweep_radau_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
+            n_done = np.zeros(self.n_instances, dtype=np.int64)
+            locate = bool(events) and int(max_events) > 0
+            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan) if locate else None
+            rc = self._lib.marl_sweep_radau_eval_dev(*args, _as_ptr(te) if te.size else None, te.size,
+                                                     C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
+                                                     _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
+            self._check(rc, "marl_sweep_radau_eval_dev")
+            return [RK45Result(s, t=te[:int(k)].copy(),
+                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
+                    for b, (s, k) in enumerate(zip(stats, n_done))]
         if not events:
             self._check(self._lib.marl_sweep_radau_dev(*args, stats), "marl_sweep_radau_dev")
             return [RK45Result(s) for s in stats]

@@ -2746,29 +2746,29 @@ extern "C" int marl_integrate_bdf(marl_ctx* ctx, double* y, double t0, double t1
 }
 
 // ---- a sweep of Radau instances (marl_radau_batch.h) -------------------------------------------------------------------------
-extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
-                                           const int32_t* groups, int64_t max_attempts, double* t_events, int64_t max_events, marl_stats* stats);
-
-extern "C" int marl_sweep_radau_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
-                                    const int32_t* groups, int64_t max_attempts, marl_stats* stats)
-{
-    return marl_sweep_radau_events_dev(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, nullptr, 0, stats);
-}
-
+// The Radau sweep behind marl_sweep_radau_dev / _events_dev / _eval_dev.
 // t_events (host, may be NULL): [instance][7][max_events] root times of the seven monitors, located inside the sweep as the single run
 // locates them (dense output of the accepted step + Brent, one A_DENSE action per function evaluation); entries beyond n_events are NaN.
-extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
-                                           const int32_t* groups, int64_t max_attempts, double* t_events, int64_t max_events, marl_stats* stats)
+// t_eval (host, n_eval times), y_eval_dev (device, [instance][n_eval][5N]), n_done (host, [instance]): the samples inside every accepted
+// step by the same dense output, one A_FRAME action each, after the step's roots (PC_FRAMES); n_eval = 0: none, and the same cycles.
+static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
+                       int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, double* t_events,
+                       int64_t max_events, marl_stats* stats)
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_radau_dev: invalid argument") : -1;
-    const bool locate = t_events != nullptr && max_events > 0;
+    if (n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done))) return fail(ctx, -1, "marl_sweep_radau_eval_dev: invalid argument");
+    const bool locate = t_events != nullptr && max_events > 0, frames = n_eval > 0;
     if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_radau_dev: whole-grid context required");
     if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "radau: need first_step > 0 and t1 >= t0 (forward integration)");
     if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "radau: `first_step` exceeds bounds");
     if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "radau: tolerances must be positive");
+    for (int64_t i = 0; i < n_eval; i++)
+        if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
+            return fail(ctx, -1, "radau: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
     if (ctx->batch > 65535) return fail(ctx, -1, "marl_sweep_radau_dev: at most 65535 instances per call");
     const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
     if (n > 8192) return fail(ctx, -1, "marl_sweep_radau_dev: sweeps are for small grids (N <= 1638); use marl_integrate_radau for one large grid");
+    if (n_done) memset(n_done, 0, sizeof(int64_t) * (size_t)B);
     HIP_OK(ctx, hipSetDevice(ctx->device));
     rtol = clamp_rtol(rtol);
     RadauWork w;
@@ -2790,11 +2790,17 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
         HIP_OK(ctx, hipMemsetAsync(drec_dense, 0, sizeof(double) * NQ * B, ctx->stream));
         HIP_OK(ctx, hipMemsetAsync(dtev, 0xff, sizeof(double) * (size_t)(7 * max_events) * B, ctx->stream));   // (all bits set: NaN)
     }
+    double* dteval = nullptr;      // the sample times, for the controllers
+    if (frames) {                  // (pageable host memory: the copy has left the caller's array when the call returns)
+        HIP_OK(ctx, hipMalloc((void**)&dteval, sizeof(double) * (size_t)n_eval));
+        HIP_OK(ctx, hipMemcpyAsync(dteval, t_eval, sizeof(double) * (size_t)n_eval, hipMemcpyHostToDevice, ctx->stream));
+    }
     unsigned* wg_next = nullptr;   // one-workgroup-per-instance paths: the instance queue, then the list of instances a pass visits [2 B]
     auto cleanup = [&]() {
         (void)hipFree(dctl); (void)hipFree(drec); (void)hipFree(dcounts);
         if (drec_dense) (void)hipFree(drec_dense);
         if (dtev) (void)hipFree(dtev);
+        if (dteval) (void)hipFree(dteval);
         if (wg_next) (void)hipFree(wg_next);
     };
     std::vector<RadauCtl> hctl((size_t)B);
@@ -2805,6 +2811,7 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
         c.t = t0; c.S_h_abs = first_step; c.S_h_abs_old = -1; c.S_err_old = -1;
         c.pc = radau::PC_INIT; c.status = 1;
         c.locate_events = locate ? 1 : 0; c.max_events = max_events;
+        c.n_eval = n_eval;
     }
     if (hipMemcpyAsync(dctl, hctl.data(), sizeof(RadauCtl) * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { cleanup(); return fail(ctx, -3, "copy failed"); }
     if (hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
@@ -2852,7 +2859,7 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
     //   2            the workgroup does those as well (no host in the loop; measured slower: cyclic reduction on ONE compute unit);
     //   0            the launch-per-action cycle (larger grids always take it).
     const int wg_mode = (n <= PCR_FUSED_MAX) ? (int)ctx->radau_sweep_wg : 0;
-    const bool use_wg = wg_mode == 2 && !locate;
+    const bool use_wg = wg_mode == 2 && !locate && !frames;
     WgWork ww{};
     if (wg_mode) {
         if (!ctx->cus) {
@@ -2875,7 +2882,7 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
         const int32_t* run_list = nrun < 0 ? nullptr : reinterpret_cast<const int32_t*>(wg_next + 2);
 #define MARL_WG_LAUNCH(VD_, H_)                                                                                                             \
         hipLaunchKernelGGL((radau_wg_kernel<VD_, H_>), grid, dim3(WG_THREADS), 0, ctx->stream, dctl, B, N, ww, ctx->dconsts, atol, P, E3[0], E3[1], E3[2], \
-                           wg_next, dcounts, dlists, dtev, run_list, todo)
+                           wg_next, dcounts, dlists, dtev, run_list, todo, (const double*)dteval, y_eval_dev)
         if (ctx->var_dphi) {
             if (hybrid == 0) MARL_WG_LAUNCH(true, 0); else if (hybrid == 1) MARL_WG_LAUNCH(true, 1); else MARL_WG_LAUNCH(true, 2);
         } else {
@@ -2888,14 +2895,14 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
         RB_OK();
     }
     int64_t wg_nrun = -1;
-    const bool hybrid = wg_mode == 1 || wg_mode == 3 || (wg_mode == 2 && locate);
+    const bool hybrid = wg_mode == 1 || wg_mode == 3 || (wg_mode == 2 && (locate || frames));
     const int hybrid_kind = wg_mode == 3 ? 2 : 1;   // 2: Jacobians stay in the workgroup, only factorisations come back to the host cycle
     for (int64_t cycle = 0; !use_wg; cycle++) {
         // the controllers advance every instance to its next piece of work and sort the instances into work lists; the host
         // reads the list lengths (one small copy + synchronisation per cycle) and launches each kind of work over its list only
         if (!zc_words || cycle == 0) (void)hipMemsetAsync(dcounts, 0, sizeof(int32_t) * L_COUNT, ctx->stream);   // (publish_counts_kernel zeroes them afterwards)
         if (hybrid) launch_wg(hybrid_kind, wg_nrun);   // every running instance up to its next Jacobian / factorisation (or its end)
-        else hipLaunchKernelGGL(radau_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, drec_dense, dtev);
+        else hipLaunchKernelGGL(radau_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, drec_dense, dtev, dteval);
         RB_OK();
         if (zc_words) {   // the list lengths through polled host memory
             hipLaunchKernelGGL(publish_counts_kernel, dim3(1), dim3(1), 0, ctx->stream, dcounts, reinterpret_cast<int32_t*>(ctx->zc_d + 16), (int32_t)(cycle + 1));
@@ -2923,7 +2930,11 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
             wg_nrun = nj + nl;
         }
         const unsigned nR = (unsigned)hcounts[L_RHS1], nA = (unsigned)hcounts[L_ACCEPT], nJ = (unsigned)hcounts[L_JAC], nL = (unsigned)hcounts[L_LU],
-                       nN = (unsigned)hcounts[L_NEWTON], nE = (unsigned)hcounts[L_ERR], nD = (unsigned)hcounts[L_DENSE];
+                       nN = (unsigned)hcounts[L_NEWTON], nE = (unsigned)hcounts[L_ERR], nD = (unsigned)hcounts[L_DENSE], nF = (unsigned)hcounts[L_FRAME];
+        if (nF) {   // t_eval samples inside the accepted step: its dense output into the instances' frames (no monitors: nothing reads a frame)
+            hipLaunchKernelGGL(frame_eval_batch_kernel, dim3(gx, 1, nF), b256, 0, ctx->stream, w.Q, w.yold, n, y_eval_dev, n_eval, Z(L_FRAME));
+            RB_OK();
+        }
         if (nD) {   // event root finding: the dense output of the accepted step at the abscissa Brent asks for, and that state's monitors
             hipLaunchKernelGGL(dense_eval_batch_kernel, dim3(gx, 1, nD), b256, 0, ctx->stream, w.Q, w.yold, n, w.tmp, Z(L_DENSE));
             RB_OK();
@@ -3048,9 +3059,37 @@ extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double 
             st.nfev = c.nfev; st.njev = c.njev; st.nlu = c.nlu; st.n_accepted = c.n_acc; st.n_rejected = c.n_rej;
             st.status = c.status; st.t = c.t; st.h_next = c.S_h_abs;
             for (int e = 0; e < 7; e++) { st.event_value[e] = c.g[e]; st.n_events[e] = c.n_events[e]; }
+            if (frames) n_done[b] = c.fr_next;
         }
+    if (rc_out == 0 && t1 == t0 && frames && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as the single run gives it
+        const size_t row = sizeof(double) * (size_t)n;
+        if (hipMemcpy2DAsync(y_eval_dev, row * (size_t)n_eval, y_dev, row, row, (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            rc_out = fail(ctx, -3, "state copy failed");
+        else
+            for (int64_t b = 0; b < B; b++) n_done[b] = 1;
+    }
     cleanup();
     return rc_out;
+}
+
+extern "C" int marl_sweep_radau_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                    const int32_t* groups, int64_t max_attempts, marl_stats* stats)
+{
+    return sweep_radau(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
+}
+
+extern "C" int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                           const int32_t* groups, int64_t max_attempts, double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_radau(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, nullptr, 0, nullptr, nullptr, t_events, max_events, stats);
+}
+
+extern "C" int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                         const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                         int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_radau(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats);
 }
 
 #endif  // MARL_LAB

@@ -69,7 +69,7 @@ __device__ inline cplx lift(double a, cplx) { return {a, 0.0}; }
 // Batched sweeps of Radau instances (marl_radau_batch.h): every instance follows its own control flow, advanced one ACTION per
 // cycle by a device-side controller; the kernels below serve the single-instance driver (ctl == NULL, scalar arguments) and the
 // batched one (blockIdx.z = instance; per-instance scalars from ctl[z]; ZBatch masks out instances that need something else).
-enum : int32_t { A_RHS_Y = 1, A_JAC = 2, A_LU = 4, A_NEWTON = 8, A_ERR = 16, A_ACCEPT = 32, A_ERR2 = 64, A_DENSE = 128 };
+enum : int32_t { A_RHS_Y = 1, A_JAC = 2, A_LU = 4, A_NEWTON = 8, A_ERR = 16, A_ACCEPT = 32, A_ERR2 = 64, A_DENSE = 128, A_FRAME = 256 };
 struct RadauCtl {
     // set once
     double t_bound, rtol, atol, newton_tol;
@@ -96,6 +96,10 @@ struct RadauCtl {
     int64_t max_events;
     double dense_x;                  // (t - sol_t_old) / sol_h of the state the A_DENSE kernels evaluate
     double br_a, br_b, br_fa, xpre, xcur, xblk, fpre, fcur, fblk, spre, scur;
+    // t_eval frames inside a sweep (ivp.py:706-723): after the roots of an accepted step, one A_FRAME action per sample inside it - the
+    // dense output at dense_x written to frame fr_next of the instance.  n_eval = 0: no samples (set once)
+    int64_t n_eval, fr_next;         // fr_next: the frames written so far = the index of the next sample
+    int32_t fr_wait, pad3;           // fr_wait: an A_FRAME action is out; count it on resume
 };
 __device__ __forceinline__ const RadauCtl* ctl_of(const ZBatch& B)
 {

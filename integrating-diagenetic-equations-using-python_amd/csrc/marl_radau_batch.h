@@ -16,7 +16,7 @@ namespace marl {
 namespace radau {
 
 enum : int32_t { PC_INIT = 0, PC_GOT_F0, PC_STEP, PC_ATTEMPT, PC_NEWTON_START, PC_NEWTON_LU_DONE, PC_NEWTON_ITER, PC_ERR_DONE, PC_ACCEPTED, PC_ACCEPTED_JAC_DONE, PC_DONE,
-                 PC_EVENTS, PC_BRENT };
+                 PC_EVENTS, PC_BRENT, PC_FRAMES };
 constexpr int NEWTON_MAXITER = 6;
 
 __device__ __forceinline__ double predict_factor(double h_abs, double h_abs_old, double error_norm, double error_norm_old)   // radau.py:133-173
@@ -31,13 +31,15 @@ __device__ __forceinline__ double predict_factor(double h_abs, double h_abs_old,
 // Work lists: the controller appends each instance to the list of every kernel group that serves its action; counts[L_*] are read by
 // the host, which sizes the launches by them (masked-out workgroups are not free: at 512 instances a cycle that launched every kernel
 // over every instance spent 2.4 ms dispatching ~320 000 workgroups that returned at once).
-enum : int { L_RHS1 = 0, L_ACCEPT, L_JAC, L_LU, L_NEWTON, L_ERR, L_RUNNING, L_DENSE, L_COUNT };
+enum : int { L_RHS1 = 0, L_ACCEPT, L_JAC, L_LU, L_NEWTON, L_ERR, L_RUNNING, L_DENSE, L_FRAME, L_COUNT };
+static_assert(L_COUNT + 1 <= 32, "the host's two count buffers hold 32 words (the lengths, then the sequence word)");
 
 // One instance's step logic from where it stopped to its next action (c.action, c.pc).  g_now: the seven monitors of the instance's y.
 // (Brent's method: brent_advance, marl_brent.h - shared with the RK45 sweep that locates roots, on RadauCtl's own fields here.)
 // g_dense: the seven monitors of the dense-output state the last A_DENSE action evaluated (event root finding); t_events: this
-// instance's root times [7][max_events] (NULL: sign changes are only counted).
-__device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g_now)[7], int64_t n, const double* g_dense = nullptr, double* t_events = nullptr)
+// instance's root times [7][max_events] (NULL: sign changes are only counted).  t_eval: the c.n_eval sample times of the sweep.
+__device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g_now)[7], int64_t n, const double* g_dense = nullptr, double* t_events = nullptr,
+                                                   const double* t_eval = nullptr)
 {
     const double S6 = sqrt(6.0);
     const double C3[3] = {(4 - S6) / 10, (4 + S6) / 10, 1};
@@ -204,11 +206,7 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
             continue;
         }
         if (pc == PC_EVENTS) {                   // the next monitor whose root in (sol_t_old, t] is still to be located (ivp.py:686-694)
-            if (c.ev_pending == 0) {
-                if (c.t - c.t_bound >= 0) { c.status = 0; pc = PC_DONE; break; }
-                pc = PC_STEP;
-                continue;
-            }
+            if (c.ev_pending == 0) { pc = PC_FRAMES; continue; }
             int e = 0;
             while (!((c.ev_pending >> e) & 1)) e++;
             c.br_e = e; c.br_phase = 0; c.br_iter = 0;
@@ -255,6 +253,18 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
             pc = PC_EVENTS;
             continue;
         }
+        if (pc == PC_FRAMES) {                   // the samples in (sol_t_old, t] - and t0 with the first step - by dense output (ivp.py:706-723)
+            if (c.fr_wait) { c.fr_wait = 0; c.fr_next++; }   // (the frame asked for in the last cycle is written)
+            if (c.fr_next < c.n_eval && t_eval[c.fr_next] <= c.t) {
+                c.dense_x = (t_eval[c.fr_next] - c.sol_t_old) / c.sol_h;
+                c.fr_wait = 1;
+                c.action = A_FRAME;              // frame fr_next of this instance
+                break;
+            }
+            if (c.t - c.t_bound >= 0) { c.status = 0; pc = PC_DONE; break; }   // (no samples: reached in the cycle that accepted the step, as before)
+            pc = PC_STEP;
+            continue;
+        }
         break;
     }
     c.pc = pc;
@@ -262,7 +272,8 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
 
 __global__ void __launch_bounds__(64) radau_control_kernel(RadauCtl* __restrict__ ctls, const double* __restrict__ rec, int64_t B, int64_t n,
                                                            int32_t* __restrict__ counts, int32_t* __restrict__ lists,
-                                                           const double* __restrict__ rec_dense = nullptr, double* __restrict__ t_events = nullptr)
+                                                           const double* __restrict__ rec_dense = nullptr, double* __restrict__ t_events = nullptr,
+                                                           const double* __restrict__ t_eval = nullptr)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
@@ -276,7 +287,7 @@ __global__ void __launch_bounds__(64) radau_control_kernel(RadauCtl* __restrict_
         const double gd[7] = {d[1], d[2], d[3], d[5] - 1.0, d[6] - 1.0, d[4], d[7]};
         for (int e = 0; e < 7; e++) g_dense[e] = gd[e];
     }
-    radau_control_step(c, g_now, n, g_dense, t_events ? t_events + b * 7 * c.max_events : nullptr);
+    radau_control_step(c, g_now, n, g_dense, t_events ? t_events + b * 7 * c.max_events : nullptr, t_eval);
     const int pc = c.pc;
     ctls[b] = c;
     if (pc != PC_DONE) atomicAdd(&counts[L_RUNNING], 1);
@@ -288,6 +299,7 @@ __global__ void __launch_bounds__(64) radau_control_kernel(RadauCtl* __restrict_
     if (c.action & A_NEWTON) push(L_NEWTON);
     if (c.action & (A_ERR | A_ERR2)) push(L_ERR);
     if (c.action & A_DENSE) push(L_DENSE);
+    if (c.action & A_FRAME) push(L_FRAME);
 }
 
 // A_DENSE: the dense output of the step just accepted at x = ctl.dense_x (RadauDenseOutput, radau.py:557-572; dense_eval_kernel) -> out
@@ -297,6 +309,22 @@ __global__ void __launch_bounds__(256) dense_eval_batch_kernel(const double* __r
     if (z_masked_out(B)) return;
     const RadauCtl* c = ctl_of(B);
     Q = z_shift(Q, B); yold = z_shift(yold, B); out = z_shift(out, B);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double q0 = Q[3 * i], q1 = Q[3 * i + 1], q2 = Q[3 * i + 2], yo = yold[i];
+    const double p1 = c->dense_x, p2 = p1 * p1, p3 = p2 * p1;
+    out[i] = dot3(q0, p1, q1, p2, q2, p3) + yo;
+}
+
+// A_FRAME: the same dense output at the sample t_eval[ctl.fr_next] -> frame fr_next of the instance, y_eval [B][n_eval][n] (contiguous:
+// not the arena's stride).  Nothing else reads a frame: no monitors follow, and the buffers of the root search stay as they are.
+__global__ void __launch_bounds__(256) frame_eval_batch_kernel(const double* __restrict__ Q, const double* __restrict__ yold, int64_t n, double* __restrict__ y_eval,
+                                                               int64_t n_eval, ZBatch B)
+{
+    if (z_masked_out(B)) return;
+    const RadauCtl* c = ctl_of(B);
+    Q = z_shift(Q, B); yold = z_shift(yold, B);
+    double* out = y_eval + ((int64_t)z_inst(B) * n_eval + c->fr_next) * n;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double q0 = Q[3 * i], q1 = Q[3 * i + 1], q2 = Q[3 * i + 2], yo = yold[i];

@@ -154,7 +154,8 @@ __global__ void __launch_bounds__(WG_THREADS) radau_wg_kernel(RadauCtl* __restri
                                                               double fd_threshold, P33 P, double E0, double E1, double E2, unsigned* __restrict__ next_instance,
                                                               int32_t* __restrict__ counts = nullptr, int32_t* __restrict__ lists = nullptr,
                                                               double* __restrict__ t_events = nullptr, const int32_t* __restrict__ run_list = nullptr,
-                                                              int64_t todo = -1)
+                                                              int64_t todo = -1, const double* __restrict__ t_eval = nullptr,
+                                                              double* __restrict__ y_eval = nullptr)
 {
     constexpr int hybrid = HYBRID;
     __shared__ WgBuf buf;
@@ -193,7 +194,7 @@ __global__ void __launch_bounds__(WG_THREADS) radau_wg_kernel(RadauCtl* __restri
             if (tid == 0) {
                 double g[7], gd[7];
                 for (int e = 0; e < 7; e++) { g[e] = g_now[e]; gd[e] = g_dense[e]; }
-                radau_control_step(sc, g, n, gd, t_events ? t_events + b * 7 * sc.max_events : nullptr);
+                radau_control_step(sc, g, n, gd, t_events ? t_events + b * 7 * sc.max_events : nullptr, t_eval);
             }
             __syncthreads();
             WG_TICK(0);
@@ -216,6 +217,13 @@ __global__ void __launch_bounds__(WG_THREADS) radau_wg_kernel(RadauCtl* __restri
                 for (int64_t i = tid; i < n; i += WG_THREADS) out[i] = dot3(Q[3 * i], p1, Q[3 * i + 1], p2, Q[3 * i + 2], p3) + yold[i];
                 __syncthreads();
                 wg_monitors(out, N, C, T, buf.red, g_dense);
+            }
+            // ---- a t_eval sample inside the accepted step: the same dense output into frame fr_next of the instance (frame_eval_batch_kernel)
+            if (action & A_FRAME) {
+                const double *Q = wg_at(w.Q, off), *yold = wg_at(w.yold, off);
+                double* out = y_eval + (b * sc.n_eval + sc.fr_next) * n;
+                const double p1 = sc.dense_x, p2 = p1 * p1, p3 = p2 * p1;
+                for (int64_t i = tid; i < n; i += WG_THREADS) out[i] = dot3(Q[3 * i], p1, Q[3 * i + 1], p2, Q[3 * i + 2], p3) + yold[i];
             }
 
             // ---- a single state -> its derivative: y -> f (start), y + err -> tmp (second error estimate), y_new -> f_new (accepted step)

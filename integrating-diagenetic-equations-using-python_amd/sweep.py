@@ -103,11 +103,22 @@ class HipSweepEngine:
             r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
-    def integrate_radau(self, y0, t_span, first_step, rtol, atol, max_attempts):
+    def integrate_radau(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64):
         """The reference's default solver over the shard: every instance its own Radau step logic, advanced together on the device
-        (marl_sweep_radau_dev).  Returns (y_final (n_local, 5N), list of RK45Result)."""
+        (marl_sweep_radau_dev).  Returns (y_final (n_local, 5N), list of RK45Result); ``t_eval`` and ``events`` as for
+        :meth:`integrate_rk45` (marl_sweep_radau_eval_dev: samples and roots on the accepted step's dense output, inside the sweep)."""
         yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
-        res = self.model.sweep_radau_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+        more = {"events": True, "max_events": max_events} if events else {}
+        if t_eval is None:
+            res = self.model.sweep_radau_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
+            return yd.cpu().numpy(), res
+        n_eval = int(np.size(t_eval))
+        frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
+        res = self.model.sweep_radau_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
+                                            y_eval_dev_ptr=frames.data_ptr(), **more)
+        frames = frames.cpu().numpy()
+        for b, r in enumerate(res):
+            r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
     def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None):
@@ -171,14 +182,15 @@ def initial_states(base_parms, instances):
 
 
 def run_sweep_radau(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                    device=None, engine_factory=None, gather=True, balance="cost", cost=None):
+                    device=None, engine_factory=None, gather=True, balance="cost", cost=None, t_eval=None, events=False, max_events=64):
     """As :func:`run_sweep_rk45` with the reference's DEFAULT solver (scipy Radau semantics, marlpde/parameters.py:213): what the
     reference does one scenario per process (its tests loop over scenarios), spread over the ranks with no data-path collective.
     An implicit run's cost depends on the scenario (20x between the fastest and the slowest of a parameter grid), and the slowest
     rank sets the wall time: ``balance`` = ``"cost"`` (default: :func:`assign` by ``cost``, or by :func:`implicit_cost_proxy` when
-    none is given), ``"round_robin"`` or ``"contiguous"``.  Results come back in the order of ``instances`` whatever the assignment."""
+    none is given), ``"round_robin"`` or ``"contiguous"``.  Results come back in the order of ``instances`` whatever the assignment.
+    ``t_eval``, ``events``, ``max_events`` and what they add to the returned tuple: as documented for :func:`run_sweep_rk45`."""
     return _run_sweep("integrate_radau", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost)
+                      balance, cost, t_eval, events, max_events)
 
 
 def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
@@ -223,7 +235,7 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
         dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device   # one process per GPU
         engine_factory = lambda bp, inst: HipSweepEngine(bp, inst, dev)  # noqa: E731
     y0 = np.asarray(y0)
-    sampled = t_eval is not None   # (RK45 only: the drivers of the implicit sweeps pass none)
+    sampled = t_eval is not None   # (RK45 and Radau sweeps; the BDF driver passes none)
     if sampled:
         t_eval = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
     if local:
