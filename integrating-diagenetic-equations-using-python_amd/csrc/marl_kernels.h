@@ -123,12 +123,22 @@ struct StencilBlock {
     unsigned edge_cells;
     __device__ __forceinline__ bool edge_wave() const
     {
-        if constexpr (EDGE_ONCE) return edge_cells & 1u;
+        if constexpr (SEAM > 0) {   // (tested where it is used, on an opaque copy: hoisted out of the step loop the test becomes a lane mask - a pair, spilled)
+            unsigned e = edge_cells;
+            asm volatile("" : "+s"(e));
+            return e & 1u;
+        } else if constexpr (EDGE_ONCE) return edge_cells & 1u;
         else return __builtin_amdgcn_ballot_w64(is_edge() != 0) != 0;
     }
-    __device__ __forceinline__ unsigned is_first() const { return masks & 1u; }
-    __device__ __forceinline__ unsigned is_last() const { return (masks >> 8) & 1u; }
-    __device__ __forceinline__ unsigned in_zone() const { return (masks >> 16) & 1u; }
+    // SEAM (rk4_chain_kernel): the three bits as three flags instead - an interior window sets them on the scalar side (set_interior), and
+    // merged with a packed word they would be unpacked again per lane in every window
+    bool w_zone = false;
+    // (SEAM: compared where they are asked for, inside the boundary branch, on an opaque copy of the word - formed in front of the step
+    // loop the two compares are lane masks, two pairs carried and spilled across every stage for a branch one wave of the grid takes)
+    __device__ __forceinline__ unsigned edge_word() const { unsigned e = edge_cells; asm volatile("" : "+s"(e)); return e; }
+    __device__ __forceinline__ unsigned is_first() const { if constexpr (SEAM > 0) return (unsigned)tid + 1u == ((edge_word() >> 8) & 0x1ffu); else return masks & 1u; }
+    __device__ __forceinline__ unsigned is_last() const { if constexpr (SEAM > 0) return (unsigned)tid + 1u == ((edge_word() >> 20) & 0x1ffu); else return (masks >> 8) & 1u; }
+    __device__ __forceinline__ unsigned in_zone() const { if constexpr (SEAM > 0) return w_zone; else return (masks >> 16) & 1u; }
     __device__ __forceinline__ unsigned is_edge() const { return masks & 0x101u; }   // first or last: non-zero
     PointCache<(CACHE && CACHE_LDS) ? BLK : 0> cache;  // centre of the transcendental expansions (TR_FILL / TR_REUSE / TR_AUTO)
     bool reuse_live = false;     // wave-uniform: the centre is filled and no evaluation since has fallen out of range
@@ -154,7 +164,8 @@ struct StencilBlock {
     __device__ __forceinline__ StencilBlock(double* lds_, int64_t g0, const DevConsts* __restrict__ c)
         : lds(lds_), T(load_tables(lds_ + EDGE_DOUBLES, BLK)), K(load_hot(c)), C(c), tid(threadIdx.x), parity(0)
     {
-        set_window(g0);
+        if constexpr (SEAM > 0) set_interior(false);   // (every window sets its own)
+        else set_window(g0);
         if constexpr (CACHE && CACHE_LDS) cache.s = lds_ + EDGE_DOUBLES + TABLE_DOUBLES + tid;
     }
 
@@ -174,6 +185,33 @@ struct StencilBlock {
         masks = ((g == 0) ? 1u : 0u) | ((g == N - 1) ? 0x100u : 0u) | ((g >= mlo && g < mhi) ? 0x10000u : 0u);
         edge_cells = 0;
         if constexpr (EDGE_ONCE) edge_cells = (__builtin_amdgcn_ballot_w64(is_edge() != 0) != 0) ? 1u : 0u;
+    }
+
+    // SEAM: the same from the scalar side.  gw: global index of the cell of the window's thread 0 (wave-uniform).  The one word says
+    // whether this WAVE holds a boundary cell (bit 0, what set_window's ballot gives) and which thread of the window sits on cell 0
+    // (bits 8-16: 1 + thread, 0 = none) and on cell N - 1 (bits 20-28): the stages carry one scalar register for the two boundary
+    // cells of the grid instead of two lane masks, and the lanes are told apart only inside the branch that one wave of the grid takes.
+    __device__ __forceinline__ void set_window_seam(int64_t gw)
+    {
+        const int64_t N = C->N, mlo = C->mask_lo, mhi = C->mask_hi;
+        const int64_t g = gw + tid;
+        w_zone = g >= mlo && g < mhi;
+        masks = 0;
+        const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
+        const int64_t t0 = -gw, t1 = N - 1 - gw;   // the threads on cell 0 and on cell N - 1
+        unsigned e = 0;
+        if (t0 >= 0 && t0 < BLK) e |= (((unsigned)t0 + 1u) << 8) | ((int)(t0 >> 6) == wave ? 1u : 0u);
+        if (t1 >= 0 && t1 < BLK) e |= (((unsigned)t1 + 1u) << 20) | ((int)(t1 >> 6) == wave ? 1u : 0u);
+        edge_cells = __builtin_amdgcn_readfirstlane(e);
+    }
+
+    // SEAM: a window that holds neither cell 0 nor cell N - 1 and lies wholly inside (zone) or wholly outside the dissolution zone -
+    // what set_window gives for every lane of it, without a per-lane instruction.  `zone` is wave-uniform.
+    __device__ __forceinline__ void set_interior(bool zone)
+    {
+        w_zone = zone;
+        masks = 0;
+        edge_cells = 0;
     }
 
     // k = RHS(stage state ys) for the thread's cell.  Contains exactly one __syncthreads(): the own-cell phase
@@ -257,7 +295,22 @@ struct StencilBlock {
 #pragma unroll
                     for (int f = 0; f < NF; f++) up[f] = ghost_upper(f, ys[f], um[f]);
                 }
-                if (is_first()) {
+                if constexpr (SEAM > 0) {
+                    // The boundary values through an opaque address, read HERE, in the wave-uniform part of the branch: hoisted to the kernel's
+                    // start they are scalar pairs that live across the step loop, and the allocator reloads their spilled copies in every step.
+                    // (the OFFSET is what is opaque: an opaque copy of the pointer counts as captured, and every scalar load of the
+                    // constants behind it becomes a vector load)
+                    size_t off = offsetof(DevConsts, bc);
+                    asm volatile("" : "+s"(off));
+                    const double* bcp = reinterpret_cast<const double*>(reinterpret_cast<const char*>(C) + off);
+                    double bcv[NF];
+#pragma unroll
+                    for (int f = 0; f < NF; f++) bcv[f] = bcp[f];
+                    if (is_first()) {
+#pragma unroll
+                        for (int f = 0; f < NF; f++) um[f] = ghost_lower(bcv[f], ys[f]);
+                    }
+                } else if (is_first()) {
 #pragma unroll
                     for (int f = 0; f < NF; f++) um[f] = ghost_lower(C->bc[f], ys[f]);
                 }
@@ -737,6 +790,31 @@ rk4_stream_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ cons
 // is rk4_stream_kernel's; an item still depends on items t-1, t, t+1 of the level before (host, chain_shape: no item but the
 // last is narrower than H cells).  tools/check_stream_isa.py checks I1-I5 on this kernel too (tests/test_chain_isa.py).
 // ---------------------------------------------------------------------------------------------
+// rk4_chain_kernel's arguments as they lie in its kernel-argument segment.  The kernel reads those it needs once per item or per window
+// through an opaque pointer to that segment (scalar loads) instead of holding them: held, they are spilled to lanes of a vector register
+// - the loop sits at its cap of scalar registers - and every use costs a v_readlane.
+struct ChainArgs {
+    double *bufA, *bufB;
+    const DevConsts* consts;
+    Slab S;
+    double dt;
+    unsigned levels, items;
+    unsigned *queue, *done, *sticky;
+    unsigned item_base, level_base;
+    double* bufC;
+    unsigned K, nsub_last;
+    int64_t bound;
+};
+static_assert(offsetof(ChainArgs, S) == 24 && offsetof(ChainArgs, dt) == 64 && offsetof(ChainArgs, queue) == 80 && offsetof(ChainArgs, bufC) == 112 &&
+              offsetof(ChainArgs, bound) == 128 && sizeof(ChainArgs) == 136, "the argument list of rk4_chain_kernel, in order");
+typedef const __attribute__((address_space(4))) ChainArgs* ChainArgsPtr;
+__device__ __forceinline__ ChainArgsPtr chain_args()
+{
+    ChainArgsPtr a = (ChainArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(a));   // opaque: a load through it is not merged with an earlier one and kept
+    return a;
+}
+
 template <int BLK, int LAYOUT, int NSTEPS>
 __global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4, 8)))
 rk4_chain_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ consts, Slab S, double dt, unsigned levels, unsigned items,
@@ -754,12 +832,22 @@ rk4_chain_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ const
     const DevConsts& C = consts[0];
     SB sb(lds, 0, consts);   // tables once per workgroup (barrier inside)
     sb.seam = seam;
+    // (the step in a scalar pair of its own: it arrives in one wide load with `levels`, `items`, `queue`, `done`, and the allocator keeps -
+    // and, where cold code borrows the registers, reloads in every step - the whole tuple for as long as one member is live)
+    dt = pin_uniform(dt);
     const unsigned total = levels * items;   // (host: < 2^31)
     const unsigned chains = items - 1;
 
     while (true) {
         // (the shape of this loop: see rk4_stream_kernel)
         __syncthreads();
+        // the queue's arguments through the segment too, once per item (they shadow the parameters): they arrive in one wide load with the
+        // step size, and while any member of it is held the allocator keeps - and reloads in every step - the whole tuple
+        typedef __attribute__((address_space(1))) unsigned* GlobalWords;
+        ChainArgsPtr G = chain_args();
+        unsigned *const queue = (unsigned*)(GlobalWords)G->queue, *const done = (unsigned*)(GlobalWords)G->done,
+                 *const sticky = (unsigned*)(GlobalWords)G->sticky;
+        const unsigned items = G->items, item_base = G->item_base, level_base = G->level_base;
         if (threadIdx.x == 0) {
             s_item = __hip_atomic_fetch_add(&queue[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - item_base;
             s_abort = 0;
@@ -787,37 +875,91 @@ rk4_chain_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ const
             __syncthreads();
             if (s_abort) break;
         }
-        const double* src = bufC ? (level == 0 ? bufA : ((level & 1u) ? bufB : bufC)) : ((level & 1u) ? bufB : bufA);
-        double* dst = bufC ? (level + 1 == levels ? bufA : ((level & 1u) ? bufC : bufB)) : ((level & 1u) ? bufA : bufB);
-        // the item's windows (all wave-uniform): window j has its thread 0 on local cell first + j W
-        const bool chain = tile < chains;
-        const unsigned nsub = chain ? (tile + 1 == chains ? nsub_last : K) : 1u;
-        const int64_t first = S.out_lo - H + (chain ? (int64_t)tile * (V + (int64_t)W * (K - 1)) : bound);
-        const int64_t clip = chain ? S.out_lo + bound : S.out_hi;
+        const double* src;
+        double* dst;
+        unsigned nsub;
+        int64_t first, clip;
+        {   // (the arguments through the segment: see ChainArgs)
+            ChainArgsPtr A = chain_args();
+            double *const pA = A->bufA, *const pB = A->bufB, *const pC = A->bufC;
+            const unsigned nlev = A->levels, KK = A->K, nlast = A->nsub_last;
+            const int64_t olo = A->S.out_lo, ohi = A->S.out_hi, bnd = A->bound;
+            src = (const double*)(const __attribute__((address_space(1))) double*)(pC ? (level == 0 ? pA : ((level & 1u) ? pB : pC)) : ((level & 1u) ? pB : pA));
+            dst = (double*)(__attribute__((address_space(1))) double*)(pC ? (level + 1 == nlev ? pA : ((level & 1u) ? pC : pB)) : ((level & 1u) ? pA : pB));
+            // the item's windows (all wave-uniform): window j has its thread 0 on local cell first + j W
+            const bool chain = tile < chains;
+            nsub = chain ? (tile + 1 == chains ? nlast : KK) : 1u;
+            first = olo - H + (chain ? (int64_t)tile * (V + (int64_t)W * (KK - 1)) : bnd);
+            clip = chain ? olo + bnd : ohi;
+        }
 #pragma unroll 1
         for (unsigned j = 0; j < nsub; j++) {
             int tid = threadIdx.x;
             asm volatile("" : "+v"(tid));   // opaque: what derives from the thread index is recomputed per window, not carried across the loops
             sb.rebind(tid);
-            const int64_t l = first + (int64_t)j * W + tid;
-            const bool in = l >= 0 && l < S.n_buf;
+            // An INTERIOR window - wholly inside the buffer, neither cell 0 nor cell N - 1 in it, wholly inside or wholly outside the
+            // dissolution zone: all but three or four windows of a grid - is recognised once on the scalar side (wave-uniform).  Its
+            // masks are constants and its loads need no guard: the per-lane 64-bit compares of set_window, the ballot and the
+            // boundary selects run only in the other windows.  Same values either way.
+            // (The tests are signs of 64-bit differences, formed modulo 2^64 - every operand is below 2^62 - and taken from the high
+            // words: scalar subtractions and one 32-bit compare, where a signed 64-bit compare of two scalars is a vector instruction.)
+            ChainArgsPtr A = chain_args();
+            const int64_t n_buf = A->S.n_buf, goff = A->S.goff, ld = A->S.ld;
+            const int64_t lw = first + (int64_t)j * W, gw = lw + goff;
+            const int64_t mlo = C.mask_lo, mhi = C.mask_hi;
+            // (each sign word opaque: combined freely, they are merged back into 64-bit values and compared on the vector side)
+            auto neg = [](int64_t a, int64_t b) {   // < 0: a < b
+                int32_t hi = (int32_t)(((uint64_t)a - (uint64_t)b) >> 32);
+                asm("" : "+s"(hi));
+                return hi;
+            };
+            const int32_t out_any = neg(lw, 0) | neg(n_buf, lw + BLK) | neg(gw, 1) | neg(C.N - 1, gw + BLK);   // < 0: not interior
+            const int32_t zone_part = neg(gw, mlo) | neg(mhi, gw + BLK);       // >= 0: wholly inside the zone
+            const int32_t zone_some = neg(mlo, gw + BLK) & neg(gw, mhi);       // >= 0: wholly outside
+            const bool interior = out_any >= 0 && (zone_part >= 0 || zone_some >= 0);
+            const int64_t l = lw + tid;
+            bool in = true;
+            int64_t la = l;   // the cell the lane loads: its own, or - outside the buffer - a valid one (the value is replaced below)
+            if (!interior) {
+                asm volatile("");   // a real branch
+                in = l >= 0 && l < n_buf;
+                la = in ? l : 0;
+            }
             double y[NF];
 #pragma unroll
-            for (int f = 0; f < NF; f++)
-                y[f] = in ? __hip_atomic_load(src + at<LAYOUT>(f, l, S.ld), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : C.bc[f];
-            sb.set_window(l + S.goff);
+            for (int f = 0; f < NF; f++) y[f] = __hip_atomic_load(src + at<LAYOUT>(f, la, ld), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (interior) {
+                sb.set_interior(zone_part >= 0);
+            } else {
+                asm volatile("");
+#pragma unroll
+                for (int f = 0; f < NF; f++) y[f] = in ? y[f] : C.bc[f];
+                sb.set_window_seam(gw);
+            }
             sb.reuse_live = false;   // every window fills its own expansion centre, as an item of rk4_stream_kernel does
-            // (readfirstlane: in a scalar register; left to itself the compiler builds it per lane from a lane mask)
-            sb.seam_pos = __builtin_amdgcn_readfirstlane((int)(j & 1u) * 8 + (j ? SB::SEAM_READS : 0) + (tid < 64 ? SB::SEAM_WAVE0 : 0)
-                                                         + (tid / 64 == (BLK - H - 1) / 64 ? SB::SEAM_WAVEW : 0));
+            // (the wave's number through readfirstlane: everything else is then scalar arithmetic; left to itself the compiler builds the
+            // word per lane from lane masks)
+            const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
+            sb.seam_pos = (int)(j & 1u) * 8 + (j ? SB::SEAM_READS : 0) + (wave == 0 ? SB::SEAM_WAVE0 : 0)
+                          + (wave == (BLK - H - 1) / 64 ? SB::SEAM_WAVEW : 0);
+            // the lanes that store, [lo, hi): both bounds are scalars of 32 bits.  hi - the window's end or the clip - is formed here, in front
+            // of the evaluations (one word carried instead of the 64-bit clip); lo is read off the seam word behind them (a window with a left
+            // halo of its own is the one that does not read the seam), where `j == 0` itself would be carried as a lane mask, a spilled pair.
+            const int64_t room = clip - lw;
+            int hi = neg(room, BLK - H) < 0 ? (int)room : BLK - H;
+            asm volatile("" : "+s"(hi));
             rk4_advance<NSTEPS>(sb, y, dt);
-            const int lo = j ? 0 : H;
+            int sp = sb.seam_pos;
+            asm volatile("" : "+s"(sp));
+            const int lo = (sp & SB::SEAM_READS) ? 0 : H;
             int ts = threadIdx.x;
             asm volatile("" : "+v"(ts));    // (the cell index again: two registers less across the evaluations)
             const int64_t ls = first + (int64_t)j * W + ts;
-            if (ts >= lo && ts < BLK - H && ls < clip) {
+            if (ts >= lo && ts < hi) {
+                int64_t lds_ = 0;   // (the tiled layout has no field stride: no pointer to the segment is formed for it)
+                if constexpr (LAYOUT == LAYOUT_FIELD_MAJOR) lds_ = chain_args()->S.ld;
 #pragma unroll
-                for (int f = 0; f < NF; f++) __hip_atomic_store(dst + at<LAYOUT>(f, ls, S.ld), y[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int f = 0; f < NF; f++) __hip_atomic_store(dst + at<LAYOUT>(f, ls, lds_), y[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
