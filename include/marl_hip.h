@@ -219,6 +219,20 @@ int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double 
 int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                               const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                               int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* A SWEEP of BDF integrations: the other implicit method the reference's Solver names for its jac_sparsity
+ * (marlpde/parameters.py:205-219), for many scenarios at once.  It replaces a loop of solve_ivp(method="BDF") runs (and this library's
+ * own loop of marl_integrate_bdf runs, one busy workgroup and a host round trip per solve each): every instance follows scipy's BDF
+ * step logic (scipy/integrate/_ivp/bdf.py:310-450, restated for one instance in bdf_run) as a device-side state machine
+ * (csrc/marl_bdf_ctl.h), and the host repeats one fixed cycle of launches over work lists (csrc/marl_bdf_batch.h) - every kernel runs
+ * to completion, none waits for another workgroup.  Semantics of marl_sweep_radau_dev: y_dev [n_instances][5N] FIELD-MAJOR, advanced
+ * in place; stats[b]: nfev / njev / nlu / n_accepted / n_rejected / status / t / h_next as scipy counts them, n_events the monitors'
+ * sign changes over accepted steps, event_value the monitors of the final state.  t1 == t0: no step, the state is untouched,
+ * status 0, nfev = njev = 1 (BDF.__init__).  A failed solve is a status, not an error.  Synchronises.
+ * It does NOT: locate root times or write t_eval frames (BDF's dense output is built after the order change; both are
+ * marl_integrate_bdf's), take grids whose solve does not fit one workgroup (5 N <= 2048, N <= 409; larger: -1, use marl_integrate_bdf),
+ * or keep an instance in a persistent workgroup. */
+int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                       const int32_t* groups, int64_t max_attempts, marl_stats* stats);
 
 /* ---- 1-D domain decomposition of ONE large grid (BASELINE config 5; the reference never decomposes the depth
  * axis).  One process per GPU holds a slab [g_begin, g_end) of the N_global cells in a slab context; the host

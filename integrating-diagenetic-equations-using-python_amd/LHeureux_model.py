@@ -454,6 +454,19 @@ class LMAHeureuxPorosityDiff:
         return [RK45Result(s, t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
                 for b, s in enumerate(stats)]
 
+    def sweep_bdf_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None):
+        """Every instance of the model integrated with scipy's BDF semantics, all instances advanced together on the device
+        (marl_sweep_bdf_dev: per-instance step control on the device, batched solves); device states [instances][5N] in place.
+        Returns one :class:`RK45Result` per instance (statistics; the monitors' sign changes are counted in ``n_events``).  Root
+        times and ``t_eval`` frames are not part of this sweep (single runs: :meth:`integrate_bdf`), and the grid is limited to
+        N <= 409 (a solve must fit one workgroup)."""
+        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        stats = (MarlStats * self.n_instances)()
+        rc = self._lib.marl_sweep_bdf_dev(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol),
+                                          float(atol), _as_ptr(grp) if grp is not None else None, int(max_attempts), stats)
+        self._check(rc, "marl_sweep_bdf_dev")
+        return [RK45Result(s) for s in stats]
+
     def sweep_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
                           events=False, max_events=64):
         """Every instance integrated with adaptive RK45, one workgroup each (marl_sweep_rk45_dev); device states [instances][5N]

@@ -20,6 +20,7 @@
 #include "marl_radau_wg.h"
 #include "marl_bdf.h"
 #include "marl_bdf_wg.h"
+#include "marl_bdf_batch.h"
 
 using namespace marl;
 
@@ -3090,6 +3091,221 @@ extern "C" int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0
                                          int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
 {
     return sweep_radau(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats);
+}
+
+// ---- a sweep of BDF instances (marl_bdf_batch.h, marl_bdf_ctl.h) ---------------------------------------------------------------
+// BDF.__init__ of every instance (f, the first Jacobian, D, the monitors) in front of the cycle, then the cycle of sweep_radau's
+// launch-per-action mode: controllers, the list lengths through polled host memory (or a copy: implicit_zero_copy = 0), then every
+// kind of work over its list in the order marl_bdf_ctl.h documents.  No kernel waits for another workgroup.
+static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
+                     int64_t max_attempts, marl_stats* stats)
+{
+    if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_bdf_dev: invalid argument") : -1;
+    if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_bdf_dev: whole-grid context required");
+    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "bdf: need first_step > 0 and t1 >= t0 (forward integration)");
+    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "bdf: `first_step` exceeds bounds");
+    if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "bdf: tolerances must be positive");
+    if (ctx->batch > 65535) return fail(ctx, -1, "marl_sweep_bdf_dev: at most 65535 instances per call");
+    const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
+    if (n > radau::PCR_FUSED_MAX)
+        return fail(ctx, -1, "marl_sweep_bdf_dev: a solve must fit one workgroup (N <= %d); use marl_integrate_bdf (run_sweep_bdf without batched) for larger grids",
+                    (int)(radau::PCR_FUSED_MAX / NF));
+    if (ctx->radau_solver != 0) return fail(ctx, -1, "marl_sweep_bdf_dev: needs the PCR solver (option radau_solver = 0)");
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    rtol = clamp_rtol(rtol);
+    RadauWork w;
+    int64_t zs = 0;
+    if (int rc = radau_alloc(ctx, w, groups, B, &zs)) return rc;
+    if (w.cr_k && !w.plan.k) return fail(ctx, -1, "marl_sweep_bdf_dev: the cyclic-reduction levels of this context do not fit the one-launch solve");
+    using bdf::BdfCtl;
+    using namespace bdf;
+    BdfCtl* dctl = nullptr;
+    double* drec = nullptr;
+    int32_t* dcounts = nullptr;   // [L_COUNT] then lists [BL_COUNT][B]
+    HIP_OK(ctx, hipMalloc((void**)&dctl, sizeof(BdfCtl) * B));
+    auto cleanup = [&]() {
+        (void)hipFree(dctl);
+        if (drec) (void)hipFree(drec);
+        if (dcounts) (void)hipFree(dcounts);
+    };
+    if (hipMalloc((void**)&drec, sizeof(double) * NQ * B) != hipSuccess || hipMalloc((void**)&dcounts, sizeof(int32_t) * (size_t)(radau::L_COUNT + BL_COUNT * B)) != hipSuccess) {
+        cleanup();
+        return fail(ctx, -3, "allocation failed");
+    }
+    int32_t* dlists = dcounts + radau::L_COUNT;
+    std::vector<BdfCtl> hctl((size_t)B);
+    for (auto& c : hctl) bdfctl::bdf_control_init(c, t0, t1, first_step, rtol, atol, max_attempts);
+#define SB_FAIL(...)               \
+    do {                           \
+        cleanup();                 \
+        return fail(ctx, __VA_ARGS__); \
+    } while (0)
+#define SB_OK()                                                                                   \
+    do {                                                                                          \
+        hipError_t e_ = hipGetLastError();                                                        \
+        if (e_ != hipSuccess) SB_FAIL(-100 - (int)e_, "kernel launch failed: %s", hipGetErrorString(e_)); \
+    } while (0)
+    if (hipMemcpyAsync(dctl, hctl.data(), sizeof(BdfCtl) * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) SB_FAIL(-3, "copy failed");
+    if (hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        SB_FAIL(-3, "state copy failed");
+    if (hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream) != hipSuccess) SB_FAIL(-3, "memset failed");
+    bdf::Vec6 gamma = {};
+    for (int k = 1; k <= bdf::MAX_ORDER; k++) gamma.v[k] = gamma.v[k - 1] + 1.0 / k;
+    double* D = w.Z;
+    double* f = w.Z0;
+    double *ypred = w.Q, *psi = w.Q + n, *d = w.Q + 2 * n;
+    const dim3 b256(256);
+    const unsigned gx = blocks256(n), gc = blocks256(N);
+    const int64_t nbm = std::min<int64_t>((N + 255) / 256, 1024);
+    if (int rc = ensure_part(ctx, (size_t)(nbm * B))) { cleanup(); return rc; }
+    auto L = [&](int which) { return BdfBatch{zs, dctl, dlists + (int64_t)which * B}; };
+    auto Z = [&](int which) { return ZBatch{zs, nullptr, 0, 0, dlists + (int64_t)which * B}; };
+    // the finite-difference Jacobian at (yj, fj) of the instances of zb (cnt of them); first: no step-size factors yet (num_jac)
+    auto jacobian = [&](const double* yj, const double* fj, int first, unsigned cnt, const ZBatch& zb) -> int {
+        hipLaunchKernelGGL(radau::fd_prepare_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, yj, fj, w.fac, atol, first, w.groups, w.ng, n, w.h, w.yscale, w.YP, zb);
+        for (int pass = 0; pass < 2; pass++) {
+            if (ctx->var_dphi)
+                hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), dim3(gc, (unsigned)w.ng, cnt), b256, 0, ctx->stream, w.YP, w.FN, ctx->dconsts, ctx->slab, n, 0, zb);
+            else
+                hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, dim3(gc, (unsigned)w.ng, cnt), b256, 0, ctx->stream, w.YP, w.FN, ctx->dconsts, ctx->slab, n, 0, zb);
+            if (pass == 0)
+                hipLaunchKernelGGL(radau::fd_columns_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, yj, fj, w.FN, w.groups, w.ng, N, w.fac, w.yscale, w.Jraw, w.maxdiff,
+                                   w.scl, w.small, w.hnew, w.YP, zb);
+            else
+                hipLaunchKernelGGL(radau::fd_finish_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, fj, w.FN, w.groups, N, w.fac, w.h, w.maxdiff, w.scl, w.small, w.hnew,
+                                   w.Jraw, w.J, zb);
+        }
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    };
+    auto rhs_of = [&](const double* src, double* dst, unsigned cnt, const ZBatch& zb) {
+        if (ctx->var_dphi)
+            hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), dim3(gc, 1, cnt), b256, 0, ctx->stream, src, dst, ctx->dconsts, ctx->slab, n, 0, zb);
+        else
+            hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, dim3(gc, 1, cnt), b256, 0, ctx->stream, src, dst, ctx->dconsts, ctx->slab, n, 0, zb);
+    };
+    // BDF.__init__ of every instance: f = fun(t0, y0); J = jac(t0, y0); D[0] = y0, D[1] = f h; g = events(t0, y0)
+    {
+        const ZBatch all{zs, nullptr, 0, 0, nullptr};
+        rhs_of(w.y, w.f, (unsigned)B, all);
+        SB_OK();
+        if (jacobian(w.y, w.f, 1, (unsigned)B, all)) SB_FAIL(-3, "kernel launch failed (Jacobian)");
+        hipLaunchKernelGGL(init_D_batch_kernel, dim3(gx, 1, (unsigned)B), b256, 0, ctx->stream, w.y, w.f, n, D, BdfBatch{zs, dctl, nullptr});
+        SB_OK();
+        hipLaunchKernelGGL(monitors_kernel<LAYOUT_FIELD_MAJOR>, dim3((unsigned)nbm, (unsigned)B), b256, 0, ctx->stream, w.y, ctx->dconsts, ctx->slab, zs / 8, ctx->part);
+        SB_OK();
+        hipLaunchKernelGGL(reduce_records_kernel, dim3((unsigned)B), b256, 0, ctx->stream, ctx->part, nbm, drec);
+        SB_OK();
+    }
+    int32_t* hcounts = reinterpret_cast<int32_t*>(ctx->rd_host);
+    volatile int32_t* zc_words = nullptr;
+    if (ctx->implicit_zero_copy) {
+        if (!ctx->zc_h) {
+            if (hipHostMalloc((void**)&ctx->zc_h, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+                hipHostGetDevicePointer((void**)&ctx->zc_d, ctx->zc_h, 0) != hipSuccess) SB_FAIL(-3, "host allocation failed");
+        }
+        zc_words = reinterpret_cast<volatile int32_t*>(ctx->zc_h + 16);
+        zc_words[radau::L_COUNT] = 0;
+    }
+    constexpr int64_t kStallCycles = 1000;   // cycles without any instance moving (pc, attempts, status): every cycle moves each running one
+    int64_t stalled = 0;
+    for (int64_t cycle = 0;; cycle++) {
+        hipLaunchKernelGGL(bdf_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists);
+        SB_OK();
+        if (zc_words) {   // the list lengths through polled host memory (the kernel zeroes the counts for the next cycle)
+            hipLaunchKernelGGL(radau::publish_counts_kernel, dim3(1), dim3(1), 0, ctx->stream, dcounts, reinterpret_cast<int32_t*>(ctx->zc_d + 16), (int32_t)(cycle + 1));
+            SB_OK();
+            int64_t spins = 0;
+            while (zc_words[radau::L_COUNT] != (int32_t)(cycle + 1)) {
+#if defined(__x86_64__)
+                __builtin_ia32_pause();
+#endif
+                if (++spins > (int64_t)1 << 28) {
+                    if (hipStreamSynchronize(ctx->stream) != hipSuccess || zc_words[radau::L_COUNT] != (int32_t)(cycle + 1)) SB_FAIL(-3, "sweep: the work-list lengths never arrived");
+                }
+            }
+            for (int i = 0; i < BL_COUNT; i++) hcounts[i] = zc_words[i];
+        } else {
+            (void)hipMemcpyAsync(hcounts, dcounts, sizeof(int32_t) * BL_COUNT, hipMemcpyDeviceToHost, ctx->stream);
+            (void)hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream);
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) SB_FAIL(-3, "synchronize failed");
+        }
+        const unsigned nA = (unsigned)hcounts[BL_ACCEPT], nC = (unsigned)hcounts[BL_CHANGE_D], nJ = (unsigned)hcounts[BL_JAC], nL = (unsigned)hcounts[BL_LU],
+                       nS = (unsigned)hcounts[BL_SOLVE];
+        if (nA > B || nC > B || nJ > B || nL > B || nS > B) SB_FAIL(-3, "sweep: a work list is longer than the sweep");
+        stalled = hcounts[BL_PROGRESS] ? 0 : stalled + 1;
+        if (stalled >= kStallCycles) {
+            (void)hipStreamSynchronize(ctx->stream);
+            SB_FAIL(-3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
+        }
+        if (nA) {   // the accepted step: differences, y = y_new, the norms of the order selection
+            hipLaunchKernelGGL(accept_norms_batch_kernel, dim3(1, 1, nA), dim3(1024), 0, ctx->stream, D, d, w.ynew, n, w.y, L(BL_ACCEPT));
+            SB_OK();
+        }
+        if (nC) {
+            hipLaunchKernelGGL(change_D_batch_kernel, dim3(gx, 1, nC), b256, 0, ctx->stream, D, n, L(BL_CHANGE_D));
+            SB_OK();
+        }
+        if (nJ) {   // J = jac(t_new, y_predict), with f = fun(t_new, y_predict) (not counted)
+            rhs_of(ypred, w.fnew, nJ, Z(BL_JAC));
+            SB_OK();
+            if (jacobian(ypred, w.fnew, 0, nJ, Z(BL_JAC))) SB_FAIL(-3, "kernel launch failed (Jacobian)");
+        }
+        if (nL) {   // LU of I - c J (pcr_factor_launch, real system)
+            if (w.cr_k) {
+                hipLaunchKernelGGL(cr_init_batch_kernel, dim3(pcr_groups((N + 1) / 2), 1, nL), b256, 0, ctx->stream, w.J, N, w.Cr, L(BL_LU));
+                SB_OK();
+                for (int l = 0; l < w.cr_k; l++) {
+                    const radau::CrShape sh{w.cr_n[l], w.cr_off[l], w.cr_n[l + 1], w.cr_off[l + 1]};
+                    hipLaunchKernelGGL(cr_reduce_batch_kernel, dim3(pcr_groups(sh.n_next), 1, nL), b256, 0, ctx->stream, w.Cr, sh, l + 1 == w.cr_k ? 1 : 0, w.Sr, L(BL_LU));
+                    SB_OK();
+                }
+                const int64_t M = w.cr_n[w.cr_k];
+                for (int level = 0; level < w.nlevels; level++) {
+                    hipLaunchKernelGGL(pcr_factor_batch_kernel, dim3(pcr_groups(M), 1, nL), b256, 0, ctx->stream, w.J, M, level, w.Sr, L(BL_LU));
+                    SB_OK();
+                }
+            } else {
+                for (int level = -1; level < w.nlevels; level++) {
+                    hipLaunchKernelGGL(pcr_factor_batch_kernel, dim3(pcr_groups(N), 1, nL), b256, 0, ctx->stream, w.J, N, level, w.Sr, L(BL_LU));
+                    SB_OK();
+                }
+            }
+        }
+        if (nS) {   // solve_bdf_system: one workgroup per instance
+            if (ctx->var_dphi)
+                hipLaunchKernelGGL(solve_batch_kernel<true>, dim3(1, 1, nS), dim3(radau::WG_THREADS), 0, ctx->stream, D, gamma, ypred, psi, w.scale, w.ynew, d, f, N, w.nlevels,
+                                   w.Sr, ctx->dconsts, w.plan, w.Cr, L(BL_SOLVE));
+            else
+                hipLaunchKernelGGL(solve_batch_kernel<false>, dim3(1, 1, nS), dim3(radau::WG_THREADS), 0, ctx->stream, D, gamma, ypred, psi, w.scale, w.ynew, d, f, N, w.nlevels,
+                                   w.Sr, ctx->dconsts, w.plan, w.Cr, L(BL_SOLVE));
+            SB_OK();
+        }
+        if (hcounts[BL_RUNNING] == 0) break;   // (the last cycle's accepted steps are launched above)
+    }
+#undef SB_OK
+#undef SB_FAIL
+    int rc_out = 0;
+    if (hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        rc_out = fail(ctx, -3, "state copy failed");
+    if (rc_out == 0 && hipMemcpyAsync(hctl.data(), dctl, sizeof(BdfCtl) * B, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc_out = fail(ctx, -3, "copy failed");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc_out == 0) rc_out = fail(ctx, -3, "synchronize failed");
+    if (rc_out == 0)
+        for (int64_t b = 0; b < B; b++) {
+            const BdfCtl& c = hctl[(size_t)b];
+            marl_stats& st = stats[b];
+            memset(&st, 0, sizeof st);
+            st.nfev = c.nfev; st.njev = c.njev; st.nlu = c.nlu; st.n_accepted = c.n_acc; st.n_rejected = c.n_rej;
+            st.status = c.status; st.t = c.t; st.h_next = c.S_h_abs;
+            for (int e = 0; e < 7; e++) { st.event_value[e] = c.g[e]; st.n_events[e] = c.n_events[e]; }
+        }
+    cleanup();
+    return rc_out;
+}
+
+extern "C" int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                  const int32_t* groups, int64_t max_attempts, marl_stats* stats)
+{
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, stats);
 }
 
 #endif  // MARL_LAB

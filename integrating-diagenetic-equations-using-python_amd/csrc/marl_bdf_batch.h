@@ -1,0 +1,213 @@
+// marl_bdf_batch.h - a SWEEP of implicit BDF integrations: the kernels of marl_sweep_bdf_dev (marl_api.hip, sweep_bdf).  The shape is
+// the Radau sweep's launch-per-action cycle (marl_radau_batch.h, radau_sweep_wg = 0): every instance runs scipy's BDF step logic as a
+// resumable state machine (marl_bdf_ctl.h; bdf_control_kernel, one lane per instance) that publishes its next piece of data-parallel
+// work as an action word; the host repeats one fixed cycle of launches, each over the work list of the instances that asked for it.
+// Every kernel runs to completion; nothing here waits for another workgroup.
+//
+// Arena of an instance (radau_alloc; bdf_run's layout): D = [Z | W | F] (8 n of 9 n), f(t_new, y) of the Newton iteration = Z0,
+// y_predict / psi / d = Q, f(t0, y0) = f, f(t_new, y_predict) of a Jacobian refresh = fnew.
+// The vector kernels keep the thread mapping and the reduction order of their single-run kernels (marl_bdf.h), the solve IS the
+// single run's (solve_wg_body, marl_bdf_wg.h), the Jacobian is the Radau path's fd_* sequence over a list and the factorisation calls
+// the same group functions (pcr_factor_group, cr_init_group, cr_reduce_group) with (mu, jscale) = (1, c) of the instance - so a sweep
+// and a single run differ by the controller's scalar arithmetic (device libm; R U with numpy's roundings) and nothing else.
+#pragma once
+#include "marl_bdf_ctl.h"
+#include "marl_bdf_wg.h"
+#include "marl_radau_cr.h"
+
+namespace marl {
+namespace bdf {
+
+using bdfctl::BdfCtl;
+
+// work lists of a cycle; the count words are published by radau::publish_counts_kernel (L_COUNT words, then the sequence word)
+enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_RUNNING, BL_PROGRESS, BL_COUNT };
+static_assert(BL_COUNT <= radau::L_COUNT, "publish_counts_kernel copies L_COUNT words");
+
+// blockIdx.z -> instance (list == NULL: every instance, in order), its arena and its controller
+struct BdfBatch {
+    int64_t zstride;
+    BdfCtl* ctls;
+    const int32_t* list;
+};
+__device__ __forceinline__ ZBatch z_of(const BdfBatch& B) { return ZBatch{B.zstride, nullptr, 0, 0, B.list}; }
+
+// One lane per instance: resume the step logic, run it to the next action word, append the instance to the list of every bit.
+// rec: [B][8] monitors records of the instances' initial states (read at the first cycle).
+__global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ctls, const double* __restrict__ rec, int64_t B, int64_t n,
+                                                         int32_t* __restrict__ counts, int32_t* __restrict__ lists)
+{
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    BdfCtl c = ctls[b];
+    if (c.pc == bdfctl::PC_DONE) return;
+    const double* r = rec + b * 8;
+    const double g0[7] = {r[1], r[2], r[3], r[5] - 1.0, r[6] - 1.0, r[4], r[7]};   // record_to_events (marl_api.hip)
+    const int32_t pc0 = c.pc, status0 = c.status;
+    const int64_t attempts0 = c.attempts;
+    bdfctl::bdf_control_step(c, n, g0);
+    ctls[b] = c;
+    if (c.pc != bdfctl::PC_DONE) atomicAdd(&counts[BL_RUNNING], 1);
+    if (c.pc != pc0 || c.status != status0 || c.attempts != attempts0) atomicAdd(&counts[BL_PROGRESS], 1);
+    auto push = [&](int which) { lists[(int64_t)which * B + atomicAdd(&counts[which], 1)] = (int32_t)b; };
+    if (c.action & bdfctl::A_ACCEPT) push(BL_ACCEPT);
+    if (c.action & bdfctl::A_CHANGE_D) push(BL_CHANGE_D);
+    if (c.action & bdfctl::A_JAC) push(BL_JAC);
+    if (c.action & bdfctl::A_LU) push(BL_LU);
+    if (c.action & bdfctl::A_SOLVE) push(BL_SOLVE);
+}
+
+// D[0] = y0, D[1] = f h  (init_D_kernel; h = the controller's first step)
+__global__ void __launch_bounds__(256) init_D_batch_kernel(const double* __restrict__ y, const double* __restrict__ f, int64_t n, double* __restrict__ D, BdfBatch B)
+{
+    const ZBatch zb = z_of(B);
+    const double h = B.ctls[z_inst(zb)].S_h_abs;
+    y = z_shift(y, zb); f = z_shift(f, zb); D = z_shift(D, zb);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    D[i] = y[i];
+    D[n + i] = f[i] * h;
+}
+
+// A_CHANGE_D: D[:order + 1] = RU^T D[:order + 1] with the controller's RU and ru_order (change_D_kernel)
+__global__ void __launch_bounds__(256) change_D_batch_kernel(double* __restrict__ D, int64_t n, BdfBatch B)
+{
+    const ZBatch zb = z_of(B);
+    const BdfCtl* c = B.ctls + z_inst(zb);
+    D = z_shift(D, zb);
+    const int order = c->ru_order;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double d[MAX_ORDER + 1];
+#pragma unroll
+    for (int j = 0; j <= MAX_ORDER; j++) d[j] = j <= order ? D[(int64_t)j * n + i] : 0.0;
+#pragma unroll
+    for (int k = 0; k <= MAX_ORDER; k++) {
+        if (k > order) break;
+        double a = 0;
+#pragma unroll
+        for (int j = 0; j <= MAX_ORDER; j++)
+            if (j <= order) a += c->RU[j][k] * d[j];
+        D[(int64_t)k * n + i] = a;
+    }
+}
+
+// A_ACCEPT, one workgroup per instance: the accepted step's update of the differences and y = y_new (accept_kernel), then the norms
+// of the order selection the controller asked for (want_norms) - each with the loop and the reduction tree of scaled_norm_kernel /
+// scaled_norm2_kernel with one workgroup -> ctl.ss_m, ctl.ss_p.  order: the controller's (it changes in the cycle AFTER the norms).
+__global__ void __launch_bounds__(1024) accept_norms_batch_kernel(double* __restrict__ D, const double* __restrict__ d, const double* __restrict__ ynew, int64_t n,
+                                                                  double* __restrict__ y, BdfBatch B)
+{
+    __shared__ double red[1024];
+    const ZBatch zb = z_of(B);
+    BdfCtl* c = B.ctls + z_inst(zb);
+    D = z_shift(D, zb); d = z_shift(d, zb); ynew = z_shift(ynew, zb); y = z_shift(y, zb);
+    const int order = c->order, want = c->want_norms;
+    const double rtol = c->rtol, atol = c->atol;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) {
+        const double di = d[i];
+        D[(int64_t)(order + 2) * n + i] = di - D[(int64_t)(order + 1) * n + i];
+        D[(int64_t)(order + 1) * n + i] = di;
+        double above = di;
+        for (int j = order; j >= 0; j--) {
+            const double v = D[(int64_t)j * n + i] + above;
+            D[(int64_t)j * n + i] = v;
+            above = v;
+        }
+        y[i] = ynew[i];
+    }
+    if (!want) return;   // (uniform)
+    __syncthreads();     // (each thread reads back only what it wrote: i stays in its residue class; the barrier keeps the kernel plain)
+    double r[2] = {0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        if (!((want >> k) & 1)) continue;   // (uniform)
+        const double* v = D + (int64_t)(k ? order + 2 : order) * n;
+        const double coef = k ? c->err_coef_p : c->err_coef_m;
+        double ss = 0;
+        for (int64_t i = threadIdx.x; i < n; i += 1024) {
+            const double e = coef * v[i] / (atol + rtol * fabs(y[i]));
+            ss += e * e;
+        }
+        __syncthreads();
+        red[threadIdx.x] = ss;
+        __syncthreads();
+        for (int s = 512; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+            __syncthreads();
+        }
+        r[k] = red[0];
+    }
+    if (threadIdx.x == 0) {
+        if (want & 1) c->ss_m = r[0];
+        if (want & 2) c->ss_p = r[1];
+    }
+}
+
+// A_LU: the real system  I - c J  of every listed instance - the group functions of pcr_factor_kernel / cr_init_kernel /
+// cr_reduce_kernel with (mu, jscale) = (1, c) of the instance, as pcr_factor_launch(ctx, w, 1.0, {0, 0}, c, 1) passes them for one
+__global__ void __launch_bounds__(256) pcr_factor_batch_kernel(const double* __restrict__ J, int64_t N, int level, radau::PcrSystem<double> Sr, BdfBatch B)
+{
+    using namespace radau;
+    const ZBatch zb = z_of(B);
+    const double jscale = B.ctls[z_inst(zb)].c;
+    J = z_shift(J, zb); Sr = z_shift_system(Sr, zb);
+    __shared__ PcrStage<double> stage[PCR_CELLS_PER_BLOCK];
+    const int g = threadIdx.x >> 5, e = threadIdx.x & 31;
+    const int64_t i = (int64_t)blockIdx.x * PCR_CELLS_PER_BLOCK + g;
+    pcr_factor_group<double>(J, N, level, 1.0, Sr, stage[g], jscale, i, e);
+}
+
+__global__ void __launch_bounds__(256) cr_init_batch_kernel(const double* __restrict__ J, int64_t N, radau::CrSystem<double> Cr, BdfBatch B)
+{
+    using namespace radau;
+    const ZBatch zb = z_of(B);
+    const double jscale = B.ctls[z_inst(zb)].c;
+    J = z_shift(J, zb); Cr = z_shift_cr(Cr, zb);
+    __shared__ PcrStage<double> stage[PCR_CELLS_PER_BLOCK];
+    const int g = threadIdx.x >> 5, e = threadIdx.x & 31;
+    const int64_t i = (int64_t)blockIdx.x * PCR_CELLS_PER_BLOCK + g;
+    cr_init_group<double>(J, N, 1.0, jscale, Cr, stage[g], i, e);
+}
+
+__global__ void __launch_bounds__(256) cr_reduce_batch_kernel(radau::CrSystem<double> Cr, radau::CrShape sh, int last, radau::PcrSystem<double> Sr, BdfBatch B)
+{
+    using namespace radau;
+    const ZBatch zb = z_of(B);
+    Cr = z_shift_cr(Cr, zb); Sr = z_shift_system(Sr, zb);
+    __shared__ PcrStage<double> stage[PCR_CELLS_PER_BLOCK];
+    const int g = threadIdx.x >> 5, e = threadIdx.x & 31;
+    const int64_t i = (int64_t)blockIdx.x * PCR_CELLS_PER_BLOCK + g;
+    double *Ln = last ? Sr.L[0] : Cr.L + sh.off_next * 25, *Dn = last ? Sr.D[0] : Cr.D + sh.off_next * 25;
+    double *Un = last ? Sr.U[0] : Cr.U + sh.off_next * 25, *In = last ? Sr.Dinv[0] : Cr.Dinv + sh.off_next * 25;
+    cr_reduce_group<double>(1.0, Cr, sh, last != 0, Ln, Dn, Un, In, stage[g], i, e);
+}
+
+// A_SOLVE: solve_bdf_system of every listed instance, one workgroup each - the single run's body with the scalars of the instance's
+// controller; what the single run's kernel writes into the zero-copy words goes into the controller
+template <bool VD>
+__global__ void __launch_bounds__(radau::WG_THREADS) solve_batch_kernel(const double* __restrict__ D, Vec6 gamma, double* __restrict__ ypred, double* __restrict__ psi,
+                                                                         double* __restrict__ scale, double* __restrict__ ynew, double* __restrict__ d,
+                                                                         double* __restrict__ f, int64_t N, int nlevels, radau::PcrSystem<double> Sr,
+                                                                         const DevConsts* __restrict__ consts, radau::CrPlan pl, radau::CrSystem<double> Cr, BdfBatch B)
+{
+    using namespace radau;
+    const ZBatch zb = z_of(B);
+    const int64_t inst = z_inst(zb);
+    BdfCtl* c = B.ctls + inst;
+    D = z_shift(D, zb); ypred = z_shift(ypred, zb); psi = z_shift(psi, zb); scale = z_shift(scale, zb); ynew = z_shift(ynew, zb); d = z_shift(d, zb); f = z_shift(f, zb);
+    Sr = z_shift_system(Sr, zb); Cr = z_shift_cr(Cr, zb);
+    const SolveOut r = solve_wg_body<VD>(c->mode, D, c->order, gamma, c->alpha_order, ypred, psi, scale, ynew, d, f, N, c->c, nlevels, Sr, consts[inst], c->newton_tol,
+                                         c->err_coef, c->rtol, c->atol, pl, Cr);
+    if (threadIdx.x == 0) {
+        c->iters = r.iters;
+        c->converged = r.converged;   // (0 when f was not finite: the iteration was abandoned, bdf.py:44-45)
+        c->dy_ss = r.dy_ss;
+        c->err_ss = r.err_ss;
+        if (r.converged)
+            for (int e = 0; e < 7; e++) c->g_new[e] = r.g_new[e];
+    }
+}
+
+}  // namespace bdf
+}  // namespace marl

@@ -1,0 +1,249 @@
+// marl_bdf_ctl.h - the step logic of scipy's BDF (scipy/integrate/_ivp/bdf.py:310-450 inside the solve_ivp loop, ivp.py:654-723; restated
+// for one instance in marl_api.hip, bdf_run) as a RESUMABLE state machine for the BDF sweep (marl_bdf_batch.h): bdf_control_step runs
+// one instance's scalar logic up to the next point where it needs a result of data-parallel work, publishes everything that needs no
+// scalar decision in between as ONE action word (A_* bits) and resumes in the next cycle with the kernels' results.  The work of an
+// action word is done in this fixed order (the host cycle's launch order, and what a CPU driver of this header has to do):
+//     A_ACCEPT (+ the order-selection norms asked for by `want_norms`)  ->  A_CHANGE_D (RU, ru_order)  ->  A_JAC (f and J at y_predict)
+//     ->  A_LU (I - c J)  ->  A_SOLVE (solve_bdf_system; mode 0: predictor first, 1: restart from y_predict)
+// so that an accepted step without order selection costs one cycle (accept | solve of the next step) and one with it two.
+// f(t0, y0), the first Jacobian, D[0] = y0, D[1] = f h and the monitors of y0 (BDF.__init__) are done before the first cycle.
+// Like marl_brent.h: nothing but <math.h> / <stdint.h>, so that a host C++ compiler builds this header alone
+// (tests/test_bdf_control_cpu.py holds it to scipy's solve_ivp(method="BDF") that way).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define MARL_BDF_FN __host__ __device__ __forceinline__
+#else
+#define MARL_BDF_FN inline
+#endif
+
+namespace marl {
+namespace bdfctl {
+
+constexpr int MAX_ORDER = 5, NEWTON_MAXITER = 4;
+constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10;
+
+enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16 };
+enum : int32_t { PC_INIT = 0, PC_STEP, PC_ATTEMPT, PC_SOLVED, PC_SELECT, PC_STEP_END, PC_DONE };
+
+struct BdfCtl {
+    // set once
+    double t_bound, rtol, atol, newton_tol;
+    int64_t max_attempts;
+    // BDF._step_impl state
+    double t, S_h_abs, h_abs, min_step, h, t_new, error_norm, safety;
+    double g[7];                       // the monitors of the last accepted state
+    int64_t n_events[7];
+    int64_t nfev, njev, nlu, n_acc, n_rej, attempts;
+    int32_t action;                    // A_* bits: the work of this cycle
+    int32_t pc, status;
+    int32_t order, n_equal_steps, have_lu, current_jac, n_iter;
+    // what the kernels of this cycle read
+    int32_t mode;                      // A_SOLVE: 0 = predictor first, 1 = restart from y_predict
+    int32_t want_norms;                // A_ACCEPT: bit 0 = the norm of error_const[order - 1] D[order], bit 1 = of error_const[order + 1] D[order + 2]
+    int32_t ru_order, pad;             // A_CHANGE_D: D[:ru_order + 1] = RU^T D[:ru_order + 1]
+    double c;                          // h / alpha[order]
+    double alpha_order, err_coef;      // alpha[order], error_const[order] of the solve
+    double err_coef_m, err_coef_p;     // error_const[order -+ 1] of the order selection
+    double RU[MAX_ORDER + 1][MAX_ORDER + 1];
+    double ru_factor;                  // (the factor RU was built from: for the record)
+    // what the kernels leave
+    int32_t iters, converged;          // A_SOLVE: function evaluations; converged (0 too when f was not finite)
+    double dy_ss, err_ss;              // sum (dy / scale)^2 of the last iteration; sum (error_const[order] d / scale)^2 of the converged state
+    double g_new[7];                   // the monitors of the converged state
+    double ss_m, ss_p;                 // A_ACCEPT: the two sums of want_norms
+};
+
+MARL_BDF_FN double kappa_of(int k) { return k == 1 ? -0.1850 : k == 2 ? -1.0 / 9 : k == 3 ? -0.0823 : k == 4 ? -0.0415 : 0.0; }
+MARL_BDF_FN double gamma_of(int k)   // gamma = hstack((0, cumsum(1 / arange(1, MAX_ORDER + 1))))
+{
+    double g = 0;
+    for (int j = 1; j <= k; j++) g = g + 1.0 / j;
+    return g;
+}
+MARL_BDF_FN double alpha_of(int k) { return (1 - kappa_of(k)) * gamma_of(k); }
+MARL_BDF_FN double error_const_of(int k) { return kappa_of(k) * gamma_of(k) + 1.0 / (k + 1); }
+
+// compute_R (bdf.py:18-25).  R U has entries that cancel to zero in exact arithmetic, so the roundings are spelled out: numpy's
+// (i - 1 - factor j) / i with every operation rounded, and below R.dot(U) as its BLAS sums it (a chain of fused multiply-adds over
+// ascending k) - with both, RU is numpy's bit for bit and the CPU test's runs take scipy's steps to the last bit.
+MARL_BDF_FN void compute_R(int order, double factor, double (&R)[MAX_ORDER + 1][MAX_ORDER + 1])
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    for (int j = 0; j <= order; j++) R[0][j] = 1;
+    for (int i = 1; i <= order; i++) {
+        R[i][0] = 0;
+        for (int j = 1; j <= order; j++) R[i][j] = R[i - 1][j] * ((i - 1 - factor * j) / i);
+    }
+}
+
+// change_D (bdf.py:28-33): the product R U of the rescaling by `factor`, left in the controller for the kernel (A_CHANGE_D)
+MARL_BDF_FN void request_change_D(BdfCtl& c, double factor)
+{
+    double R[MAX_ORDER + 1][MAX_ORDER + 1], U[MAX_ORDER + 1][MAX_ORDER + 1];
+    const int order = c.order;
+    compute_R(order, factor, R);
+    compute_R(order, 1.0, U);
+    for (int i = 0; i <= order; i++)
+        for (int j = 0; j <= order; j++) {
+            double a = 0;
+            for (int k = 0; k <= order; k++) a = fma(R[i][k], U[k][j], a);
+            c.RU[i][j] = a;
+        }
+    c.ru_order = order;
+    c.ru_factor = factor;
+    c.action |= A_CHANGE_D;
+}
+
+// A controller at (t0, first_step) in front of its first cycle.  rtol: already clamped to 100 eps (ivp's validate_tol).
+MARL_BDF_FN void bdf_control_init(BdfCtl& c, double t0, double t1, double first_step, double rtol, double atol, int64_t max_attempts)
+{
+    c = BdfCtl{};
+    c.t_bound = t1; c.rtol = rtol; c.atol = atol; c.max_attempts = max_attempts;
+    c.newton_tol = fmax(10 * 2.220446049250313e-16 / rtol, fmin(0.03, sqrt(rtol)));
+    c.t = t0; c.S_h_abs = first_step;
+    c.order = 1;
+    c.pc = PC_INIT; c.status = 1;
+}
+
+// One instance from where it stopped to its next action word.  n: unknowns (5 N).  g0: the seven monitors of y0 (read at PC_INIT only).
+MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0)
+{
+    c.action = 0;
+    int pc = c.pc;
+    // a small interpreter: `continue` = go on with the new pc in this cycle, `break` out of the loop = yield
+    for (int guard = 0; guard < 64; guard++) {
+        if (pc == PC_INIT) {                      // BDF.__init__: f = fun(t0, y0), J = jac(t0, y0), D[0] = y0, D[1] = f h - done before the first cycle
+            for (int e = 0; e < 7; e++) c.g[e] = g0[e];
+            c.nfev = 1; c.njev = 1;
+            c.order = 1; c.n_equal_steps = 0; c.have_lu = 0;
+            pc = PC_STEP;
+            continue;
+        }
+        if (pc == PC_STEP) {                      // top of _step_impl
+            if (c.t == c.t_bound) { c.status = 0; pc = PC_DONE; break; }
+            c.min_step = 10 * fabs(nextafter(c.t, __builtin_inf()) - c.t);
+            if (c.S_h_abs < c.min_step) {
+                if (c.action & A_CHANGE_D) break;   // one rescaling of D per cycle: come back here once the pending one is done
+                c.h_abs = c.min_step;
+                request_change_D(c, c.min_step / c.S_h_abs);
+                c.n_equal_steps = 0;
+            } else {
+                c.h_abs = c.S_h_abs;
+            }
+            c.current_jac = 0;
+            pc = PC_ATTEMPT;
+            continue;
+        }
+        if (pc == PC_ATTEMPT) {                   // top of `while not step_accepted`
+            if (c.h_abs < c.min_step) { c.status = -1; pc = PC_DONE; break; }
+            if (c.max_attempts > 0 && c.attempts >= c.max_attempts) { c.status = 2; pc = PC_DONE; break; }
+            double t_new = c.t + c.h_abs;
+            if (t_new - c.t_bound > 0) {          // clipping at t_bound
+                if (c.action & A_CHANGE_D) break;
+                t_new = c.t_bound;
+                request_change_D(c, fabs(t_new - c.t) / c.h_abs);
+                c.n_equal_steps = 0;
+                c.have_lu = 0;
+            }
+            c.attempts++;
+            c.t_new = t_new;
+            c.h = t_new - c.t;
+            c.h_abs = fabs(c.h);
+            c.alpha_order = alpha_of(c.order);
+            c.err_coef = error_const_of(c.order);
+            c.c = c.h / c.alpha_order;
+            if (!c.have_lu) { c.action |= A_LU; c.nlu++; c.have_lu = 1; }   // LU = self.lu(self.I - c * J)
+            c.mode = 0;
+            c.action |= A_SOLVE; pc = PC_SOLVED;
+            break;
+        }
+        if (pc == PC_SOLVED) {                    // the result of solve_bdf_system
+            c.nfev += c.iters;
+            c.n_iter = c.iters;
+            if (!c.converged) {
+                if (c.current_jac) {              // the step failed: halve
+                    c.h_abs *= 0.5;
+                    request_change_D(c, 0.5);
+                    c.n_equal_steps = 0;
+                    c.have_lu = 0;
+                    c.n_rej++;
+                    pc = PC_ATTEMPT;
+                    continue;
+                }
+                c.njev++;                         // J = self.jac(t_new, y_predict); LU = None; the solve starts again from y_predict
+                c.current_jac = 1;
+                c.nlu++; c.have_lu = 1;
+                c.mode = 1;
+                c.action = A_JAC | A_LU | A_SOLVE; pc = PC_SOLVED;
+                break;
+            }
+            c.safety = 0.9 * (2 * NEWTON_MAXITER + 1) / (2 * NEWTON_MAXITER + c.n_iter);
+            c.error_norm = sqrt(c.err_ss) / sqrt((double)n);
+            if (c.error_norm > 1) {               // (the LU is kept)
+                const double sf = c.safety * pow(c.error_norm, -1.0 / (c.order + 1));
+                const double factor = (sf > MIN_FACTOR) ? sf : MIN_FACTOR;
+                c.h_abs *= factor;
+                request_change_D(c, factor);
+                c.n_equal_steps = 0;
+                c.n_rej++;
+                pc = PC_ATTEMPT;
+                continue;
+            }
+            // accepted
+            c.n_equal_steps++;
+            c.t = c.t_new;
+            c.S_h_abs = c.h_abs;
+            c.n_acc++;
+            for (int e = 0; e < 7; e++) {         // non-terminal events, both directions (ivp.py:131-156): counted, not located
+                const bool up = c.g[e] <= 0 && c.g_new[e] >= 0, down = c.g[e] >= 0 && c.g_new[e] <= 0;
+                if (up || down) c.n_events[e]++;
+                c.g[e] = c.g_new[e];
+            }
+            c.action = A_ACCEPT;
+            c.want_norms = 0;
+            if (c.n_equal_steps < c.order + 1) { pc = PC_STEP_END; continue; }
+            if (c.order > 1) { c.want_norms |= 1; c.err_coef_m = error_const_of(c.order - 1); }
+            if (c.order < MAX_ORDER) { c.want_norms |= 2; c.err_coef_p = error_const_of(c.order + 1); }
+            pc = PC_SELECT;
+            break;
+        }
+        if (pc == PC_SELECT) {                    // order / step-size selection (bdf.py:427-448) with the two norms
+            const double em = (c.want_norms & 1) ? sqrt(c.ss_m) / sqrt((double)n) : __builtin_inf();
+            const double ep = (c.want_norms & 2) ? sqrt(c.ss_p) / sqrt((double)n) : __builtin_inf();
+            const double en[3] = {em, c.error_norm, ep};
+            double factors[3];
+            int best = 0;
+            for (int i = 0; i < 3; i++) {
+                factors[i] = pow(en[i], -1.0 / (c.order + i));
+                if (factors[i] > factors[best]) best = i;
+            }
+            for (int i = 0; i < 3; i++)
+                if (factors[i] != factors[i]) { best = i; break; }   // np.argmax: the first NaN
+            c.order += best - 1;
+            const double sf = c.safety * factors[best];
+            const double factor = (sf < MAX_FACTOR) ? sf : MAX_FACTOR;   // python's min(MAX_FACTOR, x): a NaN x yields MAX_FACTOR
+            c.S_h_abs *= factor;
+            request_change_D(c, factor);
+            c.n_equal_steps = 0;
+            c.have_lu = 0;
+            c.want_norms = 0;
+            pc = PC_STEP_END;
+            continue;
+        }
+        if (pc == PC_STEP_END) {                  // the solve_ivp loop (ivp.py:667-668)
+            if (c.t - c.t_bound >= 0) { c.status = 0; pc = PC_DONE; break; }
+            pc = PC_STEP;
+            continue;
+        }
+        break;
+    }
+    c.pc = pc;
+}
+
+}  // namespace bdfctl
+}  // namespace marl

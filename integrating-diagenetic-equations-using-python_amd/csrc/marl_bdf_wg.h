@@ -24,14 +24,23 @@ union SolveBuf {
     double red[NQ * radau::WG_THREADS];          // reductions (monitors: 64 KB)
 };
 
+// What a solve leaves for the step logic (written by thread 0 only - into the zero-copy words of a single run, into the instance's
+// controller in a sweep); g_new: the monitors of the converged state, in LDS
+struct SolveOut {
+    int iters, converged, any_bad;
+    double dy_ss, err_ss;
+    const double* g_new;
+};
+
+// The body of the solve, for one workgroup of WG_THREADS threads: shared by the single run's kernel below and the sweep's
+// (marl_bdf_batch.h: one workgroup per listed instance, scalars from the instance's controller).
 // mode: 0 = predictor first (bdf.py:358-361 and y = y_predict, d = 0), 1 = restart (y = y_predict, d = 0), 2 = continue from y, d as they are
 template <bool VD>
-__global__ void __launch_bounds__(radau::WG_THREADS) solve_wg_kernel(int mode, const double* __restrict__ D, int order, Vec6 gamma, double alpha_order,
-                                                                      double* __restrict__ ypred, double* __restrict__ psi, double* __restrict__ scale,
-                                                                      double* __restrict__ ynew, double* __restrict__ d, double* __restrict__ f, int64_t N, double c,
-                                                                      int nlevels, radau::PcrSystem<double> Sr, const DevConsts* __restrict__ consts,
-                                                                      double newton_tol, double err_coef, double rtol, double atol, double* __restrict__ words,
-                                                                      radau::CrPlan pl = radau::CrPlan{}, radau::CrSystem<double> Cr = radau::CrSystem<double>{})
+__device__ __forceinline__ SolveOut solve_wg_body(int mode, const double* __restrict__ D, int order, const Vec6& gamma, double alpha_order,
+                                                  double* __restrict__ ypred, double* __restrict__ psi, double* __restrict__ scale,
+                                                  double* __restrict__ ynew, double* __restrict__ d, double* __restrict__ f, int64_t N, double c,
+                                                  int nlevels, const radau::PcrSystem<double>& Sr, const DevConsts& C, double newton_tol, double err_coef,
+                                                  double rtol, double atol, const radau::CrPlan& pl, const radau::CrSystem<double>& Cr)
 {
     using namespace radau;
     __shared__ SolveBuf buf;
@@ -40,7 +49,6 @@ __global__ void __launch_bounds__(radau::WG_THREADS) solve_wg_kernel(int mode, c
     __shared__ double g_new[7];
     __shared__ int s_verdict;
     const Tables T = load_tables(tabs, WG_THREADS);
-    const DevConsts& C = consts[0];
     const HotConsts K = load_hot(&C);
     const int n = (int)(NF * N);
     const int tid = threadIdx.x;
@@ -152,16 +160,29 @@ __global__ void __launch_bounds__(radau::WG_THREADS) solve_wg_kernel(int mode, c
         __syncthreads();
         wg_monitors(ynew, N, C, T, buf.red, g_new);   // what the accepted step's event tests need (monitors_kernel + reduce_records_kernel)
     }
-    if (tid == 0) {
+    return SolveOut{iters, converged, any_bad, dy_ss, err_ss, g_new};
+}
+
+template <bool VD>
+__global__ void __launch_bounds__(radau::WG_THREADS) solve_wg_kernel(int mode, const double* __restrict__ D, int order, Vec6 gamma, double alpha_order,
+                                                                      double* __restrict__ ypred, double* __restrict__ psi, double* __restrict__ scale,
+                                                                      double* __restrict__ ynew, double* __restrict__ d, double* __restrict__ f, int64_t N, double c,
+                                                                      int nlevels, radau::PcrSystem<double> Sr, const DevConsts* __restrict__ consts,
+                                                                      double newton_tol, double err_coef, double rtol, double atol, double* __restrict__ words,
+                                                                      radau::CrPlan pl = radau::CrPlan{}, radau::CrSystem<double> Cr = radau::CrSystem<double>{})
+{
+    const SolveOut r = solve_wg_body<VD>(mode, D, order, gamma, alpha_order, ypred, psi, scale, ynew, d, f, N, c, nlevels, Sr, consts[0], newton_tol, err_coef,
+                                         rtol, atol, pl, Cr);
+    if (threadIdx.x == 0) {
         int32_t* flags = reinterpret_cast<int32_t*>(words + SW_FLAGS);
-        if (any_bad) *flags = 1;
-        words[SW_ERR] = err_ss;
-        words[SW_ITERS] = (double)iters;
-        words[SW_CONVERGED] = (double)converged;
-        if (converged)
-            for (int e = 0; e < 7; e++) words[SW_G + e] = g_new[e];
+        if (r.any_bad) *flags = 1;
+        words[SW_ERR] = r.err_ss;
+        words[SW_ITERS] = (double)r.iters;
+        words[SW_CONVERGED] = (double)r.converged;
+        if (r.converged)
+            for (int e = 0; e < 7; e++) words[SW_G + e] = r.g_new[e];
         __threadfence_system();   // everything above is visible to the host before the word it waits for
-        words[SW_DONE] = dy_ss;
+        words[SW_DONE] = r.dy_ss;
     }
 }
 

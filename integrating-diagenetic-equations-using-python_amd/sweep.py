@@ -77,8 +77,8 @@ class HipSweepEngine:
 
     @property
     def model(self):
-        """The batched model (device constants, controllers, arenas for all instances): built on first use - integrate_bdf runs
-        single-instance contexts and never needs it."""
+        """The batched model (device constants, controllers, arenas for all instances): built on first use - integrate_bdf without
+        ``batched`` runs single-instance contexts and never needs it."""
         if self._model is None:
             from .LHeureux_model import LMAHeureuxPorosityDiff
             self._model = LMAHeureuxPorosityDiff.from_scenario(self.base_parms, device=self.device.index, instances=self.instances)
@@ -121,12 +121,18 @@ class HipSweepEngine:
             r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
-    def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None):
+    def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False):
         """scipy BDF semantics (the other implicit method of the reference's Solver, marlpde/parameters.py:205-219) for every instance of
-        the shard.  There is no batched BDF kernel set (VERDICT r2 missing #5 called it minor): the instances run as concurrent SINGLE runs
-        (marl_integrate_bdf, one context and one HIP stream per worker thread - ctypes releases the GIL, and a single BDF run of a small
-        grid leaves the GPU mostly idle between its small launches), so each instance is bit for bit the single run.  Returns
-        (y_final (n_local, 5N), list of RK45Result)."""
+        the shard.  By default the instances run as concurrent SINGLE runs (marl_integrate_bdf, one context and one HIP stream per worker
+        thread - ctypes releases the GIL, and a single BDF run of a small grid leaves the GPU mostly idle between its small launches),
+        so each instance is bit for bit the single run.  ``batched=True`` runs the shard through the batched kernel set instead
+        (marl_sweep_bdf_dev on the batched model, as :meth:`integrate_radau`: per-instance step control on the device, every launch
+        over all instances that need that work; N <= 409): the same decisions up to the controller's scalar arithmetic, no root
+        times, no ``t_eval``.  Returns (y_final (n_local, 5N), list of RK45Result)."""
+        if batched:
+            yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
+            res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+            return yd.cpu().numpy(), res
         from concurrent.futures import ThreadPoolExecutor
         from .LHeureux_model import LMAHeureuxPorosityDiff
         torch = self.torch
@@ -194,11 +200,12 @@ def run_sweep_radau(base_parms, instances, t_span, first_step, rtol, atol, max_a
 
 
 def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                  device=None, engine_factory=None, gather=True, balance="cost", cost=None):
-    """As :func:`run_sweep_radau` with scipy's BDF semantics; on a GPU the rank's instances run as concurrent single runs
-    (:meth:`HipSweepEngine.integrate_bdf`)."""
+                  device=None, engine_factory=None, gather=True, balance="cost", cost=None, batched=False):
+    """As :func:`run_sweep_radau` with scipy's BDF semantics; on a GPU the rank's instances run as concurrent single runs, or with
+    ``batched=True`` (N <= 409) through the batched BDF kernels, all instances advanced together
+    (:meth:`HipSweepEngine.integrate_bdf`).  ``batched`` reaches the engine only when asked for."""
     return _run_sweep("integrate_bdf", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost)
+                      balance, cost, batched=batched)
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
@@ -220,7 +227,7 @@ def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_at
 
 
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64):
+               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64, batched=False):
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -243,6 +250,8 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
         more = {"t_eval": t_eval} if sampled else {}
         if events:   # (passed only when asked for: engines without root location keep working)
             more |= {"events": True, "max_events": max_events}
+        if batched:   # (the BDF driver; passed only when asked for, like `events`)
+            more |= {"batched": True}
         y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()
     else:   # (more ranks than instances)
