@@ -119,6 +119,24 @@ int marl_convert_layout_dev(marl_ctx* ctx, const double* src_dev, double* dst_de
 /* Test hook: y[i] = op(x[i]) with the kernels' own math primitives: op 0 log, 1 exp, 2 pow(x, e),
  * 3 reciprocal, 4 Fiadeiro-Veronis sigma(Pe = x, W = e).  Device pointers; asynchronous. */
 int marl_debug_math(marl_ctx* ctx, int op, const double* x_dev, double* y_dev, int64_t n, double e);
+/* Test hooks of the implicit path (marl_integrate_radau / marl_integrate_bdf below): one call of the finite-difference Jacobian and one
+ * factorisation with its solves, through the very functions an integration calls.  HOST pointers; single-instance contexts; both
+ * synchronise.
+ * marl_debug_num_jac: f0 = f(y) by the RHS kernel, then scipy's num_jac (common.py:268-451) at (y, f0) as the integrators run it.
+ *   y: float64[5N] field-major; threshold: num_jac's (the integrators pass atol); groups: int32[5N] or NULL, as for marl_integrate_radau;
+ *   factor_inout: float64[5N] field-major, the persistent step factors: read when first == 0 (first != 0: every factor starts from
+ *   sqrt(eps), as on the first Jacobian of a run), written with the adapted factors; J_out: float64[N][3][5][5], the device layout:
+ *   J_out[((i*3 + d)*5 + f)*5 + fp] = d rate(f, i) / d y(fp, i + d - 1); entries outside the pattern or the grid are 0.
+ * marl_debug_block_solve: factorises  mu I - jscale J  (J in the layout above) and solves nrhs right-hand sides one after another with
+ *   that ONE factorisation.  systems = 1: the real system only (BDF: mu_r = 1, jscale = c); 2: the real system and the complex one,
+ *   mu = mu_c_re + i mu_c_im (Radau: jscale = 1).  b_r / x_r: float64[nrhs][5N] CELL-MAJOR (unknown 5 i + f); b_c / x_c:
+ *   [nrhs][5N] complex, (re, im) interleaved, NULL with systems = 1.  The path (parallel cyclic reduction alone, cyclic reduction in
+ *   front of it, per-level / fused / tail launches) is chosen by the options radau_cr, radau_cr_small, radau_cr_small_min_n,
+ *   radau_fused_solve and radau_cr_tail exactly as for a run. */
+int marl_debug_num_jac(marl_ctx* ctx, const double* y, double threshold, const int32_t* groups, double* factor_inout, int first,
+                       double* J_out);
+int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jscale, double mu_r, double mu_c_re, double mu_c_im, int systems,
+                           int64_t nrhs, const double* b_r, const double* b_c, double* x_r, double* x_c);
 
 /* ---- fixed-step classical RK4 (BASELINE config 2; no counterpart in the reference, which only
  * remarks that forward Euler fails: README.md:9).  y is advanced in place by nsteps steps of dt. */

@@ -409,6 +409,49 @@ class LMAHeureuxPorosityDiff:
         res.y_final = y
         return res
 
+    # -- test hooks of the implicit path -------------------------------------------------------------------
+    def debug_num_jac(self, y, threshold, groups=None, factor=None):
+        """One finite-difference Jacobian as the implicit integrators evaluate it (marl_debug_num_jac).  ``factor`` None: the first
+        Jacobian of a run (every factor sqrt(eps)); else the factors the previous call returned.  Returns ``(J, factor)``: J in the
+        device layout (N, 3, 5, 5) - ``J[i, d, f, fp]`` = d rate(f, i) / d y(fp, i + d - 1) - and the adapted factors (5N, field-major)."""
+        y = self._host_state(y)
+        n, N = y.size, self.Depths.N
+        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        if grp is not None and grp.size != n:
+            raise ValueError(f"groups has {grp.size} entries, expected {n}")
+        fac = np.zeros(n) if factor is None else np.array(factor, dtype=np.float64).ravel()
+        if fac.size != n:
+            raise ValueError(f"factor has {fac.size} entries, expected {n}")
+        J = np.empty((N, 3, 5, 5))
+        self._check(self._lib.marl_debug_num_jac(self._ctx, _as_ptr(y), float(threshold), _as_ptr(grp) if grp is not None else None,
+                                                 _as_ptr(fac), 1 if factor is None else 0, _as_ptr(J)), "marl_debug_num_jac")
+        return J, fac
+
+    def debug_block_solve(self, J, b_r, b_c=None, mu_r=1.0, mu_c=0j, jscale=1.0):
+        """Factorise ``mu I - jscale J`` once and solve the right-hand sides with it (marl_debug_block_solve).  ``J``: (N, 3, 5, 5) as
+        :meth:`debug_num_jac` returns it; ``b_r``: (nrhs, 5N) cell-major, real system; ``b_c``: (nrhs, 5N) complex, the complex system
+        (None: the real system only, BDF's call).  Returns ``x_r`` or ``(x_r, x_c)``."""
+        N = self.Depths.N
+        J = np.ascontiguousarray(J, dtype=np.float64)
+        if J.size != 75 * N:
+            raise ValueError(f"J has {J.size} entries, expected {75 * N}")
+        b_r = np.ascontiguousarray(np.atleast_2d(b_r), dtype=np.float64)
+        if b_r.shape[1] != 5 * N:
+            raise ValueError(f"b_r has {b_r.shape[1]} columns, expected {5 * N}")
+        x_r = np.empty_like(b_r)
+        x_c = None
+        if b_c is not None:
+            b_c = np.ascontiguousarray(np.atleast_2d(b_c), dtype=np.complex128)
+            if b_c.shape != b_r.shape:
+                raise ValueError("b_c must have the shape of b_r")
+            x_c = np.empty_like(b_c)
+        mu_c = complex(mu_c)
+        self._check(self._lib.marl_debug_block_solve(self._ctx, _as_ptr(J), float(jscale), float(mu_r), mu_c.real, mu_c.imag,
+                                                     1 if b_c is None else 2, b_r.shape[0], _as_ptr(b_r),
+                                                     _as_ptr(b_c) if b_c is not None else None, _as_ptr(x_r),
+                                                     _as_ptr(x_c) if b_c is not None else None), "marl_debug_block_solve")
+        return x_r if b_c is None else (x_r, x_c)
+
     def integrate_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, layout=LAYOUT_FIELD_MAJOR, max_attempts=0):
         stats = MarlStats()
         rc = self._lib.marl_integrate_rk45_dev(self._ctx, C.c_void_p(y_dev_ptr), layout, float(t_span[0]), float(t_span[1]),

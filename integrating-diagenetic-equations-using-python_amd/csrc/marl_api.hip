@@ -2746,6 +2746,56 @@ extern "C" int marl_integrate_bdf(marl_ctx* ctx, double* y, double t0, double t1
                               t_events, max_events, max_attempts, stats);
 }
 
+// ---- test hooks of the implicit path: ONE Jacobian, ONE factorisation and its solves (tests/test_gpu_implicit_parts.py) -------
+// Both go through the functions radau_run / bdf_run call - radau_alloc, radau_num_jac, pcr_factor_launch, radau_solve - so that what
+// the tests see is what an integration runs, chosen by the same options.
+extern "C" int marl_debug_num_jac(marl_ctx* ctx, const double* y, double threshold, const int32_t* groups, double* factor_inout, int first,
+                                  double* J_out)
+{
+    if (!ctx || !y || !factor_inout || !J_out) return ctx ? fail(ctx, -1, "marl_debug_num_jac: invalid argument") : -1;
+    if (ctx->batch != 1 || ctx->halo > 0) return fail(ctx, -1, "marl_debug_num_jac: single-instance, whole-grid context required");
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    RadauWork w;
+    if (int rc = radau_alloc(ctx, w, groups)) return rc;
+    const size_t n = (size_t)NF * ctx->N;
+    HIP_OK(ctx, hipMemcpyAsync(w.y, y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!first) {
+        HIP_OK(ctx, hipMemcpyAsync(w.fac, factor_inout, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        w.have_factor = true;
+    }
+    if (int rc = launch_rhs(ctx, w.y, w.f, LAYOUT_FIELD_MAJOR)) return rc;
+    if (int rc = radau_num_jac(ctx, w, w.y, w.f, threshold)) return rc;
+    HIP_OK(ctx, hipMemcpyAsync(J_out, w.J, 15 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(factor_inout, w.fac, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jscale, double mu_r, double mu_c_re, double mu_c_im, int systems,
+                                      int64_t nrhs, const double* b_r, const double* b_c, double* x_r, double* x_c)
+{
+    if (!ctx || !J || !b_r || !x_r || nrhs < 0 || (systems != 1 && systems != 2) || (systems == 2 && (!b_c || !x_c)))
+        return ctx ? fail(ctx, -1, "marl_debug_block_solve: invalid argument") : -1;
+    if (ctx->batch != 1 || ctx->halo > 0) return fail(ctx, -1, "marl_debug_block_solve: single-instance, whole-grid context required");
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    RadauWork w;
+    if (int rc = radau_alloc(ctx, w, nullptr)) return rc;
+    if (!w.pcr) return fail(ctx, -1, "marl_debug_block_solve: the cyclic-reduction solver (radau_solver = 0) only");
+    const size_t n = (size_t)NF * ctx->N;
+    const bool both = systems == 2;
+    HIP_OK(ctx, hipMemcpyAsync(w.J, J, 15 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = pcr_factor_launch(ctx, w, mu_r, cplx{mu_c_re, mu_c_im}, jscale, systems)) return rc;
+    for (int64_t k = 0; k < nrhs; k++) {   // one factorisation, nrhs solves: a solve must leave the factors as it found them
+        HIP_OK(ctx, hipMemcpyAsync(w.rhs_r, b_r + k * n, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (both) HIP_OK(ctx, hipMemcpyAsync(w.rhs_c, b_c + k * 2 * n, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = radau_solve(ctx, w, both)) return rc;
+        HIP_OK(ctx, hipMemcpyAsync(x_r + k * n, w.rhs_r, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (both) HIP_OK(ctx, hipMemcpyAsync(x_c + k * 2 * n, w.rhs_c, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 // ---- a sweep of Radau instances (marl_radau_batch.h) -------------------------------------------------------------------------
 // The Radau sweep behind marl_sweep_radau_dev / _events_dev / _eval_dev.
 // t_events (host, may be NULL): [instance][7][max_events] root times of the seven monitors, located inside the sweep as the single run

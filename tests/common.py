@@ -69,6 +69,48 @@ INCR_TOL = {
     "rk45_baseline":               dict(rel=1e-6, ulps=2, measured=1.2e-7),
 }
 
+# The implicit path's parts (tests/test_gpu_implicit_parts.py; references and measure: tests/implicit_ref.py).
+# Jacobian values: |J_device - J_oracle| <= K eps max(|f0_r|, |f_r(y + h_c e_c)|) / |h_c| per entry; `measured` is the largest ratio over
+# the cases and chained calls of a state on an MI355X, K is 10 x that (the margin of INCR_TOL).  One row per state: eps |f_r| is the rounding
+# of a rate's RESULT; where the rate is a small remainder of cancelling terms (depleted: CC = 1 - 1e-9, where the kernel forms the calcite rate
+# as DC + CC (DA - DC) from terms of ~200) the two RHS implementations differ by the rounding of the TERMS, 1e4 .. 1e8 times more.
+IMPLICIT_JAC_K = {
+    # state                 bound           measured on MI355X: worst ratio over the state's cases
+    "flat":            dict(K=31.0, measured=3.01),
+    "zeros":           dict(K=4.9e5, measured=4.85e4),
+    "tiny":            dict(K=4.6e5, measured=4.59e4),
+    "depleted":        dict(K=2.9e9, measured=2.82e8),
+}
+# Block solves: the bound of a system is 100 x the E of the numpy restatement (the device's recurrences, its Gauss-Jordan block inverse
+# included) on that system, at least 1e-12 (implicit_ref.solve_bound) -
+# computed, not tabulated.  Recorded here per case (grid | reduction levels; 0 = PCR alone, -1 = automatic): `measured`, the device's
+# worst E over the case's paths and systems whose bound is below 1; `over_bound`, its worst E / bound over all systems.
+IMPLICIT_SOLVE_E = {
+    # case                  measured on MI355X
+    "N5|levels0":      dict(measured=1.7e-12, over_bound=0.013),
+    "N33|levels0":     dict(measured=1.0e-12, over_bound=0.017),
+    "N64|levels0":     dict(measured=2.0e-13, over_bound=0.021),
+    "N200|levels0":    dict(measured=6.4e-09, over_bound=0.059),
+    "N409|levels0":    dict(measured=1.7e-05, over_bound=0.13),
+    "N33|levels1":     dict(measured=8.2e-13, over_bound=0.083),
+    "N33|levels2":     dict(measured=6.4e-13, over_bound=0.083),
+    "N33|levels3":     dict(measured=4.1e-13, over_bound=0.083),
+    "N37|levels1":     dict(measured=5.2e-14, over_bound=0.011),
+    "N37|levels2":     dict(measured=5.1e-14, over_bound=0.022),
+    "N37|levels3":     dict(measured=5.1e-14, over_bound=0.023),
+    "N64|levels1":     dict(measured=1.9e-13, over_bound=0.021),
+    "N64|levels2":     dict(measured=1.9e-13, over_bound=0.011),
+    "N64|levels3":     dict(measured=2.1e-13, over_bound=0.016),
+    "N200|levels1":    dict(measured=6.1e-09, over_bound=0.061),
+    "N200|levels2":    dict(measured=6.3e-09, over_bound=0.058),
+    "N200|levels3":    dict(measured=6.3e-09, over_bound=0.057),
+    "N409|levels1":    dict(measured=2.1e-05, over_bound=0.058),
+    "N409|levels2":    dict(measured=2.9e-05, over_bound=0.063),
+    "N409|levels3":    dict(measured=6.2e-07, over_bound=0.055),
+    "N2049|levels-1":  dict(measured=1.7e-02, over_bound=0.034),
+    "N5003|levels-1":  dict(measured=8.3e-06, over_bound=0.034),
+}
+
 # fixed-step configurations at N >= 65 536 (the GPU tests run these; the sensitivity test perturbs the oracle at the same ones)
 RK4_FINE_CONFIGS = {
     "rk4_config2": dict(scenario="default", N=65536, nsteps=37, amplitude=0.01, dtf=0.25),
