@@ -21,6 +21,7 @@
 #include "marl_bdf.h"
 #include "marl_bdf_wg.h"
 #include "marl_bdf_batch.h"
+#include "marl_devbuf.h"
 
 using namespace marl;
 
@@ -464,21 +465,38 @@ int64_t marl_state_doubles(const marl_ctx* ctx, int layout) { return ctx ? state
 // ----------------------------------------------------------------------------------------------
 static inline int64_t inst_stride(const marl_ctx* ctx, int layout) { return state_doubles(ctx->slab.n_buf, layout); }
 
+static inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// "no batch": what every kernel with a trailing ZBatch takes by default - a single run is the cnt = 1 case of a batched launch
+static const ZBatch kNoBatch{0, nullptr, 0, 0, nullptr};
+
+// Field-major states -> their derivatives: `nstates` states one after another, for each of the `cnt` instances of `zb` (blockIdx.z).
+// const_stride 0: the states of an instance share its ONE model (stage states, finite-difference columns); 1: one model per state.
+// The stride between states is 5 n_buf doubles; on a whole-grid context (n_buf = N: marl_ctx_create) that is the 5 N of the implicit path.
+static int launch_rhs_fm(marl_ctx* ctx, const double* y, double* dydt, int64_t nstates, unsigned cnt = 1, const ZBatch& zb = kNoBatch,
+                         int const_stride = 0)
+{
+    const dim3 grid(blocks256(ctx->slab.n_buf), (unsigned)nstates, cnt);
+    const int64_t stride = inst_stride(ctx, LAYOUT_FIELD_MAJOR);
+    if (ctx->var_dphi)
+        hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, const_stride, zb);
+    else
+        hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, const_stride, zb);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
 // nstates > 0: that many states of the ONE model of the context, one after another (implicit path); 0: one state per instance
 static int launch_rhs(marl_ctx* ctx, const double* y, double* dydt, int layout, int64_t nstates = 0)
 {
-    const dim3 grid((unsigned)((ctx->slab.n_buf + 255) / 256), (unsigned)(nstates > 0 ? nstates : ctx->batch));
+    if (layout != LAYOUT_TILED) return launch_rhs_fm(ctx, y, dydt, nstates > 0 ? nstates : ctx->batch, 1, kNoBatch, nstates > 0 ? 0 : 1);
+    const dim3 grid(blocks256(ctx->slab.n_buf), (unsigned)(nstates > 0 ? nstates : ctx->batch));
     const int64_t stride = inst_stride(ctx, layout);
     const int cs = nstates > 0 ? 0 : 1;
-    if (ctx->var_dphi) {
-        if (layout == LAYOUT_TILED)
-            hipLaunchKernelGGL((rhs_kernel<LAYOUT_TILED, true>), grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, cs);
-        else
-            hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, cs);
-    } else if (layout == LAYOUT_TILED)
-        hipLaunchKernelGGL(rhs_kernel<LAYOUT_TILED>, grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, cs);
+    if (ctx->var_dphi)
+        hipLaunchKernelGGL((rhs_kernel<LAYOUT_TILED, true>), grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, cs);
     else
-        hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, cs);
+        hipLaunchKernelGGL(rhs_kernel<LAYOUT_TILED>, grid, dim3(256), 0, ctx->stream, y, dydt, ctx->dconsts, ctx->slab, stride, cs);
     LAUNCH_OK(ctx);
     return 0;
 }
@@ -1764,21 +1782,34 @@ inline void zc_arm(marl_ctx* ctx, int slot, int count = 1)
 {
     for (int i = 0; i < count; i++) reinterpret_cast<volatile uint64_t*>(ctx->zc_h)[slot + i] = kZcSentinel;
 }
+// the mapped, coherent host words ctx->zc_h / zc_d, allocated on first use (they live as long as the context)
+int zc_ensure(marl_ctx* ctx)
+{
+    if (ctx->zc_h) return 0;
+    HIP_OK(ctx, hipHostMalloc((void**)&ctx->zc_h, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_OK(ctx, hipHostGetDevicePointer((void**)&ctx->zc_d, ctx->zc_h, 0));
+    return 0;
+}
+// poll until arrived() holds; after 2^28 spins (~seconds: something is wrong with the stream) let the runtime say what, and look once more
+template <class Arrived>
+int zc_spin(marl_ctx* ctx, Arrived&& arrived, const char* never)
+{
+    for (int64_t spins = 0; !arrived();) {
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+        if (++spins > (int64_t)1 << 28) {
+            HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+            if (!arrived()) return fail(ctx, -3, "%s", never);
+        }
+    }
+    return 0;
+}
 inline int zc_wait(marl_ctx* ctx, int slot, int count = 1)
 {
     volatile uint64_t* p = reinterpret_cast<volatile uint64_t*>(ctx->zc_h);
-    for (int i = 0; i < count; i++) {
-        int64_t spins = 0;
-        while (p[slot + i] == kZcSentinel) {
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-            if (++spins > (int64_t)1 << 28) {   // ~seconds: something is wrong with the stream - let the runtime say what
-                HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-                if (p[slot + i] == kZcSentinel) return fail(ctx, -3, "implicit driver: a result word was never written");
-            }
-        }
-    }
+    for (int i = 0; i < count; i++)
+        if (int rc = zc_spin(ctx, [&] { return p[slot + i] != kZcSentinel; }, "implicit driver: a result word was never written")) return rc;
     return 0;
 }
 
@@ -1860,10 +1891,7 @@ int radau_alloc(marl_ctx* ctx, RadauWork& w, const int32_t* groups_host, int64_t
     w.small = (int32_t*)take((n + 1) / 2 + 1); w.groups = (int32_t*)take((n + 1) / 2 + 1); w.flags = (int32_t*)take(2);
     ctx->zc_on = false;
     if (instances == 1 && ctx->implicit_zero_copy) {
-        if (!ctx->zc_h) {
-            HIP_OK(ctx, hipHostMalloc((void**)&ctx->zc_h, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_OK(ctx, hipHostGetDevicePointer((void**)&ctx->zc_d, ctx->zc_h, 0));
-        }
+        if (int rc = zc_ensure(ctx)) return rc;
         HIP_OK(ctx, hipStreamSynchronize(ctx->stream));   // nothing of an earlier run may still write the words
         memset(ctx->zc_h, 0, 32 * sizeof(double));
         zc_arm(ctx, 0);
@@ -1895,7 +1923,6 @@ int radau_alloc(marl_ctx* ctx, RadauWork& w, const int32_t* groups_host, int64_t
     return 0;
 }
 
-inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 // workgroups of the norm kernels: one up to 8192 unknowns, then one per 4096, at most kRadauPartials
 inline int radau_norm_blocks(int64_t n) { return n <= 8192 ? 1 : (int)std::min<int64_t>(256, (n + 4095) / 4096); }
 
@@ -1903,52 +1930,55 @@ inline unsigned pcr_groups(int64_t rows) { return (unsigned)((rows + radau::PCR_
 
 // factorise  mu I - jscale J  for the real system (systems = 1) or the real and the complex one (2): block PCR over all N rows
 // (1 + ceil(log2 N) launches), or - large grids of single runs - cr_k levels of cyclic reduction and PCR over the rows that are left
-int pcr_factor_launch(marl_ctx* ctx, RadauWork& w, double mu_r, cplx mu_c, double jscale, int systems)
+// The `cnt` instances of `zb` (a sweep's work list; their mu then comes from their controllers) or, by default, the single run's arena.
+int pcr_factor_launch(marl_ctx* ctx, RadauWork& w, double mu_r, cplx mu_c, double jscale, int systems, unsigned cnt = 1, const ZBatch& zb = kNoBatch)
 {
     const int64_t N = ctx->N;
-    const ZBatch none{0, nullptr, 0, 0, nullptr};
     if (!w.cr_k) {
-        const dim3 grid(pcr_groups(N), systems);
+        const dim3 grid(pcr_groups(N), systems, cnt);
         for (int level = -1; level < w.nlevels; level++) {
-            hipLaunchKernelGGL(radau::pcr_factor_kernel, grid, dim3(256), 0, ctx->stream, w.J, N, level, mu_r, mu_c, w.Sr, w.Sc, none, jscale);
+            hipLaunchKernelGGL(radau::pcr_factor_kernel, grid, dim3(256), 0, ctx->stream, w.J, N, level, mu_r, mu_c, w.Sr, w.Sc, zb, jscale);
             LAUNCH_OK(ctx);
         }
         return 0;
     }
-    hipLaunchKernelGGL(radau::cr_init_kernel, dim3(pcr_groups((N + 1) / 2), systems), dim3(256), 0, ctx->stream, w.J, N, mu_r, mu_c, jscale, w.Cr, w.Cc);
+    hipLaunchKernelGGL(radau::cr_init_kernel, dim3(pcr_groups((N + 1) / 2), systems, cnt), dim3(256), 0, ctx->stream, w.J, N, mu_r, mu_c, jscale, w.Cr, w.Cc, zb);
     LAUNCH_OK(ctx);
     for (int l = 0; l < w.cr_k; l++) {
         const radau::CrShape sh{w.cr_n[l], w.cr_off[l], w.cr_n[l + 1], w.cr_off[l + 1]};
-        hipLaunchKernelGGL(radau::cr_reduce_kernel, dim3(pcr_groups(sh.n_next), systems), dim3(256), 0, ctx->stream, mu_r, mu_c, w.Cr, w.Cc, sh,
-                           l + 1 == w.cr_k ? 1 : 0, w.Sr, w.Sc);
+        hipLaunchKernelGGL(radau::cr_reduce_kernel, dim3(pcr_groups(sh.n_next), systems, cnt), dim3(256), 0, ctx->stream, mu_r, mu_c, w.Cr, w.Cc, sh,
+                           l + 1 == w.cr_k ? 1 : 0, w.Sr, w.Sc, zb);
         LAUNCH_OK(ctx);
     }
     const int64_t M = w.cr_n[w.cr_k];
     for (int level = 0; level < w.nlevels; level++) {   // (level -1 - blocks from J and their inverses - is what the last reduction left in set 0)
-        hipLaunchKernelGGL(radau::pcr_factor_kernel, dim3(pcr_groups(M), systems), dim3(256), 0, ctx->stream, w.J, M, level, mu_r, mu_c, w.Sr, w.Sc, none, jscale);
+        hipLaunchKernelGGL(radau::pcr_factor_kernel, dim3(pcr_groups(M), systems, cnt), dim3(256), 0, ctx->stream, w.J, M, level, mu_r, mu_c, w.Sr, w.Sc, zb, jscale);
         LAUNCH_OK(ctx);
     }
     return 0;
 }
 
-// PCR solve of M rows, in place in x_r (and, with `both`, x_c)
-int pcr_solve_launch(marl_ctx* ctx, RadauWork& w, int64_t M, bool both, double* x_r, cplx* x_c)
+// PCR solve of M rows, in place in x_r (and, with `both`, x_c).  One launch where the system fits a workgroup - with `plan` (k > 0: M = N
+// rows) that launch also runs the reduction levels in front of PCR and the back-substitution (crpcr_solve_all); plan.k == 0: PCR alone,
+// and the kernel reads neither the plan's levels nor w.Cr / w.Cc.
+int pcr_solve_launch(marl_ctx* ctx, RadauWork& w, int64_t M, bool both, double* x_r, cplx* x_c, const radau::CrPlan& plan, unsigned cnt = 1,
+                     const ZBatch& zb = kNoBatch)
 {
     const int64_t n = NF * M;
     if (n <= radau::PCR_FUSED_MAX && ctx->radau_fused_solve) {   // small systems: every level in one launch
-        hipLaunchKernelGGL(radau::pcr_solve_fused_kernel, dim3(1, both ? 2 : 1), dim3(radau::PCR_FUSED_THREADS), 0, ctx->stream, M, w.nlevels, 0, w.Sr, w.Sc,
-                           x_r, x_r, x_c, x_c);
+        hipLaunchKernelGGL(radau::pcr_solve_fused_kernel, dim3(1, both ? 2 : 1, cnt), dim3(radau::PCR_FUSED_THREADS), 0, ctx->stream, M, w.nlevels, 0, w.Sr, w.Sc,
+                           x_r, x_r, x_c, x_c, zb, plan, w.Cr, w.Cc);
         LAUNCH_OK(ctx);
         return 0;
     }
-    const dim3 grid(blocks256(n), both ? 2 : 1);
+    const dim3 grid(blocks256(n), both ? 2 : 1, cnt);
     // ping-pong: x -> b[0] -> b[1] -> ... ; the last launch (x = D^-1 b) writes back into x
     const double* in_r = x_r;
     const cplx* in_c = x_c;
     for (int level = 0; level <= w.nlevels; level++) {
         double* out_r = (level == w.nlevels) ? x_r : w.Sr.b[level & 1];
         cplx* out_c = (level == w.nlevels) ? x_c : w.Sc.b[level & 1];
-        hipLaunchKernelGGL(radau::pcr_solve_kernel, grid, dim3(256), 0, ctx->stream, M, level, w.nlevels, 0, w.Sr, w.Sc, in_r, out_r, in_c, out_c);
+        hipLaunchKernelGGL(radau::pcr_solve_kernel, grid, dim3(256), 0, ctx->stream, M, level, w.nlevels, 0, w.Sr, w.Sc, in_r, out_r, in_c, out_c, zb);
         LAUNCH_OK(ctx);
         in_r = out_r;
         in_c = out_c;
@@ -1970,25 +2000,23 @@ int radau_factor(marl_ctx* ctx, RadauWork& w, double mu_r, cplx mu_c)
     return pcr_factor_launch(ctx, w, mu_r, mu_c, 1.0, 2);
 }
 
-// solve in place: w.rhs_r (and, with `both`, w.rhs_c), cell-major
-int radau_solve(marl_ctx* ctx, RadauWork& w, bool both)
+// solve in place: w.rhs_r (and, with `both`, w.rhs_c), cell-major; of the single run, or of the `cnt` instances of `zb`
+int radau_solve(marl_ctx* ctx, RadauWork& w, bool both, unsigned cnt = 1, const ZBatch& zb = kNoBatch)
 {
     const int64_t N = ctx->N;
 #ifdef MARL_LAB_BLOCK_THOMAS
-    if (!w.pcr) {
+    if (!w.pcr && cnt == 1 && !zb.zstride) {
         hipLaunchKernelGGL(radau::solve_kernel, dim3(both ? 2 : 1), dim3(64), 0, ctx->stream, w.J, N, w.Dinv_r, w.Up_r, w.Dinv_c, w.Up_c, w.rhs_r, w.rhs_c,
                            both ? 3 : 1);
         LAUNCH_OK(ctx);
         return 0;
     }
 #endif
-    if (!w.cr_k) return pcr_solve_launch(ctx, w, N, both, w.rhs_r, w.rhs_c);
-    if (w.plan.k && ctx->radau_fused_solve) {   // small grids: reduction levels, compact PCR and back-substitution in one launch (crpcr_solve_all)
-        hipLaunchKernelGGL(radau::pcr_solve_fused_kernel, dim3(1, both ? 2 : 1), dim3(radau::PCR_FUSED_THREADS), 0, ctx->stream, N, w.nlevels, 0, w.Sr, w.Sc,
-                           w.rhs_r, w.rhs_r, w.rhs_c, w.rhs_c, ZBatch{0, nullptr, 0, 0, nullptr}, w.plan, w.Cr, w.Cc);
-        LAUNCH_OK(ctx);
-        return 0;
-    }
+    // plain PCR, or - small grids - reduction levels, compact PCR and back-substitution in one launch.  A sweep only ever gets here:
+    // radau_alloc gives it reduction levels only with the one-workgroup solve (small_cr needs one_wg, which for instances > 1 needs
+    // radau_fused_solve, and at most CR_WG_MAX_LEVELS of them: marl_set_option), and large_cr needs instances == 1.
+    if (!w.cr_k || (w.plan.k && ctx->radau_fused_solve)) return pcr_solve_launch(ctx, w, N, both, w.rhs_r, w.rhs_c, w.plan, cnt, zb);
+    if (cnt != 1 || zb.zstride) return fail(ctx, -3, "radau_solve: the level-by-level cyclic-reduction solve is for single runs");
     // right-hand sides down the reduction levels, the compact system by PCR, solutions back up (in place from level to level); from the
     // first level of at most CR_TAIL_ROWS rows on, all remaining levels in one launch each way (option radau_cr_tail = 0: level by level)
     const unsigned gy = both ? 2 : 1;
@@ -2020,7 +2048,7 @@ int radau_solve(marl_ctx* ctx, RadauWork& w, bool both)
         MARL_TAIL(cr_rhs_tail_kernel, nb)
     }
     const int64_t offk = w.cr_off[w.cr_k];
-    if (int rc = pcr_solve_launch(ctx, w, w.cr_n[w.cr_k], both, w.Cr.b + offk * NF, w.Cc.b + offk * NF)) return rc;
+    if (int rc = pcr_solve_launch(ctx, w, w.cr_n[w.cr_k], both, w.Cr.b + offk * NF, w.Cc.b + offk * NF, radau::CrPlan{})) return rc;
     if (tailJ > 0) {
         const int64_t rows = (int64_t)radau::CR_TAIL_TOP << tailJ;
         const unsigned nb = (unsigned)((tail.n[0] + rows - 1) / rows);
@@ -2036,25 +2064,33 @@ int radau_solve(marl_ctx* ctx, RadauWork& w, bool both)
     return 0;
 }
 
-// J = finite-difference Jacobian at (y, f0)  (num_jac; njev is the caller's)
-int radau_num_jac(marl_ctx* ctx, RadauWork& w, const double* y, const double* f0, double threshold)
+// J = finite-difference Jacobian at (y, f0)  (num_jac; njev is the caller's), of the single run or of the `cnt` instances of `zb`.
+// first: no step-size factors yet (a list with an action word - the Radau sweep's - takes that from each instance's controller)
+int radau_num_jac(marl_ctx* ctx, RadauWork& w, const double* y, const double* f0, double threshold, int first, unsigned cnt = 1,
+                  const ZBatch& zb = kNoBatch)
 {
     const int64_t N = ctx->N, n = NF * N;
-    hipLaunchKernelGGL(radau::fd_prepare_kernel, dim3(blocks256(n)), dim3(256), 0, ctx->stream, y, f0, w.fac, threshold, w.have_factor ? 0 : 1, w.groups,
-                       w.ng, n, w.h, w.yscale, w.YP);
+    const dim3 grid(blocks256(n), 1, cnt);
+    hipLaunchKernelGGL(radau::fd_prepare_kernel, grid, dim3(256), 0, ctx->stream, y, f0, w.fac, threshold, first, w.groups, w.ng, n, w.h, w.yscale, w.YP, zb);
     LAUNCH_OK(ctx);
-    w.have_factor = true;
-    if (int rc = launch_rhs(ctx, w.YP, w.FN, LAYOUT_FIELD_MAJOR, w.ng)) return rc;
-    hipLaunchKernelGGL(radau::fd_columns_kernel, dim3(blocks256(n)), dim3(256), 0, ctx->stream, y, f0, w.FN, w.groups, w.ng, N, w.fac, w.yscale, w.Jraw,
-                       w.maxdiff, w.scl, w.small, w.hnew, w.YP);
+    if (int rc = launch_rhs_fm(ctx, w.YP, w.FN, w.ng, cnt, zb)) return rc;
+    hipLaunchKernelGGL(radau::fd_columns_kernel, grid, dim3(256), 0, ctx->stream, y, f0, w.FN, w.groups, w.ng, N, w.fac, w.yscale, w.Jraw, w.maxdiff, w.scl,
+                       w.small, w.hnew, w.YP, zb);
     LAUNCH_OK(ctx);
     // second trial step of the columns whose difference drowned in rounding (all groups in one launch; the columns that
     // were fine are perturbed by 0 - scipy evaluates only the groups that need it, with the same numbers)
-    if (int rc = launch_rhs(ctx, w.YP, w.FN, LAYOUT_FIELD_MAJOR, w.ng)) return rc;
-    hipLaunchKernelGGL(radau::fd_finish_kernel, dim3(blocks256(n)), dim3(256), 0, ctx->stream, f0, w.FN, w.groups, N, w.fac, w.h, w.maxdiff, w.scl, w.small,
-                       w.hnew, w.Jraw, w.J);
+    if (int rc = launch_rhs_fm(ctx, w.YP, w.FN, w.ng, cnt, zb)) return rc;
+    hipLaunchKernelGGL(radau::fd_finish_kernel, grid, dim3(256), 0, ctx->stream, f0, w.FN, w.groups, N, w.fac, w.h, w.maxdiff, w.scl, w.small, w.hnew, w.Jraw,
+                       w.J, zb);
     LAUNCH_OK(ctx);
     return 0;
+}
+// ... of a single run, which keeps "first" itself
+int radau_num_jac_run(marl_ctx* ctx, RadauWork& w, const double* y, const double* f0, double threshold)
+{
+    const int first = w.have_factor ? 0 : 1;
+    w.have_factor = true;
+    return radau_num_jac(ctx, w, y, f0, threshold, first);
 }
 
 // err = the solved right-hand side; sum (err / scale)^2 -> w.out[0]
@@ -2198,7 +2234,7 @@ int radau_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_st
     double S_h_abs = first_step, S_h_abs_old = -1, S_err_old = -1;
     const double newton_tol = std::fmax(10 * radau::EPS / rtol, std::fmin(0.03, std::sqrt(rtol)));
     if (!ctx->zc_on) HIP_OK(ctx, hipMemsetAsync(w.flags, 0, sizeof(int32_t) * 2, ctx->stream));
-    if (int rc = radau_num_jac(ctx, w, w.y, w.f, atol)) return rc;
+    if (int rc = radau_num_jac_run(ctx, w, w.y, w.f, atol)) return rc;
     st->njev = 1;
     bool current_jac = true, have_lu = false, have_sol = false;
     RadauDense dense = {t0, 0};
@@ -2300,7 +2336,7 @@ int radau_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_st
                 n_iter = (k < NEWTON_MAXITER ? k : NEWTON_MAXITER - 1) + 1;
                 if (!converged) {
                     if (current_jac) break;
-                    if (int rc = radau_num_jac(ctx, w, w.y, w.f, atol)) return rc;
+                    if (int rc = radau_num_jac_run(ctx, w, w.y, w.f, atol)) return rc;
                     st->njev++;
                     current_jac = true;
                     have_lu = false;
@@ -2365,7 +2401,7 @@ int radau_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_st
         } else if (int rc = launch_rhs(ctx, w.ynew, w.fnew, LAYOUT_FIELD_MAJOR)) return rc;
         st->nfev++;
         if (recompute_jac) {
-            if (int rc = radau_num_jac(ctx, w, w.ynew, w.fnew, atol)) return rc;
+            if (int rc = radau_num_jac_run(ctx, w, w.ynew, w.fnew, atol)) return rc;
             st->njev++;
             current_jac = true;
         } else {
@@ -2491,7 +2527,7 @@ int bdf_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_step
     const double newton_tol = std::fmax(10 * radau::EPS / rtol, std::fmin(0.03, std::sqrt(rtol)));
     if (!ctx->zc_on) HIP_OK(ctx, hipMemsetAsync(w.flags, 0, sizeof(int32_t) * 2, ctx->stream));
     // jac_wrapped(t0, y0): f = fun_single(t, y) (not counted; the same values as w.f), J by finite differences
-    if (int rc = radau_num_jac(ctx, w, w.y, w.f, atol)) return rc;
+    if (int rc = radau_num_jac_run(ctx, w, w.y, w.f, atol)) return rc;
     st->njev = 1;
     hipLaunchKernelGGL(bdf::init_D_kernel, gn, b256, 0, ctx->stream, w.y, w.f, S_h_abs, n, D);
     LAUNCH_OK(ctx);
@@ -2617,7 +2653,7 @@ int bdf_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_step
                     if (current_jac) break;
                     // J = self.jac(t_new, y_predict): f = fun_single(t_new, y_predict) - not counted
                     if (int rc = launch_rhs(ctx, ypred, w.fnew, LAYOUT_FIELD_MAJOR)) return rc;
-                    if (int rc = radau_num_jac(ctx, w, ypred, w.fnew, atol)) return rc;
+                    if (int rc = radau_num_jac_run(ctx, w, ypred, w.fnew, atol)) return rc;
                     st->njev++;
                     have_lu = false;
                     current_jac = true;
@@ -2759,12 +2795,9 @@ extern "C" int marl_debug_num_jac(marl_ctx* ctx, const double* y, double thresho
     if (int rc = radau_alloc(ctx, w, groups)) return rc;
     const size_t n = (size_t)NF * ctx->N;
     HIP_OK(ctx, hipMemcpyAsync(w.y, y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (!first) {
-        HIP_OK(ctx, hipMemcpyAsync(w.fac, factor_inout, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        w.have_factor = true;
-    }
+    if (!first) HIP_OK(ctx, hipMemcpyAsync(w.fac, factor_inout, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (int rc = launch_rhs(ctx, w.y, w.f, LAYOUT_FIELD_MAJOR)) return rc;
-    if (int rc = radau_num_jac(ctx, w, w.y, w.f, threshold)) return rc;
+    if (int rc = radau_num_jac(ctx, w, w.y, w.f, threshold, first ? 1 : 0)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(J_out, w.J, 15 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipMemcpyAsync(factor_inout, w.fac, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2794,6 +2827,53 @@ extern "C" int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jsc
     }
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+// ---- what the sweeps of Radau and of BDF instances share: the host's end of a cycle, and the end of a sweep ----------------------
+// The lengths of this cycle's work lists -> hcounts[0 .. ncounts).  Zero-copy mode: a one-thread kernel copies them into mapped host
+// words, zeroes them and writes cycle + 1 behind them, which the host polls for; else a copy, a memset and a synchronise.
+// The caller zeroes dcounts before the first cycle; from then on they are zero again, in stream order, right after they were read, and
+// nothing between here and the next cycle's controllers touches them - the same as zeroing them at the top of that cycle.
+static int sweep_read_counts(marl_ctx* ctx, int32_t* dcounts, int ncounts, int64_t cycle, int32_t* hcounts)
+{
+    if (ctx->implicit_zero_copy) {
+        if (int rc = zc_ensure(ctx)) return rc;
+        volatile int32_t* words = reinterpret_cast<volatile int32_t*>(ctx->zc_h + 16);
+        const int32_t seq = (int32_t)(cycle + 1);
+        if (cycle == 0) words[radau::L_COUNT] = 0;   // (an earlier sweep's last sequence number; nothing of it still runs)
+        hipLaunchKernelGGL(radau::publish_counts_kernel, dim3(1), dim3(1), 0, ctx->stream, dcounts, reinterpret_cast<int32_t*>(ctx->zc_d + 16), seq);
+        LAUNCH_OK(ctx);
+        if (int rc = zc_spin(ctx, [&] { return words[radau::L_COUNT] == seq; }, "sweep: the work-list lengths never arrived")) return rc;
+        for (int i = 0; i < ncounts; i++) hcounts[i] = words[i];
+    } else {
+        HIP_OK(ctx, hipMemcpyAsync(hcounts, dcounts, sizeof(int32_t) * ncounts, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (int i = 0; i < ncounts; i++)   // (every instance adds at most one to a count: a longer list is a corrupted word, not a grid.z)
+        if ((uint32_t)hcounts[i] > (uint64_t)ctx->batch) return fail(ctx, -3, "sweep: a work list is longer than the sweep");
+    return 0;
+}
+
+template <class Ctl>   // radau::RadauCtl, bdf::BdfCtl
+static void ctl_to_stats(const Ctl& c, marl_stats& st)
+{
+    memset(&st, 0, sizeof st);
+    st.nfev = c.nfev; st.njev = c.njev; st.nlu = c.nlu; st.n_accepted = c.n_acc; st.n_rejected = c.n_rej;
+    st.status = c.status; st.t = c.t; st.h_next = c.S_h_abs;
+    for (int e = 0; e < 7; e++) { st.event_value[e] = c.g[e]; st.n_events[e] = c.n_events[e]; }
+}
+
+// the arena of instance 0 as the one-workgroup-per-instance kernels take it (marl_radau_wg.h)
+static radau::WgWork wg_work_of(const RadauWork& w, int64_t zs)
+{
+    radau::WgWork ww{};
+    ww.y = w.y; ww.f = w.f; ww.fnew = w.fnew; ww.ynew = w.ynew; ww.err = w.err; ww.yerr = w.yerr; ww.yold = w.yold; ww.scale = w.scale; ww.tmp = w.tmp;
+    ww.Z = w.Z; ww.W = w.W; ww.F = w.F; ww.Q = w.Q; ww.YS = w.YS; ww.fac = w.fac; ww.h = w.h; ww.yscale = w.yscale; ww.maxdiff = w.maxdiff; ww.scl = w.scl;
+    ww.hnew = w.hnew; ww.Jraw = w.Jraw; ww.YP = w.YP; ww.FN = w.FN; ww.J = w.J; ww.rhs_r = w.rhs_r; ww.rhs_c = w.rhs_c; ww.small = w.small; ww.groups = w.groups;
+    ww.Sr = w.Sr; ww.Sc = w.Sc; ww.ng = w.ng; ww.nlevels = w.nlevels; ww.zs = zs;
+    ww.plan = w.plan; ww.Cr = w.Cr; ww.Cc = w.Cc;
+    return ww;
 }
 
 // ---- a sweep of Radau instances (marl_radau_batch.h) -------------------------------------------------------------------------
@@ -2826,35 +2906,27 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     int64_t zs = 0;
     if (int rc = radau_alloc(ctx, w, groups, B, &zs)) return rc;
     using radau::RadauCtl;
-    // controllers, monitors records, work lists + their counts
-    RadauCtl* dctl = nullptr;
-    double* drec = nullptr;
-    int32_t* dcounts = nullptr;   // [L_COUNT] then lists [L_COUNT][B]
-    HIP_OK(ctx, hipMalloc((void**)&dctl, sizeof(RadauCtl) * B));
-    HIP_OK(ctx, hipMalloc((void**)&drec, sizeof(double) * NQ * B));
-    HIP_OK(ctx, hipMalloc((void**)&dcounts, sizeof(int32_t) * (size_t)(radau::L_COUNT * (B + 1))));
+    std::vector<RadauCtl> hctl((size_t)B);   // (before the device buffers: they wait for the stream when they go, this must still be there)
+    // controllers, monitors records, work lists + their counts; every return from here on frees them (DevBuf)
+    DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream), b_rec_dense(ctx->stream), b_tev(ctx->stream), b_teval(ctx->stream), b_wg(ctx->stream);
+    HIP_OK(ctx, b_ctl.alloc(sizeof(RadauCtl) * B));
+    HIP_OK(ctx, b_rec.alloc(sizeof(double) * NQ * B));
+    HIP_OK(ctx, b_counts.alloc(sizeof(int32_t) * (size_t)(radau::L_COUNT * (B + 1))));
+    RadauCtl* const dctl = b_ctl.as<RadauCtl>();
+    double* const drec = b_rec.as<double>();
+    int32_t* const dcounts = b_counts.as<int32_t>();   // [L_COUNT] then lists [L_COUNT][B]
     int32_t* dlists = dcounts + radau::L_COUNT;
-    double *drec_dense = nullptr, *dtev = nullptr;   // event root finding: monitors of the dense-output states, the root times
-    if (locate) {
-        HIP_OK(ctx, hipMalloc((void**)&drec_dense, sizeof(double) * NQ * B));
-        HIP_OK(ctx, hipMalloc((void**)&dtev, sizeof(double) * (size_t)(7 * max_events) * B));
-        HIP_OK(ctx, hipMemsetAsync(drec_dense, 0, sizeof(double) * NQ * B, ctx->stream));
-        HIP_OK(ctx, hipMemsetAsync(dtev, 0xff, sizeof(double) * (size_t)(7 * max_events) * B, ctx->stream));   // (all bits set: NaN)
+    if (locate) {   // event root finding: monitors of the dense-output states, the root times
+        HIP_OK(ctx, b_rec_dense.alloc(sizeof(double) * NQ * B));
+        HIP_OK(ctx, b_tev.alloc(sizeof(double) * (size_t)(7 * max_events) * B));
+        HIP_OK(ctx, hipMemsetAsync(b_rec_dense.p, 0, sizeof(double) * NQ * B, ctx->stream));
+        HIP_OK(ctx, hipMemsetAsync(b_tev.p, 0xff, sizeof(double) * (size_t)(7 * max_events) * B, ctx->stream));   // (all bits set: NaN)
     }
-    double* dteval = nullptr;      // the sample times, for the controllers
-    if (frames) {                  // (pageable host memory: the copy has left the caller's array when the call returns)
-        HIP_OK(ctx, hipMalloc((void**)&dteval, sizeof(double) * (size_t)n_eval));
-        HIP_OK(ctx, hipMemcpyAsync(dteval, t_eval, sizeof(double) * (size_t)n_eval, hipMemcpyHostToDevice, ctx->stream));
+    if (frames) {   // the sample times, for the controllers (pageable host memory: the copy has left the caller's array when the call returns)
+        HIP_OK(ctx, b_teval.alloc(sizeof(double) * (size_t)n_eval));
+        HIP_OK(ctx, hipMemcpyAsync(b_teval.p, t_eval, sizeof(double) * (size_t)n_eval, hipMemcpyHostToDevice, ctx->stream));
     }
-    unsigned* wg_next = nullptr;   // one-workgroup-per-instance paths: the instance queue, then the list of instances a pass visits [2 B]
-    auto cleanup = [&]() {
-        (void)hipFree(dctl); (void)hipFree(drec); (void)hipFree(dcounts);
-        if (drec_dense) (void)hipFree(drec_dense);
-        if (dtev) (void)hipFree(dtev);
-        if (dteval) (void)hipFree(dteval);
-        if (wg_next) (void)hipFree(wg_next);
-    };
-    std::vector<RadauCtl> hctl((size_t)B);
+    double *const drec_dense = b_rec_dense.as<double>(), *const dtev = b_tev.as<double>(), *const dteval = b_teval.as<double>();
     for (auto& c : hctl) {
         memset(&c, 0, sizeof c);
         c.t_bound = t1; c.rtol = rtol; c.atol = atol; c.max_attempts = max_attempts;
@@ -2864,12 +2936,10 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
         c.locate_events = locate ? 1 : 0; c.max_events = max_events;
         c.n_eval = n_eval;
     }
-    if (hipMemcpyAsync(dctl, hctl.data(), sizeof(RadauCtl) * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { cleanup(); return fail(ctx, -3, "copy failed"); }
-    if (hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-        cleanup();
-        return fail(ctx, -3, "state copy failed");
-    }
-    (void)hipMemsetAsync(drec, 0, sizeof(double) * NQ * B, ctx->stream);
+    HIP_OK(ctx, hipMemcpyAsync(dctl, hctl.data(), sizeof(RadauCtl) * B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemsetAsync(drec, 0, sizeof(double) * NQ * B, ctx->stream));
+    HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));   // (sweep_read_counts keeps them zero between cycles)
     const double S6 = std::sqrt(6.0);
     const double E3[3] = {(-13 - 7 * S6) / 3, (-13 + 7 * S6) / 3, -1.0 / 3};
     const radau::P33 P = {{{13.0 / 3 + 7 * S6 / 3, -23.0 / 3 - 22 * S6 / 3, 10.0 / 3 + 5 * S6},
@@ -2880,26 +2950,10 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     auto Z = [&](int which) { return ZBatch{zs, act0, (int64_t)sizeof(RadauCtl), ~0, dlists + (int64_t)which * B}; };
     const dim3 b256(256);
     const unsigned gx = blocks256(n), gc = blocks256(N);
-    const cplx c0 = {0, 0};
     const int64_t nbm = std::min<int64_t>((N + 255) / 256, 1024);
-    if (int rc = ensure_part(ctx, (size_t)(nbm * B))) { cleanup(); return rc; }
-    int rc_out = 0;
+    if (int rc = ensure_part(ctx, (size_t)(nbm * B))) return rc;
     int32_t* hcounts = reinterpret_cast<int32_t*>(ctx->rd_host);
-    volatile int32_t* zc_words = nullptr;
-    if (ctx->implicit_zero_copy) {
-        if (!ctx->zc_h) {
-            if (hipHostMalloc((void**)&ctx->zc_h, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&ctx->zc_d, ctx->zc_h, 0) != hipSuccess) { cleanup(); return fail(ctx, -3, "host allocation failed"); }
-        }
-        zc_words = reinterpret_cast<volatile int32_t*>(ctx->zc_h + 16);
-        zc_words[radau::L_COUNT] = 0;
-    }
     using namespace radau;
-#define RB_OK()                                                                                       \
-    do {                                                                                              \
-        hipError_t e_ = hipGetLastError();                                                            \
-        if (e_ != hipSuccess) { cleanup(); return fail(ctx, -100 - (int)e_, "kernel launch failed: %s", hipGetErrorString(e_)); } \
-    } while (0)
     // Sweeps of small grids (5 N <= PCR_FUSED_MAX: the reference's N = 200), option radau_sweep_wg:
     //   1            HYBRID: one persistent workgroup per instance runs everything of the instance that is sequential and small (step
     //                logic, Newton iterations, error estimates, accepted steps, event roots - marl_radau_wg.h) and hands it back for
@@ -2911,20 +2965,16 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     //   0            the launch-per-action cycle (larger grids always take it).
     const int wg_mode = (n <= PCR_FUSED_MAX) ? (int)ctx->radau_sweep_wg : 0;
     const bool use_wg = wg_mode == 2 && !locate && !frames;
-    WgWork ww{};
+    const WgWork ww = wg_mode ? wg_work_of(w, zs) : WgWork{};
     if (wg_mode) {
         if (!ctx->cus) {
             hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) { cleanup(); return fail(ctx, -3, "device properties unavailable"); }
+            HIP_OK(ctx, hipGetDeviceProperties(&prop, ctx->device));
             ctx->cus = prop.multiProcessorCount;
         }
-        ww.y = w.y; ww.f = w.f; ww.fnew = w.fnew; ww.ynew = w.ynew; ww.err = w.err; ww.yerr = w.yerr; ww.yold = w.yold; ww.scale = w.scale; ww.tmp = w.tmp;
-        ww.Z = w.Z; ww.W = w.W; ww.F = w.F; ww.Q = w.Q; ww.YS = w.YS; ww.fac = w.fac; ww.h = w.h; ww.yscale = w.yscale; ww.maxdiff = w.maxdiff; ww.scl = w.scl;
-        ww.hnew = w.hnew; ww.Jraw = w.Jraw; ww.YP = w.YP; ww.FN = w.FN; ww.J = w.J; ww.rhs_r = w.rhs_r; ww.rhs_c = w.rhs_c; ww.small = w.small; ww.groups = w.groups;
-        ww.Sr = w.Sr; ww.Sc = w.Sc; ww.ng = w.ng; ww.nlevels = w.nlevels; ww.zs = zs;
-        ww.plan = w.plan; ww.Cr = w.Cr; ww.Cc = w.Cc;
-        if (hipMalloc((void**)&wg_next, sizeof(unsigned) * (size_t)(2 + 2 * B)) != hipSuccess) { wg_next = nullptr; cleanup(); return fail(ctx, -3, "allocation failed"); }
+        HIP_OK(ctx, b_wg.alloc(sizeof(unsigned) * (size_t)(2 + 2 * B)));
     }
+    unsigned* const wg_next = b_wg.as<unsigned>();   // one-workgroup-per-instance paths: the instance queue, then the list of instances a pass visits [2 B]
     // nrun < 0: the pass visits every instance; else the instances run_list[0 .. nrun) (those the last pass handed back)
     auto launch_wg = [&](int hybrid, int64_t nrun) {
         (void)hipMemsetAsync(wg_next, 0, sizeof(unsigned), ctx->stream);
@@ -2943,56 +2993,39 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     };
     if (use_wg) {
         launch_wg(0, -1);
-        RB_OK();
+        LAUNCH_OK(ctx);
     }
     int64_t wg_nrun = -1;
     const bool hybrid = wg_mode == 1 || wg_mode == 3 || (wg_mode == 2 && (locate || frames));
     const int hybrid_kind = wg_mode == 3 ? 2 : 1;   // 2: Jacobians stay in the workgroup, only factorisations come back to the host cycle
     for (int64_t cycle = 0; !use_wg; cycle++) {
         // the controllers advance every instance to its next piece of work and sort the instances into work lists; the host
-        // reads the list lengths (one small copy + synchronisation per cycle) and launches each kind of work over its list only
-        if (!zc_words || cycle == 0) (void)hipMemsetAsync(dcounts, 0, sizeof(int32_t) * L_COUNT, ctx->stream);   // (publish_counts_kernel zeroes them afterwards)
+        // reads the list lengths (sweep_read_counts) and launches each kind of work over its list only
         if (hybrid) launch_wg(hybrid_kind, wg_nrun);   // every running instance up to its next Jacobian / factorisation (or its end)
         else hipLaunchKernelGGL(radau_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, drec_dense, dtev, dteval);
-        RB_OK();
-        if (zc_words) {   // the list lengths through polled host memory
-            hipLaunchKernelGGL(publish_counts_kernel, dim3(1), dim3(1), 0, ctx->stream, dcounts, reinterpret_cast<int32_t*>(ctx->zc_d + 16), (int32_t)(cycle + 1));
-            RB_OK();
-            int64_t spins = 0;
-            while (zc_words[L_COUNT] != (int32_t)(cycle + 1)) {
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-                if (++spins > (int64_t)1 << 28) {
-                    if (hipStreamSynchronize(ctx->stream) != hipSuccess || zc_words[L_COUNT] != (int32_t)(cycle + 1)) { cleanup(); return fail(ctx, -3, "sweep: the work-list lengths never arrived"); }
-                }
-            }
-            for (int i = 0; i < L_COUNT; i++) hcounts[i] = zc_words[i];
-        } else {
-            (void)hipMemcpyAsync(hcounts, dcounts, sizeof(int32_t) * L_COUNT, hipMemcpyDeviceToHost, ctx->stream);
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) { cleanup(); return fail(ctx, -3, "synchronize failed"); }
-        }
+        LAUNCH_OK(ctx);
+        if (int rc = sweep_read_counts(ctx, dcounts, L_COUNT, cycle, hcounts)) return rc;
         if (hcounts[L_RUNNING] == 0) break;
         if (hybrid) {   // the instances handed back in this pass are the ones the next pass visits (after their Jacobian / factorisation below)
             const int64_t nj = hcounts[L_JAC], nl = hcounts[L_LU];
             int32_t* run_list = reinterpret_cast<int32_t*>(wg_next + 2);
-            if (nj) (void)hipMemcpyAsync(run_list, dlists + (int64_t)L_JAC * B, sizeof(int32_t) * (size_t)nj, hipMemcpyDeviceToDevice, ctx->stream);
-            if (nl) (void)hipMemcpyAsync(run_list + nj, dlists + (int64_t)L_LU * B, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToDevice, ctx->stream);
+            if (nj) HIP_OK(ctx, hipMemcpyAsync(run_list, dlists + (int64_t)L_JAC * B, sizeof(int32_t) * (size_t)nj, hipMemcpyDeviceToDevice, ctx->stream));
+            if (nl) HIP_OK(ctx, hipMemcpyAsync(run_list + nj, dlists + (int64_t)L_LU * B, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToDevice, ctx->stream));
             wg_nrun = nj + nl;
         }
         const unsigned nR = (unsigned)hcounts[L_RHS1], nA = (unsigned)hcounts[L_ACCEPT], nJ = (unsigned)hcounts[L_JAC], nL = (unsigned)hcounts[L_LU],
                        nN = (unsigned)hcounts[L_NEWTON], nE = (unsigned)hcounts[L_ERR], nD = (unsigned)hcounts[L_DENSE], nF = (unsigned)hcounts[L_FRAME];
         if (nF) {   // t_eval samples inside the accepted step: its dense output into the instances' frames (no monitors: nothing reads a frame)
             hipLaunchKernelGGL(frame_eval_batch_kernel, dim3(gx, 1, nF), b256, 0, ctx->stream, w.Q, w.yold, n, y_eval_dev, n_eval, Z(L_FRAME));
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
         if (nD) {   // event root finding: the dense output of the accepted step at the abscissa Brent asks for, and that state's monitors
             hipLaunchKernelGGL(dense_eval_batch_kernel, dim3(gx, 1, nD), b256, 0, ctx->stream, w.Q, w.yold, n, w.tmp, Z(L_DENSE));
-            RB_OK();
+            LAUNCH_OK(ctx);
             hipLaunchKernelGGL(monitors_kernel<LAYOUT_FIELD_MAJOR>, dim3((unsigned)nbm, (unsigned)B), b256, 0, ctx->stream, w.tmp, ctx->dconsts, ctx->slab, zs / 8, ctx->part);
-            RB_OK();
+            LAUNCH_OK(ctx);
             hipLaunchKernelGGL(reduce_records_kernel, dim3((unsigned)B), b256, 0, ctx->stream, ctx->part, nbm, drec_dense);
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
         if (nR) {   // a single state -> its derivative: y -> f (start), y + err -> tmp (second error estimate), y_new -> f_new (accepted step)
             if (ctx->var_dphi)
@@ -3001,67 +3034,28 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
             else
                 hipLaunchKernelGGL((rhs_pick_kernel<LAYOUT_FIELD_MAJOR, false>), dim3(gc, 1, nR), b256, 0, ctx->stream, w.y, w.f, w.yerr, w.tmp, w.ynew, w.fnew, ctx->dconsts,
                                    ctx->slab, Z(L_RHS1));
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
         if (nA) {
             hipLaunchKernelGGL(accept_kernel, dim3(gx, 1, nA), b256, 0, ctx->stream, w.Z, w.Q, w.y, w.yold, w.ynew, w.f, w.fnew, n, P, Z(L_ACCEPT));
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
         if ((nA || cycle == 0) && !hybrid) {   // monitors of every instance's y (read by the controllers after the start and after each accepted step)
             hipLaunchKernelGGL(monitors_kernel<LAYOUT_FIELD_MAJOR>, dim3((unsigned)nbm, (unsigned)B), b256, 0, ctx->stream, w.y, ctx->dconsts, ctx->slab, zs / 8, ctx->part);
-            RB_OK();
+            LAUNCH_OK(ctx);
             hipLaunchKernelGGL(reduce_records_kernel, dim3((unsigned)B), b256, 0, ctx->stream, ctx->part, nbm, drec);
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
-        if (nJ) {   // finite-difference Jacobian at (y, f)
-            hipLaunchKernelGGL(fd_prepare_kernel, dim3(gx, 1, nJ), b256, 0, ctx->stream, w.y, w.f, w.fac, atol, 0, w.groups, w.ng, n, w.h, w.yscale, w.YP, Z(L_JAC));
-            RB_OK();
-            for (int pass = 0; pass < 2; pass++) {
-                if (ctx->var_dphi)
-                    hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), dim3(gc, (unsigned)w.ng, nJ), b256, 0, ctx->stream, w.YP, w.FN, ctx->dconsts, ctx->slab, n, 0, Z(L_JAC));
-                else
-                    hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, dim3(gc, (unsigned)w.ng, nJ), b256, 0, ctx->stream, w.YP, w.FN, ctx->dconsts, ctx->slab, n, 0, Z(L_JAC));
-                RB_OK();
-                if (pass == 0)
-                    hipLaunchKernelGGL(fd_columns_kernel, dim3(gx, 1, nJ), b256, 0, ctx->stream, w.y, w.f, w.FN, w.groups, w.ng, N, w.fac, w.yscale, w.Jraw, w.maxdiff, w.scl,
-                                       w.small, w.hnew, w.YP, Z(L_JAC));
-                else
-                    hipLaunchKernelGGL(fd_finish_kernel, dim3(gx, 1, nJ), b256, 0, ctx->stream, w.f, w.FN, w.groups, N, w.fac, w.h, w.maxdiff, w.scl, w.small, w.hnew, w.Jraw,
-                                       w.J, Z(L_JAC));
-                RB_OK();
-            }
-        }
-        if (nL && w.cr_k) {   // cyclic reduction in front of PCR (small grids; radau_alloc): levels 0 .. cr_k - 1, then PCR on the rows that are left
-            hipLaunchKernelGGL(cr_init_kernel, dim3(pcr_groups((N + 1) / 2), 2, nL), b256, 0, ctx->stream, w.J, N, 0.0, c0, 1.0, w.Cr, w.Cc, Z(L_LU));
-            RB_OK();
-            for (int l = 0; l < w.cr_k; l++) {
-                const CrShape sh{w.cr_n[l], w.cr_off[l], w.cr_n[l + 1], w.cr_off[l + 1]};
-                hipLaunchKernelGGL(cr_reduce_kernel, dim3(pcr_groups(sh.n_next), 2, nL), b256, 0, ctx->stream, 0.0, c0, w.Cr, w.Cc, sh, l + 1 == w.cr_k ? 1 : 0, w.Sr, w.Sc,
-                                   Z(L_LU));
-                RB_OK();
-            }
-            const int64_t M = w.cr_n[w.cr_k];
-            for (int level = 0; level < w.nlevels; level++) {
-                hipLaunchKernelGGL(pcr_factor_kernel, dim3(pcr_groups(M), 2, nL), b256, 0, ctx->stream, w.J, M, level, 0.0, c0, w.Sr, w.Sc, Z(L_LU));
-                RB_OK();
-            }
-        } else
-        if (nL)
-            for (int level = -1; level < w.nlevels; level++) {
-                hipLaunchKernelGGL(pcr_factor_kernel, dim3((unsigned)((N + PCR_CELLS_PER_BLOCK - 1) / PCR_CELLS_PER_BLOCK), 2, nL), b256, 0, ctx->stream, w.J, N, level, 0.0, c0,
-                                   w.Sr, w.Sc, Z(L_LU));
-                RB_OK();
-            }
+        if (nJ)   // finite-difference Jacobian at (y, f); which instances have step-size factors already, their controllers say
+            if (int rc = radau_num_jac(ctx, w, w.y, w.f, atol, 0, nJ, Z(L_JAC))) return rc;
+        if (nL)   // both factorisations, mu from the controllers (small grids: cyclic reduction in front of PCR - radau_alloc)
+            if (int rc = pcr_factor_launch(ctx, w, 0.0, cplx{0, 0}, 1.0, 2, nL, Z(L_LU))) return rc;
         if (nN) {   // one Newton iteration
             hipLaunchKernelGGL(newton_begin_batch_kernel, dim3(gx, 1, nN), b256, 0, ctx->stream, w.y, w.Q, w.yold, n, w.scale, w.Z, w.W, w.YS, Z(L_NEWTON));
-            RB_OK();
-            if (ctx->var_dphi)
-                hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), dim3(gc, 3, nN), b256, 0, ctx->stream, w.YS, w.F, ctx->dconsts, ctx->slab, n, 0, Z(L_NEWTON));
-            else
-                hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, dim3(gc, 3, nN), b256, 0, ctx->stream, w.YS, w.F, ctx->dconsts, ctx->slab, n, 0, Z(L_NEWTON));
-            RB_OK();
+            LAUNCH_OK(ctx);
+            if (int rc = launch_rhs_fm(ctx, w.YS, w.F, 3, nN, Z(L_NEWTON))) return rc;
             hipLaunchKernelGGL(newton_rhs_batch_kernel, dim3(gx, 1, nN), b256, 0, ctx->stream, w.F, w.W, N, w.rhs_r, w.rhs_c, dctl, Z(L_NEWTON));
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
         for (int which = 0; which < 2; which++) {   // 0: both systems of the Newton iteration; 1: the real system of the error estimate
             const unsigned cnt = which == 0 ? nN : nE;
@@ -3069,59 +3063,32 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
             const ZBatch zb = Z(which == 0 ? L_NEWTON : L_ERR);
             if (which == 1) {
                 hipLaunchKernelGGL(error_rhs_batch_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, w.f, w.tmp, w.Z, w.y, N, E3[0], E3[1], E3[2], w.rhs_r, w.ynew, zb);
-                RB_OK();
+                LAUNCH_OK(ctx);
             }
-            if (n <= PCR_FUSED_MAX && ctx->radau_fused_solve) {
-                hipLaunchKernelGGL(pcr_solve_fused_kernel, dim3(1, which == 0 ? 2 : 1, cnt), dim3(PCR_FUSED_THREADS), 0, ctx->stream, N, w.nlevels, 0, w.Sr, w.Sc, w.rhs_r,
-                                   w.rhs_r, w.rhs_c, w.rhs_c, zb, w.plan, w.Cr, w.Cc);
-                RB_OK();
-            } else {
-                const double* in_r = w.rhs_r;
-                const cplx* in_c = w.rhs_c;
-                for (int level = 0; level <= w.nlevels; level++) {
-                    double* out_r = (level == w.nlevels) ? w.rhs_r : w.Sr.b[level & 1];
-                    cplx* out_c = (level == w.nlevels) ? w.rhs_c : w.Sc.b[level & 1];
-                    hipLaunchKernelGGL(pcr_solve_kernel, dim3(gx, which == 0 ? 2 : 1, cnt), b256, 0, ctx->stream, N, level, w.nlevels, 0, w.Sr, w.Sc, in_r, out_r, in_c, out_c, zb);
-                    RB_OK();
-                    in_r = out_r;
-                    in_c = out_c;
-                }
-            }
+            if (int rc = radau_solve(ctx, w, which == 0, cnt, zb)) return rc;
             if (which == 0)
                 hipLaunchKernelGGL(newton_update_batch_kernel, dim3(1, 1, cnt), dim3(1024), 0, ctx->stream, w.y, w.rhs_r, w.rhs_c, w.scale, N, w.W, w.Z, w.YS, dctl, zb);
             else
                 hipLaunchKernelGGL(error_norm_batch_kernel, dim3(1, 1, cnt), dim3(1024), 0, ctx->stream, w.rhs_r, w.y, w.ynew, N, w.err, w.yerr, dctl, zb);
-            RB_OK();
+            LAUNCH_OK(ctx);
         }
     }
-#undef RB_OK
-    // results
-    if (hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-        rc_out = fail(ctx, -3, "state copy failed");
-    if (rc_out == 0 && hipMemcpyAsync(hctl.data(), dctl, sizeof(RadauCtl) * B, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc_out = fail(ctx, -3, "copy failed");
-    if (rc_out == 0 && locate && hipMemcpyAsync(t_events, dtev, sizeof(double) * (size_t)(7 * max_events) * B, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        rc_out = fail(ctx, -3, "copy failed");
-    if (rc_out == 0 && hipStreamSynchronize(ctx->stream) != hipSuccess) rc_out = fail(ctx, -3, "synchronize failed");
-    if (rc_out == 0)
-        for (int64_t b = 0; b < B; b++) {
-            const RadauCtl& c = hctl[(size_t)b];
-            marl_stats& st = stats[b];
-            memset(&st, 0, sizeof st);
-            st.nfev = c.nfev; st.njev = c.njev; st.nlu = c.nlu; st.n_accepted = c.n_acc; st.n_rejected = c.n_rej;
-            st.status = c.status; st.t = c.t; st.h_next = c.S_h_abs;
-            for (int e = 0; e < 7; e++) { st.event_value[e] = c.g[e]; st.n_events[e] = c.n_events[e]; }
-            if (frames) n_done[b] = c.fr_next;
-        }
-    if (rc_out == 0 && t1 == t0 && frames && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as the single run gives it
+    // results (the synchronise is also what the sweep's buffers wait for before they go)
+    HIP_OK(ctx, hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(hctl.data(), dctl, sizeof(RadauCtl) * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (locate) HIP_OK(ctx, hipMemcpyAsync(t_events, dtev, sizeof(double) * (size_t)(7 * max_events) * B, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < B; b++) {
+        ctl_to_stats(hctl[(size_t)b], stats[b]);
+        if (frames) n_done[b] = hctl[(size_t)b].fr_next;
+    }
+    if (t1 == t0 && frames && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as the single run gives it
         const size_t row = sizeof(double) * (size_t)n;
-        if (hipMemcpy2DAsync(y_eval_dev, row * (size_t)n_eval, y_dev, row, row, (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc_out = fail(ctx, -3, "state copy failed");
-        else
-            for (int64_t b = 0; b < B; b++) n_done[b] = 1;
+        HIP_OK(ctx, hipMemcpy2DAsync(y_eval_dev, row * (size_t)n_eval, y_dev, row, row, (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t b = 0; b < B; b++) n_done[b] = 1;
     }
-    cleanup();
-    return rc_out;
+    return 0;
 }
 
 extern "C" int marl_sweep_radau_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
@@ -3145,8 +3112,9 @@ extern "C" int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0
 
 // ---- a sweep of BDF instances (marl_bdf_batch.h, marl_bdf_ctl.h) ---------------------------------------------------------------
 // BDF.__init__ of every instance (f, the first Jacobian, D, the monitors) in front of the cycle, then the cycle of sweep_radau's
-// launch-per-action mode: controllers, the list lengths through polled host memory (or a copy: implicit_zero_copy = 0), then every
-// kind of work over its list in the order marl_bdf_ctl.h documents.  No kernel waits for another workgroup.
+// launch-per-action mode: controllers, the list lengths (sweep_read_counts), then every kind of work over its list in the order
+// marl_bdf_ctl.h documents - Jacobians and right-hand sides through the launchers the single runs use, the factorisation and the
+// one-workgroup solve through the kernels of marl_bdf_batch.h.  No kernel waits for another workgroup.
 static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
                      int64_t max_attempts, marl_stats* stats)
 {
@@ -3169,155 +3137,84 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     if (w.cr_k && !w.plan.k) return fail(ctx, -1, "marl_sweep_bdf_dev: the cyclic-reduction levels of this context do not fit the one-launch solve");
     using bdf::BdfCtl;
     using namespace bdf;
-    BdfCtl* dctl = nullptr;
-    double* drec = nullptr;
-    int32_t* dcounts = nullptr;   // [L_COUNT] then lists [BL_COUNT][B]
-    HIP_OK(ctx, hipMalloc((void**)&dctl, sizeof(BdfCtl) * B));
-    auto cleanup = [&]() {
-        (void)hipFree(dctl);
-        if (drec) (void)hipFree(drec);
-        if (dcounts) (void)hipFree(dcounts);
-    };
-    if (hipMalloc((void**)&drec, sizeof(double) * NQ * B) != hipSuccess || hipMalloc((void**)&dcounts, sizeof(int32_t) * (size_t)(radau::L_COUNT + BL_COUNT * B)) != hipSuccess) {
-        cleanup();
-        return fail(ctx, -3, "allocation failed");
-    }
-    int32_t* dlists = dcounts + radau::L_COUNT;
-    std::vector<BdfCtl> hctl((size_t)B);
+    std::vector<BdfCtl> hctl((size_t)B);   // (before the device buffers: they wait for the stream when they go, this must still be there)
     for (auto& c : hctl) bdfctl::bdf_control_init(c, t0, t1, first_step, rtol, atol, max_attempts);
-#define SB_FAIL(...)               \
-    do {                           \
-        cleanup();                 \
-        return fail(ctx, __VA_ARGS__); \
-    } while (0)
-#define SB_OK()                                                                                   \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) SB_FAIL(-100 - (int)e_, "kernel launch failed: %s", hipGetErrorString(e_)); \
-    } while (0)
-    if (hipMemcpyAsync(dctl, hctl.data(), sizeof(BdfCtl) * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) SB_FAIL(-3, "copy failed");
-    if (hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-        SB_FAIL(-3, "state copy failed");
-    if (hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream) != hipSuccess) SB_FAIL(-3, "memset failed");
+    DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream);   // every return from here on frees them
+    HIP_OK(ctx, b_ctl.alloc(sizeof(BdfCtl) * B));
+    HIP_OK(ctx, b_rec.alloc(sizeof(double) * NQ * B));
+    HIP_OK(ctx, b_counts.alloc(sizeof(int32_t) * (size_t)(radau::L_COUNT + BL_COUNT * B)));
+    BdfCtl* const dctl = b_ctl.as<BdfCtl>();
+    double* const drec = b_rec.as<double>();
+    int32_t* const dcounts = b_counts.as<int32_t>();   // [L_COUNT] then lists [BL_COUNT][B]
+    int32_t* dlists = dcounts + radau::L_COUNT;
+    HIP_OK(ctx, hipMemcpyAsync(dctl, hctl.data(), sizeof(BdfCtl) * B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));   // (sweep_read_counts keeps them zero between cycles)
     bdf::Vec6 gamma = {};
     for (int k = 1; k <= bdf::MAX_ORDER; k++) gamma.v[k] = gamma.v[k - 1] + 1.0 / k;
     double* D = w.Z;
     double* f = w.Z0;
     double *ypred = w.Q, *psi = w.Q + n, *d = w.Q + 2 * n;
     const dim3 b256(256);
-    const unsigned gx = blocks256(n), gc = blocks256(N);
+    const unsigned gx = blocks256(n);
     const int64_t nbm = std::min<int64_t>((N + 255) / 256, 1024);
-    if (int rc = ensure_part(ctx, (size_t)(nbm * B))) { cleanup(); return rc; }
+    if (int rc = ensure_part(ctx, (size_t)(nbm * B))) return rc;
     auto L = [&](int which) { return BdfBatch{zs, dctl, dlists + (int64_t)which * B}; };
     auto Z = [&](int which) { return ZBatch{zs, nullptr, 0, 0, dlists + (int64_t)which * B}; };
-    // the finite-difference Jacobian at (yj, fj) of the instances of zb (cnt of them); first: no step-size factors yet (num_jac)
-    auto jacobian = [&](const double* yj, const double* fj, int first, unsigned cnt, const ZBatch& zb) -> int {
-        hipLaunchKernelGGL(radau::fd_prepare_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, yj, fj, w.fac, atol, first, w.groups, w.ng, n, w.h, w.yscale, w.YP, zb);
-        for (int pass = 0; pass < 2; pass++) {
-            if (ctx->var_dphi)
-                hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), dim3(gc, (unsigned)w.ng, cnt), b256, 0, ctx->stream, w.YP, w.FN, ctx->dconsts, ctx->slab, n, 0, zb);
-            else
-                hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, dim3(gc, (unsigned)w.ng, cnt), b256, 0, ctx->stream, w.YP, w.FN, ctx->dconsts, ctx->slab, n, 0, zb);
-            if (pass == 0)
-                hipLaunchKernelGGL(radau::fd_columns_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, yj, fj, w.FN, w.groups, w.ng, N, w.fac, w.yscale, w.Jraw, w.maxdiff,
-                                   w.scl, w.small, w.hnew, w.YP, zb);
-            else
-                hipLaunchKernelGGL(radau::fd_finish_kernel, dim3(gx, 1, cnt), b256, 0, ctx->stream, fj, w.FN, w.groups, N, w.fac, w.h, w.maxdiff, w.scl, w.small, w.hnew,
-                                   w.Jraw, w.J, zb);
-        }
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    };
-    auto rhs_of = [&](const double* src, double* dst, unsigned cnt, const ZBatch& zb) {
-        if (ctx->var_dphi)
-            hipLaunchKernelGGL((rhs_kernel<LAYOUT_FIELD_MAJOR, true>), dim3(gc, 1, cnt), b256, 0, ctx->stream, src, dst, ctx->dconsts, ctx->slab, n, 0, zb);
-        else
-            hipLaunchKernelGGL(rhs_kernel<LAYOUT_FIELD_MAJOR>, dim3(gc, 1, cnt), b256, 0, ctx->stream, src, dst, ctx->dconsts, ctx->slab, n, 0, zb);
-    };
-    // BDF.__init__ of every instance: f = fun(t0, y0); J = jac(t0, y0); D[0] = y0, D[1] = f h; g = events(t0, y0)
+    // BDF.__init__ of every instance: f = fun(t0, y0); J = jac(t0, y0) (no step-size factors yet); D[0] = y0, D[1] = f h; g = events(t0, y0)
     {
         const ZBatch all{zs, nullptr, 0, 0, nullptr};
-        rhs_of(w.y, w.f, (unsigned)B, all);
-        SB_OK();
-        if (jacobian(w.y, w.f, 1, (unsigned)B, all)) SB_FAIL(-3, "kernel launch failed (Jacobian)");
+        if (int rc = launch_rhs_fm(ctx, w.y, w.f, 1, (unsigned)B, all)) return rc;
+        if (int rc = radau_num_jac(ctx, w, w.y, w.f, atol, 1, (unsigned)B, all)) return rc;
         hipLaunchKernelGGL(init_D_batch_kernel, dim3(gx, 1, (unsigned)B), b256, 0, ctx->stream, w.y, w.f, n, D, BdfBatch{zs, dctl, nullptr});
-        SB_OK();
+        LAUNCH_OK(ctx);
         hipLaunchKernelGGL(monitors_kernel<LAYOUT_FIELD_MAJOR>, dim3((unsigned)nbm, (unsigned)B), b256, 0, ctx->stream, w.y, ctx->dconsts, ctx->slab, zs / 8, ctx->part);
-        SB_OK();
+        LAUNCH_OK(ctx);
         hipLaunchKernelGGL(reduce_records_kernel, dim3((unsigned)B), b256, 0, ctx->stream, ctx->part, nbm, drec);
-        SB_OK();
+        LAUNCH_OK(ctx);
     }
     int32_t* hcounts = reinterpret_cast<int32_t*>(ctx->rd_host);
-    volatile int32_t* zc_words = nullptr;
-    if (ctx->implicit_zero_copy) {
-        if (!ctx->zc_h) {
-            if (hipHostMalloc((void**)&ctx->zc_h, 32 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&ctx->zc_d, ctx->zc_h, 0) != hipSuccess) SB_FAIL(-3, "host allocation failed");
-        }
-        zc_words = reinterpret_cast<volatile int32_t*>(ctx->zc_h + 16);
-        zc_words[radau::L_COUNT] = 0;
-    }
     constexpr int64_t kStallCycles = 1000;   // cycles without any instance moving (pc, attempts, status): every cycle moves each running one
     int64_t stalled = 0;
     for (int64_t cycle = 0;; cycle++) {
         hipLaunchKernelGGL(bdf_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists);
-        SB_OK();
-        if (zc_words) {   // the list lengths through polled host memory (the kernel zeroes the counts for the next cycle)
-            hipLaunchKernelGGL(radau::publish_counts_kernel, dim3(1), dim3(1), 0, ctx->stream, dcounts, reinterpret_cast<int32_t*>(ctx->zc_d + 16), (int32_t)(cycle + 1));
-            SB_OK();
-            int64_t spins = 0;
-            while (zc_words[radau::L_COUNT] != (int32_t)(cycle + 1)) {
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-                if (++spins > (int64_t)1 << 28) {
-                    if (hipStreamSynchronize(ctx->stream) != hipSuccess || zc_words[radau::L_COUNT] != (int32_t)(cycle + 1)) SB_FAIL(-3, "sweep: the work-list lengths never arrived");
-                }
-            }
-            for (int i = 0; i < BL_COUNT; i++) hcounts[i] = zc_words[i];
-        } else {
-            (void)hipMemcpyAsync(hcounts, dcounts, sizeof(int32_t) * BL_COUNT, hipMemcpyDeviceToHost, ctx->stream);
-            (void)hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream);
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) SB_FAIL(-3, "synchronize failed");
-        }
+        LAUNCH_OK(ctx);
+        if (int rc = sweep_read_counts(ctx, dcounts, BL_COUNT, cycle, hcounts)) return rc;
         const unsigned nA = (unsigned)hcounts[BL_ACCEPT], nC = (unsigned)hcounts[BL_CHANGE_D], nJ = (unsigned)hcounts[BL_JAC], nL = (unsigned)hcounts[BL_LU],
                        nS = (unsigned)hcounts[BL_SOLVE];
-        if (nA > B || nC > B || nJ > B || nL > B || nS > B) SB_FAIL(-3, "sweep: a work list is longer than the sweep");
         stalled = hcounts[BL_PROGRESS] ? 0 : stalled + 1;
-        if (stalled >= kStallCycles) {
-            (void)hipStreamSynchronize(ctx->stream);
-            SB_FAIL(-3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
-        }
+        if (stalled >= kStallCycles)
+            return fail(ctx, -3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
         if (nA) {   // the accepted step: differences, y = y_new, the norms of the order selection
             hipLaunchKernelGGL(accept_norms_batch_kernel, dim3(1, 1, nA), dim3(1024), 0, ctx->stream, D, d, w.ynew, n, w.y, L(BL_ACCEPT));
-            SB_OK();
+            LAUNCH_OK(ctx);
         }
         if (nC) {
             hipLaunchKernelGGL(change_D_batch_kernel, dim3(gx, 1, nC), b256, 0, ctx->stream, D, n, L(BL_CHANGE_D));
-            SB_OK();
+            LAUNCH_OK(ctx);
         }
         if (nJ) {   // J = jac(t_new, y_predict), with f = fun(t_new, y_predict) (not counted)
-            rhs_of(ypred, w.fnew, nJ, Z(BL_JAC));
-            SB_OK();
-            if (jacobian(ypred, w.fnew, 0, nJ, Z(BL_JAC))) SB_FAIL(-3, "kernel launch failed (Jacobian)");
+            if (int rc = launch_rhs_fm(ctx, ypred, w.fnew, 1, nJ, Z(BL_JAC))) return rc;
+            if (int rc = radau_num_jac(ctx, w, ypred, w.fnew, atol, 0, nJ, Z(BL_JAC))) return rc;
         }
         if (nL) {   // LU of I - c J (pcr_factor_launch, real system)
             if (w.cr_k) {
                 hipLaunchKernelGGL(cr_init_batch_kernel, dim3(pcr_groups((N + 1) / 2), 1, nL), b256, 0, ctx->stream, w.J, N, w.Cr, L(BL_LU));
-                SB_OK();
+                LAUNCH_OK(ctx);
                 for (int l = 0; l < w.cr_k; l++) {
                     const radau::CrShape sh{w.cr_n[l], w.cr_off[l], w.cr_n[l + 1], w.cr_off[l + 1]};
                     hipLaunchKernelGGL(cr_reduce_batch_kernel, dim3(pcr_groups(sh.n_next), 1, nL), b256, 0, ctx->stream, w.Cr, sh, l + 1 == w.cr_k ? 1 : 0, w.Sr, L(BL_LU));
-                    SB_OK();
+                    LAUNCH_OK(ctx);
                 }
                 const int64_t M = w.cr_n[w.cr_k];
                 for (int level = 0; level < w.nlevels; level++) {
                     hipLaunchKernelGGL(pcr_factor_batch_kernel, dim3(pcr_groups(M), 1, nL), b256, 0, ctx->stream, w.J, M, level, w.Sr, L(BL_LU));
-                    SB_OK();
+                    LAUNCH_OK(ctx);
                 }
             } else {
                 for (int level = -1; level < w.nlevels; level++) {
                     hipLaunchKernelGGL(pcr_factor_batch_kernel, dim3(pcr_groups(N), 1, nL), b256, 0, ctx->stream, w.J, N, level, w.Sr, L(BL_LU));
-                    SB_OK();
+                    LAUNCH_OK(ctx);
                 }
             }
         }
@@ -3328,28 +3225,16 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
             else
                 hipLaunchKernelGGL(solve_batch_kernel<false>, dim3(1, 1, nS), dim3(radau::WG_THREADS), 0, ctx->stream, D, gamma, ypred, psi, w.scale, w.ynew, d, f, N, w.nlevels,
                                    w.Sr, ctx->dconsts, w.plan, w.Cr, L(BL_SOLVE));
-            SB_OK();
+            LAUNCH_OK(ctx);
         }
         if (hcounts[BL_RUNNING] == 0) break;   // (the last cycle's accepted steps are launched above)
     }
-#undef SB_OK
-#undef SB_FAIL
-    int rc_out = 0;
-    if (hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-        rc_out = fail(ctx, -3, "state copy failed");
-    if (rc_out == 0 && hipMemcpyAsync(hctl.data(), dctl, sizeof(BdfCtl) * B, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc_out = fail(ctx, -3, "copy failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc_out == 0) rc_out = fail(ctx, -3, "synchronize failed");
-    if (rc_out == 0)
-        for (int64_t b = 0; b < B; b++) {
-            const BdfCtl& c = hctl[(size_t)b];
-            marl_stats& st = stats[b];
-            memset(&st, 0, sizeof st);
-            st.nfev = c.nfev; st.njev = c.njev; st.nlu = c.nlu; st.n_accepted = c.n_acc; st.n_rejected = c.n_rej;
-            st.status = c.status; st.t = c.t; st.h_next = c.S_h_abs;
-            for (int e = 0; e < 7; e++) { st.event_value[e] = c.g[e]; st.n_events[e] = c.n_events[e]; }
-        }
-    cleanup();
-    return rc_out;
+    // results (the synchronise is also what the sweep's buffers wait for before they go)
+    HIP_OK(ctx, hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(hctl.data(), dctl, sizeof(BdfCtl) * B, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < B; b++) ctl_to_stats(hctl[(size_t)b], stats[b]);
+    return 0;
 }
 
 extern "C" int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,

@@ -395,6 +395,41 @@ def test_radau_sweep_workgroup_paths_against_the_launch_path(torch_cuda_radau):
                 np.testing.assert_allclose(out[2][0][b], out[0][0][b], rtol=0.1, atol=0.01)
 
 
+def test_radau_launch_per_action_sweep_is_the_same_by_copy_and_level_by_level(torch_cuda_radau):
+    """The launch-per-action sweep (radau_sweep_wg = 0) gives the same bits however the host learns the work-list lengths
+    (implicit_zero_copy 1: polled host memory, 0: copy + synchronise - same kernels, same order) and whether a solve is one launch or one
+    per level (radau_fused_solve 3 / 0: at N = 64 both are plain PCR with the same row arithmetic, as
+    test_radau_fused_solve_is_bit_identical_to_per_level_solve asserts for single runs)."""
+    torch = torch_cuda_radau
+    from dataclasses import asdict
+    from marlpde_amd.LHeureux_model import LMAHeureuxPorosityDiff
+    from marlpde_amd.parameters import Map_Scenario
+    N = 64
+    base = asdict(Map_Scenario()) | {"N": N}
+    inst = [{"Phi0": 0.6, "PhiIni": 0.5, "PhiNR": 0.6}, {"Phi0": 0.8, "PhiIni": 0.8, "PhiNR": 0.8},
+            {"Phi0": 0.5, "PhiIni": 0.5, "PhiNR": 0.5, "k3": 0.01, "k4": 0.01}]
+    y0 = np.stack([np.concatenate([np.full(N, (base | d)[k]) for k in ("CAIni", "CCIni", "cCaIni", "cCO3Ini", "PhiIni")]) for d in inst])
+    out = {}
+    for zero_copy, fused in ((1, 3), (0, 3), (1, 0)):
+        eq = LMAHeureuxPorosityDiff.from_scenario(base, device=0, instances=inst)
+        eq.use_stream(torch.cuda.current_stream().cuda_stream)
+        eq.set_option("radau_sweep_wg", 0)
+        eq.set_option("implicit_zero_copy", zero_copy)
+        eq.set_option("radau_fused_solve", fused)
+        yd = torch.from_numpy(y0).cuda()
+        try:
+            res = eq.sweep_radau_device(yd.data_ptr(), (0.0, 0.3), 1e-6, 1e-3, 1e-3)
+        finally:
+            eq.close()
+        out[zero_copy, fused] = (yd.cpu().numpy(), [(r.nfev, r.njev, r.nlu, r.n_accepted, r.n_rejected, r.status, r.t_reached) + tuple(r.n_events)
+                                                    for r in res])
+        print((zero_copy, fused), out[zero_copy, fused][1])
+    assert all(s[5] == 0 and s[6] == 0.3 for s in out[1, 3][1])
+    for other in ((0, 3), (1, 0)):
+        assert np.array_equal(out[other][0], out[1, 3][0]), other
+        assert out[other][1] == out[1, 3][1], other
+
+
 def test_radau_sweep_of_512_scenarios_properties(torch_cuda_radau):
     """A sweep the size bench.py reports (512 scenarios over Phi0 x PhiIni x k3 = k4, N = 200, to T*): every instance reaches T* with
     finite fields (positive porosity and concentrations), its statistics are in the range single runs show, and a sample of instances agrees with the same scenario

@@ -191,6 +191,27 @@ def test_arena_and_context_reuse(torch_cuda):
         assert np.array_equal(a, other) and [stats_of(r) for r in ra] == [stats_of(r) for r in ro]
 
 
+def test_list_lengths_by_copy_or_by_polled_host_memory(torch_cuda):
+    """How the host learns a cycle's work-list lengths (option implicit_zero_copy: 1 = a kernel publishes them into mapped host words the
+    host polls, 0 = a copy and a synchronise) changes neither the kernels nor their order: states and statistics are equal bit for bit."""
+    from marlpde_amd.LHeureux_model import LMAHeureuxPorosityDiff
+    N, inst = 64, [S[0], S[6], S[1]]
+    out = {}
+    for zc in (0, 1):
+        eq = LMAHeureuxPorosityDiff.from_scenario(base_of(N), device=0, instances=inst)
+        eq.use_stream(torch_cuda.cuda.current_stream().cuda_stream)
+        eq.set_option("implicit_zero_copy", zc)
+        try:
+            out[zc] = sweep(torch_cuda, N, inst, (0.0, 0.3), eq=eq)
+        finally:
+            eq.close()
+    print("copy:  ", [stats_of(r) for r in out[0][1]])
+    print("polled:", [stats_of(r) for r in out[1][1]])
+    assert all(r.status == 0 and r.t_reached == 0.3 for r in out[1][1])
+    assert np.array_equal(out[0][0], out[1][0])
+    assert [stats_of(r) for r in out[0][1]] == [stats_of(r) for r in out[1][1]]
+
+
 def test_run_sweep_bdf_batched_driver(torch_cuda):
     from marlpde_amd.sweep import HipSweepEngine, initial_states, product_grid, run_sweep_bdf
     N = 200
