@@ -246,11 +246,22 @@ int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1
  * in place; stats[b]: nfev / njev / nlu / n_accepted / n_rejected / status / t / h_next as scipy counts them, n_events the monitors'
  * sign changes over accepted steps, event_value the monitors of the final state.  t1 == t0: no step, the state is untouched,
  * status 0, nfev = njev = 1 (BDF.__init__).  A failed solve is a status, not an error.  Synchronises.
- * It does NOT: locate root times or write t_eval frames (BDF's dense output is built after the order change; both are
- * marl_integrate_bdf's), take grids whose solve does not fit one workgroup (5 N <= 2048, N <= 409; larger: -1, use marl_integrate_bdf),
- * or keep an instance in a persistent workgroup. */
+ * It does NOT: locate root times (marl_integrate_bdf's; t_eval frames: marl_sweep_bdf_eval_dev below), take grids whose solve does
+ * not fit one workgroup (5 N <= 2048, N <= 409; larger: -1, use marl_integrate_bdf), or keep an instance in a persistent workgroup. */
 int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                        const int32_t* groups, int64_t max_attempts, marl_stats* stats);
+/* The same sweep with t_eval: the time series the reference keeps of every run (marlpde/Evolve_scenario.py:104-109) with the BDF
+ * method of its Solver.  As in scipy the samples never change the steps (ivp.py:706-723); they are read from the dense output scipy
+ * builds once _step_impl has returned (bdf.py:452-478): D[:order + 1], the order and the step size as they stand after the accepted
+ * step's order / step-size selection and before the next step rescales D.  An accepted step that covers samples costs the instance
+ * one more cycle; state and statistics are those of the same call without samples.
+ * t_eval, y_eval_dev, n_done: as for marl_sweep_radau_eval_dev (frames [n_instances][n_eval][5N]; n_done[b] = the samples with
+ * t_eval[k] <= the time instance b reached, also when it ended with status -1 or 2; its later frames are not touched).
+ * n_eval = 0 (t_eval, y_eval_dev, n_done may then be NULL) is marl_sweep_bdf_dev.  t1 == t0: no step is taken and no frame is written,
+ * as marl_integrate_bdf writes none.  Synchronises. */
+int marl_sweep_bdf_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                            const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                            int64_t* n_done, marl_stats* stats);
 
 /* ---- 1-D domain decomposition of ONE large grid (BASELINE config 5; the reference never decomposes the depth
  * axis).  One process per GPU holds a slab [g_begin, g_end) of the N_global cells in a slab context; the host

@@ -3115,20 +3115,24 @@ extern "C" int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0
 // launch-per-action mode: controllers, the list lengths (sweep_read_counts), then every kind of work over its list in the order
 // marl_bdf_ctl.h documents - Jacobians and right-hand sides through the launchers the single runs use, the factorisation and the
 // one-workgroup solve through the kernels of marl_bdf_batch.h.  No kernel waits for another workgroup.
+// t_eval (host, n_eval times), y_eval_dev (device, [instance][n_eval][5N]), n_done (host, [instance]): the samples inside every accepted
+// step by the step's dense output, built as bdf_run builds it - after the order / step-size selection, before the next step rescales D
+// (A_SAMPLE, marl_bdf_ctl.h); n_eval = 0: none, and the same cycles.  A run with t1 == t0 takes no step and writes no frame.
 static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
-                     int64_t max_attempts, marl_stats* stats)
+                     int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, marl_stats* stats)
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_bdf_dev: invalid argument") : -1;
+    if (n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done))) return fail(ctx, -1, "marl_sweep_bdf_eval_dev: invalid argument");
     if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_bdf_dev: whole-grid context required");
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "bdf: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "bdf: `first_step` exceeds bounds");
-    if (!(rtol > 0) || !(atol >= 0)) return fail(ctx, -1, "bdf: tolerances must be positive");
+    if (int rc = check_ivp_args(ctx, "bdf", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
+    const bool frames = n_eval > 0;
     if (ctx->batch > 65535) return fail(ctx, -1, "marl_sweep_bdf_dev: at most 65535 instances per call");
     const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
     if (n > radau::PCR_FUSED_MAX)
         return fail(ctx, -1, "marl_sweep_bdf_dev: a solve must fit one workgroup (N <= %d); use marl_integrate_bdf (run_sweep_bdf without batched) for larger grids",
                     (int)(radau::PCR_FUSED_MAX / NF));
     if (ctx->radau_solver != 0) return fail(ctx, -1, "marl_sweep_bdf_dev: needs the PCR solver (option radau_solver = 0)");
+    if (n_done) memset(n_done, 0, sizeof(int64_t) * (size_t)B);
     HIP_OK(ctx, hipSetDevice(ctx->device));
     rtol = clamp_rtol(rtol);
     RadauWork w;
@@ -3139,7 +3143,9 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     using namespace bdf;
     std::vector<BdfCtl> hctl((size_t)B);   // (before the device buffers: they wait for the stream when they go, this must still be there)
     for (auto& c : hctl) bdfctl::bdf_control_init(c, t0, t1, first_step, rtol, atol, max_attempts);
-    DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream);   // every return from here on frees them
+    std::vector<BdfSample> hsmp(frames ? (size_t)B : 0);
+    for (auto& s : hsmp) bdfctl::bdf_sample_init(s, n_eval);
+    DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream), b_smp(ctx->stream), b_teval(ctx->stream);   // every return from here on frees them
     HIP_OK(ctx, b_ctl.alloc(sizeof(BdfCtl) * B));
     HIP_OK(ctx, b_rec.alloc(sizeof(double) * NQ * B));
     HIP_OK(ctx, b_counts.alloc(sizeof(int32_t) * (size_t)(radau::L_COUNT + BL_COUNT * B)));
@@ -3148,6 +3154,14 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     int32_t* const dcounts = b_counts.as<int32_t>();   // [L_COUNT] then lists [BL_COUNT][B]
     int32_t* dlists = dcounts + radau::L_COUNT;
     HIP_OK(ctx, hipMemcpyAsync(dctl, hctl.data(), sizeof(BdfCtl) * B, hipMemcpyHostToDevice, ctx->stream));
+    if (frames) {   // the instances' t_eval states and the sample times (pageable host memory: the copies have left it when the calls return)
+        HIP_OK(ctx, b_smp.alloc(sizeof(BdfSample) * B));
+        HIP_OK(ctx, b_teval.alloc(sizeof(double) * (size_t)n_eval));
+        HIP_OK(ctx, hipMemcpyAsync(b_smp.p, hsmp.data(), sizeof(BdfSample) * B, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(b_teval.p, t_eval, sizeof(double) * (size_t)n_eval, hipMemcpyHostToDevice, ctx->stream));
+    }
+    BdfSample* const dsmp = b_smp.as<BdfSample>();
+    const double* const dteval = b_teval.as<double>();
     HIP_OK(ctx, hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));   // (sweep_read_counts keeps them zero between cycles)
     bdf::Vec6 gamma = {};
@@ -3177,11 +3191,12 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     constexpr int64_t kStallCycles = 1000;   // cycles without any instance moving (pc, attempts, status): every cycle moves each running one
     int64_t stalled = 0;
     for (int64_t cycle = 0;; cycle++) {
-        hipLaunchKernelGGL(bdf_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists);
+        if (frames) hipLaunchKernelGGL(bdf_control_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval);
+        else hipLaunchKernelGGL(bdf_control_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval);
         LAUNCH_OK(ctx);
         if (int rc = sweep_read_counts(ctx, dcounts, BL_COUNT, cycle, hcounts)) return rc;
         const unsigned nA = (unsigned)hcounts[BL_ACCEPT], nC = (unsigned)hcounts[BL_CHANGE_D], nJ = (unsigned)hcounts[BL_JAC], nL = (unsigned)hcounts[BL_LU],
-                       nS = (unsigned)hcounts[BL_SOLVE];
+                       nS = (unsigned)hcounts[BL_SOLVE], nP = (unsigned)hcounts[BL_SAMPLE];
         stalled = hcounts[BL_PROGRESS] ? 0 : stalled + 1;
         if (stalled >= kStallCycles)
             return fail(ctx, -3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
@@ -3191,6 +3206,10 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         }
         if (nC) {
             hipLaunchKernelGGL(change_D_batch_kernel, dim3(gx, 1, nC), b256, 0, ctx->stream, D, n, L(BL_CHANGE_D));
+            LAUNCH_OK(ctx);
+        }
+        if (nP) {   // t_eval samples of the step just accepted: D after the selection's rescaling, before the next step's
+            hipLaunchKernelGGL(sample_batch_kernel, dim3(gx, 1, nP), b256, 0, ctx->stream, D, n, dteval, n_eval, dsmp, y_eval_dev, L(BL_SAMPLE));
             LAUNCH_OK(ctx);
         }
         if (nJ) {   // J = jac(t_new, y_predict), with f = fun(t_new, y_predict) (not counted)
@@ -3232,15 +3251,26 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     // results (the synchronise is also what the sweep's buffers wait for before they go)
     HIP_OK(ctx, hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_OK(ctx, hipMemcpyAsync(hctl.data(), dctl, sizeof(BdfCtl) * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (frames) HIP_OK(ctx, hipMemcpyAsync(hsmp.data(), dsmp, sizeof(BdfSample) * B, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t b = 0; b < B; b++) ctl_to_stats(hctl[(size_t)b], stats[b]);
+    for (int64_t b = 0; b < B; b++) {
+        ctl_to_stats(hctl[(size_t)b], stats[b]);
+        if (frames) n_done[b] = hsmp[(size_t)b].next;
+    }
     return 0;
 }
 
 extern "C" int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                   const int32_t* groups, int64_t max_attempts, marl_stats* stats)
 {
-    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, stats);
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, nullptr, 0, nullptr, nullptr, stats);
+}
+
+extern "C" int marl_sweep_bdf_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                       const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                       int64_t* n_done, marl_stats* stats)
+{
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, stats);
 }
 
 #endif  // MARL_LAB

@@ -19,9 +19,10 @@ namespace marl {
 namespace bdf {
 
 using bdfctl::BdfCtl;
+using bdfctl::BdfSample;
 
 // work lists of a cycle; the count words are published by radau::publish_counts_kernel (L_COUNT words, then the sequence word)
-enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_RUNNING, BL_PROGRESS, BL_COUNT };
+enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_SAMPLE, BL_RUNNING, BL_PROGRESS, BL_COUNT };
 static_assert(BL_COUNT <= radau::L_COUNT, "publish_counts_kernel copies L_COUNT words");
 
 // blockIdx.z -> instance (list == NULL: every instance, in order), its arena and its controller
@@ -34,8 +35,12 @@ __device__ __forceinline__ ZBatch z_of(const BdfBatch& B) { return ZBatch{B.zstr
 
 // One lane per instance: resume the step logic, run it to the next action word, append the instance to the list of every bit.
 // rec: [B][8] monitors records of the instances' initial states (read at the first cycle).
+// SAMPLES: the sweep has t_eval samples - samples, t_eval: the instances' t_eval states and the shared sample times.  Without them
+// the step logic is compiled as the three-argument call: a sweep without samples runs the code it ran before there were any.
+template <bool SAMPLES>
 __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ctls, const double* __restrict__ rec, int64_t B, int64_t n,
-                                                         int32_t* __restrict__ counts, int32_t* __restrict__ lists)
+                                                         int32_t* __restrict__ counts, int32_t* __restrict__ lists,
+                                                         BdfSample* __restrict__ samples, const double* __restrict__ t_eval)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
@@ -45,7 +50,8 @@ __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ct
     const double g0[7] = {r[1], r[2], r[3], r[5] - 1.0, r[6] - 1.0, r[4], r[7]};   // record_to_events (marl_api.hip)
     const int32_t pc0 = c.pc, status0 = c.status;
     const int64_t attempts0 = c.attempts;
-    bdfctl::bdf_control_step(c, n, g0);
+    if constexpr (SAMPLES) bdfctl::bdf_control_step(c, n, g0, samples + b, t_eval);
+    else bdfctl::bdf_control_step(c, n, g0);
     ctls[b] = c;
     if (c.pc != bdfctl::PC_DONE) atomicAdd(&counts[BL_RUNNING], 1);
     if (c.pc != pc0 || c.status != status0 || c.attempts != attempts0) atomicAdd(&counts[BL_PROGRESS], 1);
@@ -55,6 +61,8 @@ __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ct
     if (c.action & bdfctl::A_JAC) push(BL_JAC);
     if (c.action & bdfctl::A_LU) push(BL_LU);
     if (c.action & bdfctl::A_SOLVE) push(BL_SOLVE);
+    if constexpr (SAMPLES)
+        if (c.action & bdfctl::A_SAMPLE) push(BL_SAMPLE);
 }
 
 // D[0] = y0, D[1] = f h  (init_D_kernel; h = the controller's first step)
@@ -89,6 +97,38 @@ __global__ void __launch_bounds__(256) change_D_batch_kernel(double* __restrict_
         for (int j = 0; j <= MAX_ORDER; j++)
             if (j <= order) a += c->RU[j][k] * d[j];
         D[(int64_t)k * n + i] = a;
+    }
+}
+
+// A_SAMPLE: the t_eval samples [first, end) of the step the instance just accepted, by the step's dense output (dense_kernel's sum
+// with the weights of bdf_dense, here per sample on the device) -> frames y_eval[(instance n_eval + k) n + i], contiguous
+// [B][n_eval][n] (not the arena's stride).  One element per thread: its D[0 .. order] are read once, every sample is one store.
+__global__ void __launch_bounds__(256) sample_batch_kernel(const double* __restrict__ D, int64_t n, const double* __restrict__ t_eval, int64_t n_eval,
+                                                           const BdfSample* __restrict__ samples, double* __restrict__ y_eval, BdfBatch B)
+{
+    const ZBatch zb = z_of(B);
+    const int64_t inst = z_inst(zb);
+    const BdfSample* s = samples + inst;
+    D = z_shift(D, zb);
+    const int order = s->order;
+    const double t = s->t, h = s->h;
+    const int64_t first = s->first, end = s->end < n_eval ? s->end : n_eval;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double d[MAX_ORDER + 1];
+#pragma unroll
+    for (int j = 0; j <= MAX_ORDER; j++) d[j] = j <= order ? D[(int64_t)j * n + i] : 0.0;
+    double* out = y_eval + (inst * n_eval) * n + i;
+    for (int64_t k = first; k < end; k++) {
+        double p[MAX_ORDER + 1];
+        bdfctl::bdf_dense_weights(t, h, order, t_eval[k], p);
+        // the sum as dense_kernel (marl_bdf.h) writes it; that kernel keeps its own copy: called through a shared function its
+        // machine code changed (another order of its argument loads)
+        double a = 0;
+#pragma unroll
+        for (int j = 0; j < MAX_ORDER; j++)
+            if (j < order) a += d[j + 1] * p[j];
+        out[k * n] = a + d[0];
     }
 }
 

@@ -6,6 +6,17 @@
 //     A_ACCEPT (+ the order-selection norms asked for by `want_norms`)  ->  A_CHANGE_D (RU, ru_order)  ->  A_JAC (f and J at y_predict)
 //     ->  A_LU (I - c J)  ->  A_SOLVE (solve_bdf_system; mode 0: predictor first, 1: restart from y_predict)
 // so that an accepted step without order selection costs one cycle (accept | solve of the next step) and one with it two.
+//
+// t_eval samples (the sampling form of bdf_control_step: BdfSample, one per instance beside its BdfCtl, and the shared sample times).
+// scipy builds a step's dense output after _step_impl has returned (bdf.py:452-454), so a sample reads D[:order + 1], the order and
+// h_abs AFTER the order / step-size selection and its change_D, and BEFORE the next step rescales D again (min_step in PC_STEP, the
+// clipping at t_bound in PC_ATTEMPT).  An accepted step that covers a pending sample (t_eval[next] <= t) therefore snapshots
+// (t, h = S_h_abs, order, [first, end) of its samples) at PC_STEP_END, sets A_SAMPLE and YIELDS there: the cycle's work becomes
+//     A_ACCEPT  ->  A_CHANGE_D (the selection's)  ->  A_SAMPLE (D[0] + sum_j D[j + 1] p[j], bdf_dense_weights)
+// and the next step's logic, with whatever rescaling it asks for, starts in the following cycle.  Only steps that hold samples pay
+// that cycle (at most n_eval per instance); the last step's samples are published in the cycle that reaches PC_DONE; a run that
+// ends with status -1 or 2 does so in PC_ATTEMPT of a later cycle and keeps the samples it has written.  Without a BdfSample, or with
+// n_eval = 0, the action words and their cycles are those of the three-argument call.
 // f(t0, y0), the first Jacobian, D[0] = y0, D[1] = f h and the monitors of y0 (BDF.__init__) are done before the first cycle.
 // Like marl_brent.h: nothing but <math.h> / <stdint.h>, so that a host C++ compiler builds this header alone
 // (tests/test_bdf_control_cpu.py holds it to scipy's solve_ivp(method="BDF") that way).
@@ -25,7 +36,7 @@ namespace bdfctl {
 constexpr int MAX_ORDER = 5, NEWTON_MAXITER = 4;
 constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10;
 
-enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16 };
+enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16, A_SAMPLE = 32 };
 enum : int32_t { PC_INIT = 0, PC_STEP, PC_ATTEMPT, PC_SOLVED, PC_SELECT, PC_STEP_END, PC_DONE };
 
 struct BdfCtl {
@@ -54,6 +65,15 @@ struct BdfCtl {
     double dy_ss, err_ss;              // sum (dy / scale)^2 of the last iteration; sum (error_const[order] d / scale)^2 of the converged state
     double g_new[7];                   // the monitors of the converged state
     double ss_m, ss_p;                 // A_ACCEPT: the two sums of want_norms
+};
+
+// The t_eval state of one instance: a parallel array beside the controllers (BdfCtl keeps its layout).
+struct BdfSample {
+    int64_t n_eval, next;              // samples asked for; the first one not yet written (at the end: the frames of the instance)
+    // A_SAMPLE: the dense output of the step just accepted and the samples [first, end) it covers
+    double t, h;                       // the step's end and S_h_abs after the selection (BdfDenseOutput's t, h)
+    int64_t first, end;
+    int32_t order, pad;
 };
 
 MARL_BDF_FN double kappa_of(int k) { return k == 1 ? -0.1850 : k == 2 ? -1.0 / 9 : k == 3 ? -0.0823 : k == 4 ? -0.0415 : 0.0; }
@@ -99,6 +119,20 @@ MARL_BDF_FN void request_change_D(BdfCtl& c, double factor)
     c.action |= A_CHANGE_D;
 }
 
+// BdfDenseOutput (bdf.py:456-478) of the step that ended at `t` with step size `h`: p = cumprod((tq - (t - h j)) / (h (1 + j))), j < order;
+// the sample is D[0] + sum_j D[j + 1] p[j].  Every operation rounded on its own, as numpy does them (and bdf_dense on the host).
+MARL_BDF_FN void bdf_dense_weights(double t, double h, int order, double tq, double (&p)[MAX_ORDER + 1])
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    double acc = 1;
+    for (int j = 0; j <= MAX_ORDER; j++) {
+        if (j < order) acc *= (tq - (t - h * j)) / (h * (1 + j));
+        p[j] = j < order ? acc : 0.0;
+    }
+}
+
 // A controller at (t0, first_step) in front of its first cycle.  rtol: already clamped to 100 eps (ivp's validate_tol).
 MARL_BDF_FN void bdf_control_init(BdfCtl& c, double t0, double t1, double first_step, double rtol, double atol, int64_t max_attempts)
 {
@@ -110,8 +144,15 @@ MARL_BDF_FN void bdf_control_init(BdfCtl& c, double t0, double t1, double first_
     c.pc = PC_INIT; c.status = 1;
 }
 
+MARL_BDF_FN void bdf_sample_init(BdfSample& s, int64_t n_eval)
+{
+    s = BdfSample{};
+    s.n_eval = n_eval;
+}
+
 // One instance from where it stopped to its next action word.  n: unknowns (5 N).  g0: the seven monitors of y0 (read at PC_INIT only).
-MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0)
+// s, t_eval: the instance's sampling state and the n_eval sorted sample times (NULL: no samples).
+MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSample* s = nullptr, const double* t_eval = nullptr)
 {
     c.action = 0;
     int pc = c.pc;
@@ -236,8 +277,19 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0)
             continue;
         }
         if (pc == PC_STEP_END) {                  // the solve_ivp loop (ivp.py:667-668)
+            bool sampled = false;
+            if (s && s->next < s->n_eval && t_eval[s->next] <= c.t) {   // ivp.py:706-723: searchsorted(t_eval, t, side="right")
+                s->t = c.t; s->h = c.S_h_abs; s->order = c.order;
+                s->first = s->next;
+                int64_t e = s->next + 1;
+                while (e < s->n_eval && t_eval[e] <= c.t) e++;
+                s->end = s->next = e;
+                c.action |= A_SAMPLE;
+                sampled = true;
+            }
             if (c.t - c.t_bound >= 0) { c.status = 0; pc = PC_DONE; break; }
             pc = PC_STEP;
+            if (sampled) break;                   // the next step may rescale D: not in the cycle that samples it
             continue;
         }
         break;

@@ -121,17 +121,28 @@ class HipSweepEngine:
             r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
-    def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False):
+    def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False, t_eval=None):
         """scipy BDF semantics (the other implicit method of the reference's Solver, marlpde/parameters.py:205-219) for every instance of
         the shard.  By default the instances run as concurrent SINGLE runs (marl_integrate_bdf, one context and one HIP stream per worker
         thread - ctypes releases the GIL, and a single BDF run of a small grid leaves the GPU mostly idle between its small launches),
         so each instance is bit for bit the single run.  ``batched=True`` runs the shard through the batched kernel set instead
         (marl_sweep_bdf_dev on the batched model, as :meth:`integrate_radau`: per-instance step control on the device, every launch
         over all instances that need that work; N <= 409): the same decisions up to the controller's scalar arithmetic, no root
-        times, no ``t_eval``.  Returns (y_final (n_local, 5N), list of RK45Result)."""
+        times.  Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries the samples that instance
+        reached, ``t`` (n_t,) and ``y`` (5N, n_t), either way: the single runs take them from their own dense output, the batched
+        sweep writes them inside the sweep (marl_sweep_bdf_eval_dev), as :meth:`integrate_radau` does."""
         if batched:
             yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
-            res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+            if t_eval is None:
+                res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+                return yd.cpu().numpy(), res
+            n_eval = int(np.size(t_eval))
+            frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
+            res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
+                                              y_eval_dev_ptr=frames.data_ptr())
+            frames = frames.cpu().numpy()
+            for b, r in enumerate(res):
+                r.y = frames[b, :len(r.t)].T.copy()
             return yd.cpu().numpy(), res
         from concurrent.futures import ThreadPoolExecutor
         from .LHeureux_model import LMAHeureuxPorosityDiff
@@ -153,7 +164,7 @@ class HipSweepEngine:
                         one.use_stream(stream.cuda_stream)
                     else:
                         one.set_scenario(p)
-                    r = one.integrate_bdf(y0[b], t_span, first_step, rtol, atol, max_attempts=max_attempts)
+                    r = one.integrate_bdf(y0[b], t_span, first_step, rtol, atol, t_eval=t_eval, max_attempts=max_attempts)
                     out[b] = r
                     yf[b] = r.y_final
             finally:
@@ -200,12 +211,13 @@ def run_sweep_radau(base_parms, instances, t_span, first_step, rtol, atol, max_a
 
 
 def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                  device=None, engine_factory=None, gather=True, balance="cost", cost=None, batched=False):
+                  device=None, engine_factory=None, gather=True, balance="cost", cost=None, batched=False, t_eval=None):
     """As :func:`run_sweep_radau` with scipy's BDF semantics; on a GPU the rank's instances run as concurrent single runs, or with
     ``batched=True`` (N <= 409) through the batched BDF kernels, all instances advanced together
-    (:meth:`HipSweepEngine.integrate_bdf`).  ``batched`` reaches the engine only when asked for."""
+    (:meth:`HipSweepEngine.integrate_bdf`).  ``batched`` and ``t_eval`` reach the engine only when asked for; with ``t_eval`` two
+    more elements follow, ``n_frames`` and ``y_eval``, as documented for :func:`run_sweep_rk45` (either way of running the shard)."""
     return _run_sweep("integrate_bdf", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, batched=batched)
+                      balance, cost, t_eval, batched=batched)
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
@@ -242,7 +254,7 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
         dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device   # one process per GPU
         engine_factory = lambda bp, inst: HipSweepEngine(bp, inst, dev)  # noqa: E731
     y0 = np.asarray(y0)
-    sampled = t_eval is not None   # (RK45 and Radau sweeps; the BDF driver passes none)
+    sampled = t_eval is not None
     if sampled:
         t_eval = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
     if local:

@@ -1,8 +1,11 @@
-"""BDF sweeps, thread pool of single runs against the batched kernels (needs a GPU):  python3 tools/bdf_sweep_ab.py [--sizes 64 512] [--reps 5]
+"""BDF sweeps, thread pool of single runs against the batched kernels (needs a GPU):
+    python3 tools/bdf_sweep_ab.py [--sizes 64 512] [--reps 5] [--t-eval K] [--only batched|pool]
 
 run_sweep_bdf on one GPU over product_grid(Phi0, k3 = k4) at N = 200, t_span (0, 1), first step 1e-6, rtol = atol = 1e-3: once with
 the thread pool (concurrent marl_integrate_bdf runs, at its own limit of 16 workers) and once with batched=True (marl_sweep_bdf_dev).
-One warm-up each, then alternating repetitions in one process; medians and spread per size, and how far the two agree."""
+One warm-up each, then alternating repetitions in one process; medians and spread per size, and how far the two agree.
+--t-eval K: both paths also return the time series at K uniform samples over t_span (marl_sweep_bdf_eval_dev against the single runs'
+t_eval); the record then carries the frames' agreement too.  --only: time one of the two paths alone (no comparison)."""
 import argparse
 import json
 import os
@@ -21,10 +24,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", type=int, nargs="+", default=[64, 512])
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--N", type=int, default=200)
+ap.add_argument("--t-eval", type=int, default=0, dest="t_eval", help="K uniform samples over t_span (0: none)")
+ap.add_argument("--only", choices=["batched", "pool"], default=None)
 args = ap.parse_args()
 
 base = asdict(Map_Scenario()) | {"N": args.N}
 ARGS = ((0.0, 1.0), 1e-6, 1e-3, 1e-3)
+more = {"t_eval": np.linspace(ARGS[0][0], ARGS[0][1], args.t_eval)} if args.t_eval > 0 else {}
+paths = {None: (False, True), "batched": (True,), "pool": (False,)}[args.only]
 for B in args.sizes:
     nk = 8 if B <= 64 else 16
     insts = product_grid(Phi0=np.linspace(0.5, 0.7, B // nk), k3=np.logspace(-2, -1, nk))
@@ -34,19 +41,23 @@ for B in args.sizes:
     times = {False: [], True: []}
     out = {}
     for rep in range(-1, args.reps):   # -1: warm-up (module load, allocations)
-        for batched in (False, True):
+        for batched in paths:
             t0 = time.perf_counter()
-            out[batched] = run_sweep_bdf(base, insts, *ARGS, y0=y0, device=0, batched=batched)
+            out[batched] = run_sweep_bdf(base, insts, *ARGS, y0=y0, device=0, batched=batched, **more)
             if rep >= 0:
                 times[batched].append(time.perf_counter() - t0)
-    (yp, sp, ap_, rp, tp), (yb, sb, ab, rb, tb) = out[False], out[True]
-    same = int(np.sum((ap_ == ab) & (rp == rb)))
-    rec = {"instances": len(insts), "N": args.N, "reps": args.reps,
-           "thread_pool_s": {"median": float(np.median(times[False])), "min": min(times[False]), "max": max(times[False])},
-           "batched_s": {"median": float(np.median(times[True])), "min": min(times[True]), "max": max(times[True])},
-           "ratio_of_medians": float(np.median(times[False]) / np.median(times[True])),
-           "status_0": [int(np.sum(sp == 0)), int(np.sum(sb == 0))],
-           "accepted_steps_median_max": [float(np.median(ab)), int(np.max(ab))],
-           "instances_with_equal_accepted_and_rejected_counts": same,
-           "max_abs_state_difference": float(np.max(np.abs(yp - yb)))}
+    rec = {"instances": len(insts), "N": args.N, "reps": args.reps, "t_eval": args.t_eval}
+    for batched, name in ((False, "thread_pool_s"), (True, "batched_s")):
+        if batched in paths:
+            rec[name] = {"median": float(np.median(times[batched])), "min": min(times[batched]), "max": max(times[batched])}
+            rec["status_0_" + name[:-2]] = int(np.sum(out[batched][1] == 0))
+    if args.only is None:
+        (yp, sp, ap_, rp, tp, *fp), (yb, sb, ab, rb, tb, *fb) = out[False], out[True]
+        rec |= {"ratio_of_medians": float(np.median(times[False]) / np.median(times[True])),
+                "accepted_steps_median_max": [float(np.median(ab)), int(np.max(ab))],
+                "instances_with_equal_accepted_and_rejected_counts": int(np.sum((ap_ == ab) & (rp == rb))),
+                "max_abs_state_difference": float(np.max(np.abs(yp - yb)))}
+        if more:
+            rec |= {"instances_with_equal_frame_counts": int(np.sum(fp[0] == fb[0])),
+                    "max_abs_frame_difference": float(np.nanmax(np.abs(fp[1] - fb[1])))}
     print(json.dumps(rec), flush=True)
