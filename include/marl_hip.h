@@ -246,7 +246,8 @@ int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1
  * in place; stats[b]: nfev / njev / nlu / n_accepted / n_rejected / status / t / h_next as scipy counts them, n_events the monitors'
  * sign changes over accepted steps, event_value the monitors of the final state.  t1 == t0: no step, the state is untouched,
  * status 0, nfev = njev = 1 (BDF.__init__).  A failed solve is a status, not an error.  Synchronises.
- * It does NOT: locate root times (marl_integrate_bdf's; t_eval frames: marl_sweep_bdf_eval_dev below), take grids whose solve does
+ * Root times and t_eval frames: marl_sweep_bdf_events_dev / marl_sweep_bdf_eval_dev below (this entry counts sign changes only).
+ * It does NOT: take grids whose solve does
  * not fit one workgroup (5 N <= 2048, N <= 409; larger: -1, use marl_integrate_bdf), or keep an instance in a persistent workgroup. */
 int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                        const int32_t* groups, int64_t max_attempts, marl_stats* stats);
@@ -262,6 +263,19 @@ int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
 int marl_sweep_bdf_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                             const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                             int64_t* n_done, marl_stats* stats);
+/* The same sweep with the monitors' ROOT TIMES located inside it, what solve_ivp returns as sol.t_events for every run
+ * (marlpde/Evolve_scenario.py:118-145, 175-177; ivp.py:673-694 with solve_event_equation :51-76) - with this entry every way of
+ * integrating returns them.  The roots are read from the dense output the samples are read from (after the accepted step's order /
+ * step-size selection, before the next step rescales D), events before t_eval as in scipy: an accepted step over which monitors
+ * changed sign costs the instance one more cycle (shared with its samples), in which one workgroup runs the whole Brent search of all
+ * those monitors on the step's dense output (csrc/marl_bdf_batch.h, roots_batch_kernel).  State, statistics and frames are those of
+ * the same call without roots.
+ * t_events: host, [n_instances][7][max_events]; entry k of monitor e of instance b is valid for k < min(stats[b].n_events[e], max_events),
+ * the rest is NaN; sign changes beyond max_events are counted only.  A run that ends with status -1 or 2 keeps the roots it located;
+ * t1 == t0: none.  t_events == NULL or max_events <= 0 is marl_sweep_bdf_eval_dev; n_eval = 0 leaves the samples out.  Synchronises. */
+int marl_sweep_bdf_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                              const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                              int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
 /* ---- 1-D domain decomposition of ONE large grid (BASELINE config 5; the reference never decomposes the depth
  * axis).  One process per GPU holds a slab [g_begin, g_end) of the N_global cells in a slab context; the host

@@ -497,21 +497,39 @@ class LMAHeureuxPorosityDiff:
         return [RK45Result(s, t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
                 for b, s in enumerate(stats)]
 
-    def sweep_bdf_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None, t_eval=None, y_eval_dev_ptr=None):
+    def sweep_bdf_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None, t_eval=None, y_eval_dev_ptr=None,
+                         events=False, max_events=64):
         """Every instance of the model integrated with scipy's BDF semantics, all instances advanced together on the device
         (marl_sweep_bdf_dev: per-instance step control on the device, batched solves); device states [instances][5N] in place.
-        Returns one :class:`RK45Result` per instance (statistics; the monitors' sign changes are counted in ``n_events``).  Root
-        times are not part of this sweep (single runs: :meth:`integrate_bdf`), and the grid is limited to N <= 409 (a solve must
-        fit one workgroup).
+        Returns one :class:`RK45Result` per instance (statistics; the monitors' sign changes are counted in ``n_events``).  The grid
+        is limited to N <= 409 (a solve must fit one workgroup).
 
         With ``t_eval`` (sorted sample times within ``t_span``, shared by all instances) the sweep also writes the time series that
         ``solve_ivp(..., t_eval=)`` returns (marl_sweep_bdf_eval_dev), as :meth:`sweep_radau_device` does: ``y_eval_dev_ptr`` is device
         memory [instances][len(t_eval)][5N]; each result carries ``t = t_eval[:n_frames]``, the frames stay on the device, and frames
-        beyond ``n_frames`` are not written."""
+        beyond ``n_frames`` are not written.
+
+        ``events=True``: the monitors' root times are located inside the sweep (marl_sweep_bdf_events_dev) and returned as
+        ``t_events`` - a list of 7 arrays per instance, ``min(n_events[e], max_events)`` long, what the reference prints and stores
+        for every run (Evolve_scenario.py:118-145, 175-177); otherwise (or with ``max_events`` = 0) sign changes are only counted and
+        ``t_events`` is None.  Combinable with ``t_eval``."""
         grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
         stats = (MarlStats * self.n_instances)()
         args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
                 _as_ptr(grp) if grp is not None else None, int(max_attempts))
+        if bool(events) and int(max_events) > 0:
+            te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
+            if te.size and not y_eval_dev_ptr:
+                raise ValueError("sweep_bdf_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
+            n_done = np.zeros(self.n_instances, dtype=np.int64)
+            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan)
+            rc = self._lib.marl_sweep_bdf_events_dev(*args, _as_ptr(te) if te.size else None, te.size,
+                                                     C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
+                                                     _as_ptr(tev), int(max_events), stats)
+            self._check(rc, "marl_sweep_bdf_events_dev")
+            return [RK45Result(s, t=te[:int(k)].copy() if t_eval is not None else None,
+                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
+                    for b, (s, k) in enumerate(zip(stats, n_done))]
         if t_eval is not None:
             te = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
             if te.size and not y_eval_dev_ptr:

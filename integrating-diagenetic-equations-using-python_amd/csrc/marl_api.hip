@@ -3118,14 +3118,19 @@ extern "C" int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0
 // t_eval (host, n_eval times), y_eval_dev (device, [instance][n_eval][5N]), n_done (host, [instance]): the samples inside every accepted
 // step by the step's dense output, built as bdf_run builds it - after the order / step-size selection, before the next step rescales D
 // (A_SAMPLE, marl_bdf_ctl.h); n_eval = 0: none, and the same cycles.  A run with t1 == t0 takes no step and writes no frame.
+// t_events (host, [instance][7][max_events]), max_events: the monitors' root times, located on the same dense output in front of the
+// samples (A_ROOTS: roots_batch_kernel runs the whole search of a step's monitors in one launch) into a NaN-filled device buffer that
+// comes back once at the end; NULL or max_events <= 0: sign changes are counted only, and neither the buffer nor the instances'
+// BdfRoots exist - the kernels and cycles are those of the sweep without roots.
 static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
-                     int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, marl_stats* stats)
+                     int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, double* t_events,
+                     int64_t max_events, marl_stats* stats)
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_bdf_dev: invalid argument") : -1;
     if (n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done))) return fail(ctx, -1, "marl_sweep_bdf_eval_dev: invalid argument");
     if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_bdf_dev: whole-grid context required");
     if (int rc = check_ivp_args(ctx, "bdf", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
-    const bool frames = n_eval > 0;
+    const bool frames = n_eval > 0, locate = t_events && max_events > 0;
     if (ctx->batch > 65535) return fail(ctx, -1, "marl_sweep_bdf_dev: at most 65535 instances per call");
     const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
     if (n > radau::PCR_FUSED_MAX)
@@ -3145,7 +3150,11 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     for (auto& c : hctl) bdfctl::bdf_control_init(c, t0, t1, first_step, rtol, atol, max_attempts);
     std::vector<BdfSample> hsmp(frames ? (size_t)B : 0);
     for (auto& s : hsmp) bdfctl::bdf_sample_init(s, n_eval);
-    DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream), b_smp(ctx->stream), b_teval(ctx->stream);   // every return from here on frees them
+    std::vector<BdfRoots> hroots(locate ? (size_t)B : 0);
+    for (auto& r : hroots) bdfctl::bdf_roots_init(r, max_events);
+    const size_t tev_bytes = locate ? sizeof(double) * (size_t)B * 7 * (size_t)max_events : 0;
+    DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream), b_smp(ctx->stream), b_teval(ctx->stream), b_roots(ctx->stream),
+        b_tev(ctx->stream);   // every return from here on frees them
     HIP_OK(ctx, b_ctl.alloc(sizeof(BdfCtl) * B));
     HIP_OK(ctx, b_rec.alloc(sizeof(double) * NQ * B));
     HIP_OK(ctx, b_counts.alloc(sizeof(int32_t) * (size_t)(radau::L_COUNT + BL_COUNT * B)));
@@ -3160,8 +3169,16 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         HIP_OK(ctx, hipMemcpyAsync(b_smp.p, hsmp.data(), sizeof(BdfSample) * B, hipMemcpyHostToDevice, ctx->stream));
         HIP_OK(ctx, hipMemcpyAsync(b_teval.p, t_eval, sizeof(double) * (size_t)n_eval, hipMemcpyHostToDevice, ctx->stream));
     }
+    if (locate) {   // the instances' root-location states and their root times, NaN (all bits set) until a root is stored
+        HIP_OK(ctx, b_roots.alloc(sizeof(BdfRoots) * B));
+        HIP_OK(ctx, b_tev.alloc(tev_bytes));
+        HIP_OK(ctx, hipMemcpyAsync(b_roots.p, hroots.data(), sizeof(BdfRoots) * B, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemsetAsync(b_tev.p, 0xFF, tev_bytes, ctx->stream));
+    }
     BdfSample* const dsmp = b_smp.as<BdfSample>();
     const double* const dteval = b_teval.as<double>();
+    BdfRoots* const droots = b_roots.as<BdfRoots>();
+    double* const dtev = b_tev.as<double>();
     HIP_OK(ctx, hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));   // (sweep_read_counts keeps them zero between cycles)
     bdf::Vec6 gamma = {};
@@ -3191,12 +3208,15 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     constexpr int64_t kStallCycles = 1000;   // cycles without any instance moving (pc, attempts, status): every cycle moves each running one
     int64_t stalled = 0;
     for (int64_t cycle = 0;; cycle++) {
-        if (frames) hipLaunchKernelGGL(bdf_control_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval);
-        else hipLaunchKernelGGL(bdf_control_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval);
+        const dim3 gctl((unsigned)((B + 63) / 64)), bctl(64);
+        if (frames && locate) hipLaunchKernelGGL((bdf_control_kernel<true, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
+        else if (locate) hipLaunchKernelGGL((bdf_control_kernel<false, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
+        else if (frames) hipLaunchKernelGGL((bdf_control_kernel<true, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
+        else hipLaunchKernelGGL((bdf_control_kernel<false, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
         LAUNCH_OK(ctx);
         if (int rc = sweep_read_counts(ctx, dcounts, BL_COUNT, cycle, hcounts)) return rc;
         const unsigned nA = (unsigned)hcounts[BL_ACCEPT], nC = (unsigned)hcounts[BL_CHANGE_D], nJ = (unsigned)hcounts[BL_JAC], nL = (unsigned)hcounts[BL_LU],
-                       nS = (unsigned)hcounts[BL_SOLVE], nP = (unsigned)hcounts[BL_SAMPLE];
+                       nS = (unsigned)hcounts[BL_SOLVE], nP = (unsigned)hcounts[BL_SAMPLE], nR = locate ? (unsigned)hcounts[BL_ROOTS] : 0u;
         stalled = hcounts[BL_PROGRESS] ? 0 : stalled + 1;
         if (stalled >= kStallCycles)
             return fail(ctx, -3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
@@ -3206,6 +3226,10 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         }
         if (nC) {
             hipLaunchKernelGGL(change_D_batch_kernel, dim3(gx, 1, nC), b256, 0, ctx->stream, D, n, L(BL_CHANGE_D));
+            LAUNCH_OK(ctx);
+        }
+        if (nR) {   // root times of the step just accepted: the same D as the samples below, events first (ivp.py:673-723)
+            hipLaunchKernelGGL(roots_batch_kernel, dim3(1, 1, nR), dim3(radau::WG_THREADS), 0, ctx->stream, D, N, droots, dtev, ctx->dconsts, L(BL_ROOTS));
             LAUNCH_OK(ctx);
         }
         if (nP) {   // t_eval samples of the step just accepted: D after the selection's rescaling, before the next step's
@@ -3252,6 +3276,7 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     HIP_OK(ctx, hipMemcpy2DAsync(y_dev, n * sizeof(double), w.y, (size_t)zs, n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_OK(ctx, hipMemcpyAsync(hctl.data(), dctl, sizeof(BdfCtl) * B, hipMemcpyDeviceToHost, ctx->stream));
     if (frames) HIP_OK(ctx, hipMemcpyAsync(hsmp.data(), dsmp, sizeof(BdfSample) * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (locate) HIP_OK(ctx, hipMemcpyAsync(t_events, dtev, tev_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < B; b++) {
         ctl_to_stats(hctl[(size_t)b], stats[b]);
@@ -3263,14 +3288,21 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
 extern "C" int marl_sweep_bdf_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                   const int32_t* groups, int64_t max_attempts, marl_stats* stats)
 {
-    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, nullptr, 0, nullptr, nullptr, stats);
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
 }
 
 extern "C" int marl_sweep_bdf_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                        const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                                        int64_t* n_done, marl_stats* stats)
 {
-    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, stats);
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, nullptr, 0, stats);
+}
+
+extern "C" int marl_sweep_bdf_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                         const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                         int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats);
 }
 
 #endif  // MARL_LAB

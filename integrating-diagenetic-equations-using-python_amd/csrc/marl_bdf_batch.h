@@ -19,10 +19,11 @@ namespace marl {
 namespace bdf {
 
 using bdfctl::BdfCtl;
+using bdfctl::BdfRoots;
 using bdfctl::BdfSample;
 
 // work lists of a cycle; the count words are published by radau::publish_counts_kernel (L_COUNT words, then the sequence word)
-enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_SAMPLE, BL_RUNNING, BL_PROGRESS, BL_COUNT };
+enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_SAMPLE, BL_ROOTS, BL_RUNNING, BL_PROGRESS, BL_COUNT };
 static_assert(BL_COUNT <= radau::L_COUNT, "publish_counts_kernel copies L_COUNT words");
 
 // blockIdx.z -> instance (list == NULL: every instance, in order), its arena and its controller
@@ -37,10 +38,13 @@ __device__ __forceinline__ ZBatch z_of(const BdfBatch& B) { return ZBatch{B.zstr
 // rec: [B][8] monitors records of the instances' initial states (read at the first cycle).
 // SAMPLES: the sweep has t_eval samples - samples, t_eval: the instances' t_eval states and the shared sample times.  Without them
 // the step logic is compiled as the three-argument call: a sweep without samples runs the code it ran before there were any.
-template <bool SAMPLES>
+// ROOTS: the sweep locates the monitors' root times - roots: the instances' root-location states (A_ROOTS -> BL_ROOTS); without
+// them the step logic is compiled as the call without a BdfRoots.
+template <bool SAMPLES, bool ROOTS>
 __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ctls, const double* __restrict__ rec, int64_t B, int64_t n,
                                                          int32_t* __restrict__ counts, int32_t* __restrict__ lists,
-                                                         BdfSample* __restrict__ samples, const double* __restrict__ t_eval)
+                                                         BdfSample* __restrict__ samples, const double* __restrict__ t_eval,
+                                                         BdfRoots* __restrict__ roots)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
@@ -50,7 +54,8 @@ __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ct
     const double g0[7] = {r[1], r[2], r[3], r[5] - 1.0, r[6] - 1.0, r[4], r[7]};   // record_to_events (marl_api.hip)
     const int32_t pc0 = c.pc, status0 = c.status;
     const int64_t attempts0 = c.attempts;
-    if constexpr (SAMPLES) bdfctl::bdf_control_step(c, n, g0, samples + b, t_eval);
+    if constexpr (ROOTS) bdfctl::bdf_control_step(c, n, g0, SAMPLES ? samples + b : nullptr, SAMPLES ? t_eval : nullptr, roots + b);
+    else if constexpr (SAMPLES) bdfctl::bdf_control_step(c, n, g0, samples + b, t_eval);
     else bdfctl::bdf_control_step(c, n, g0);
     ctls[b] = c;
     if (c.pc != bdfctl::PC_DONE) atomicAdd(&counts[BL_RUNNING], 1);
@@ -63,6 +68,8 @@ __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ct
     if (c.action & bdfctl::A_SOLVE) push(BL_SOLVE);
     if constexpr (SAMPLES)
         if (c.action & bdfctl::A_SAMPLE) push(BL_SAMPLE);
+    if constexpr (ROOTS)
+        if (c.action & bdfctl::A_ROOTS) push(BL_ROOTS);
 }
 
 // D[0] = y0, D[1] = f h  (init_D_kernel; h = the controller's first step)
@@ -130,6 +137,74 @@ __global__ void __launch_bounds__(256) sample_batch_kernel(const double* __restr
             if (j < order) a += d[j + 1] * p[j];
         out[k * n] = a + d[0];
     }
+}
+
+// A_ROOTS, one workgroup per listed instance: the root times of every monitor that changed sign over the step the instance just accepted,
+// the WHOLE search of all of them in this one launch (a root costs about ten evaluations of the step's dense output: one host cycle
+// per evaluation would multiply the cycles of a run).  N <= WG_THREADS (the sweep takes 5 N <= PCR_FUSED_MAX): thread l owns cell l,
+// loads its D[0 .. order] of the five fields once (at most 30 doubles, kept in registers) and an evaluation at tq is
+//     scalar weights (bdf_dense_weights)  ->  the cell's dense state, sample_batch_kernel's sum  ->  the cell's monitor terms
+//     (wg_monitors / monitors_kernel)  ->  block_reduce in LDS  ->  the seven monitors, read back from LDS by every thread
+// with no global memory touched.  Control flow is uniform: every thread runs the scalar search (bdfctl::bdf_find_roots) redundantly
+// on the reduced monitors all threads read after the barrier, so every thread reaches every barrier; the loops are bounded
+// (<= 7 monitors x (2 + <= 100) evaluations).  Thread 0 stores the roots: t_events [instances][7][max_events] (device).
+__global__ void __launch_bounds__(radau::WG_THREADS) roots_batch_kernel(const double* __restrict__ D, int64_t N, const BdfRoots* __restrict__ roots,
+                                                                         double* __restrict__ t_events, const DevConsts* __restrict__ consts, BdfBatch B)
+{
+    using namespace radau;
+    __shared__ double red[NQ * WG_THREADS];
+    __shared__ double tabs[TABLE_DOUBLES];
+    __shared__ double g_sh[7];
+    const Tables T = load_tables(tabs, WG_THREADS);
+    const ZBatch zb = z_of(B);
+    const int64_t inst = z_inst(zb);
+    const BdfRoots& r = roots[inst];   // (read where it is: a private copy would sit in scratch memory for slot[e])
+    const DevConsts& C = consts[inst];
+    D = z_shift(D, zb);
+    const int64_t n = NF * N, l = threadIdx.x;
+    const bool mine = l < N;
+    const int order = r.order;
+    const double t = r.t, h = r.h;
+    double d[NF][MAX_ORDER + 1];
+#pragma unroll
+    for (int f = 0; f < NF; f++)
+#pragma unroll
+        for (int j = 0; j <= MAX_ORDER; j++) d[f][j] = (mine && j <= order) ? D[(int64_t)j * n + f * N + l] : 0.0;
+    const double rhorat = C.hot.rhorat, presum = C.hot.presum;
+    auto eval = [&](double tq, int e) -> double {
+        double p[MAX_ORDER + 1];
+        bdfctl::bdf_dense_weights(t, h, order, tq, p);
+        double q[NQ];
+        monitors_init(q);
+        if (mine) {
+            double u[NF];
+#pragma unroll
+            for (int f = 0; f < NF; f++) {
+                double a = 0;
+#pragma unroll
+                for (int j = 0; j < MAX_ORDER; j++)
+                    if (j < order) a += d[f][j + 1] * p[j];
+                u[f] = a + d[f][0];
+            }
+            const double Phi = u[4];
+            const double F = 1.0 - fast_exp(10.0 - 10.0 * rcp_nr(Phi), T);
+            const double rF = rhorat * F;
+            monitors_accumulate(q, u, presum + rF * (Phi * Phi * Phi) * rcp_nr(1.0 - Phi), presum - rF * Phi * Phi);
+        }
+        block_reduce<WG_THREADS, NQ, NQMIN>(q, red);   // (begins and ends with a barrier; the result is thread 0's)
+        if (threadIdx.x == 0) {
+            const double gq[7] = {q[1], q[2], q[3], q[5] - 1.0, q[6] - 1.0, q[4], q[7]};   // record_to_events (marl_api.hip)
+            for (int e = 0; e < 7; e++) g_sh[e] = gq[e];
+        }
+        __syncthreads();
+        const double ge = g_sh[e];
+        __syncthreads();   // (g_sh is free for the next evaluation)
+        return ge;
+    };
+    double* out = t_events + inst * 7 * r.max_events;
+    bdfctl::bdf_find_roots(r, eval, [&](int e, double root) {
+        if (threadIdx.x == 0) out[e * r.max_events + r.slot[e]] = root;
+    });
 }
 
 // A_ACCEPT, one workgroup per instance: the accepted step's update of the differences and y = y_new (accept_kernel), then the norms

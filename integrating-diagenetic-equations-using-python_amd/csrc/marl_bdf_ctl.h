@@ -17,12 +17,25 @@
 // that cycle (at most n_eval per instance); the last step's samples are published in the cycle that reaches PC_DONE; a run that
 // ends with status -1 or 2 does so in PC_ATTEMPT of a later cycle and keeps the samples it has written.  Without a BdfSample, or with
 // n_eval = 0, the action words and their cycles are those of the three-argument call.
+//
+// Root times of the monitors (BdfRoots, a third per-instance struct; A_ROOTS; bdf_locate_roots).  solve_ivp finds the roots of the events
+// that changed sign over an accepted step on the same dense output, before it takes the t_eval samples (ivp.py:673-694, 706-723).  At
+// acceptance (PC_SOLVED), where the sign changes are counted, every monitor that changed sign and whose count is still below max_events
+// is marked pending with that count as its slot, and the step's start is kept; the marks survive PC_SELECT.  At PC_STEP_END a step
+// with pending monitors snapshots (t_old, t, h = S_h_abs, order), sets A_ROOTS and yields exactly as a step with samples does (one
+// shared extra cycle when it has both), so that a cycle's work reads
+//     A_ACCEPT  ->  A_CHANGE_D  ->  A_ROOTS  ->  A_SAMPLE  ->  A_JAC  ->  A_LU  ->  A_SOLVE
+// (events before t_eval, as in scipy; both only read D).  The last step's roots go out in the cycle that reaches PC_DONE, a run that
+// ends with status -1 or 2 keeps the roots it has, t1 == t0 has none.  Without a BdfRoots, or with max_events <= 0, the action words,
+// the cycles and the controller's bytes are those of the calls without it; n_events counts every sign change either way.
 // f(t0, y0), the first Jacobian, D[0] = y0, D[1] = f h and the monitors of y0 (BDF.__init__) are done before the first cycle.
-// Like marl_brent.h: nothing but <math.h> / <stdint.h>, so that a host C++ compiler builds this header alone
+// Like marl_brent.h: nothing but <math.h> / <stdint.h> (and marl_brent.h), so that a host C++ compiler builds this header alone
 // (tests/test_bdf_control_cpu.py holds it to scipy's solve_ivp(method="BDF") that way).
 #pragma once
 #include <math.h>
 #include <stdint.h>
+
+#include "marl_brent.h"
 
 #ifdef __HIPCC__
 #define MARL_BDF_FN __host__ __device__ __forceinline__
@@ -36,7 +49,7 @@ namespace bdfctl {
 constexpr int MAX_ORDER = 5, NEWTON_MAXITER = 4;
 constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10;
 
-enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16, A_SAMPLE = 32 };
+enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16, A_SAMPLE = 32, A_ROOTS = 64 };
 enum : int32_t { PC_INIT = 0, PC_STEP, PC_ATTEMPT, PC_SOLVED, PC_SELECT, PC_STEP_END, PC_DONE };
 
 struct BdfCtl {
@@ -74,6 +87,17 @@ struct BdfSample {
     double t, h;                       // the step's end and S_h_abs after the selection (BdfDenseOutput's t, h)
     int64_t first, end;
     int32_t order, pad;
+};
+
+// The root-location state of one instance: a third parallel array (BdfCtl and BdfSample keep their layouts).
+struct BdfRoots {
+    int64_t max_events;                // roots kept per monitor (<= 0: none are located)
+    // A_ROOTS: the dense output of the step just accepted (BdfDenseOutput's t_old, t, h, order) and the monitors to search on it
+    double t_old, t, h;                // the step's start (kept at acceptance), its end and S_h_abs after the selection
+    int32_t order;
+    int32_t pending;                   // bit e: monitor e changed sign over the accepted step (set at acceptance, taken at PC_STEP_END)
+    int32_t mask, pad;                 // bit e: monitor e is searched in this cycle
+    int64_t slot[7];                   // monitor e's root goes to t_events[e * max_events + slot[e]]: its count before this sign change
 };
 
 MARL_BDF_FN double kappa_of(int k) { return k == 1 ? -0.1850 : k == 2 ? -1.0 / 9 : k == 3 ? -0.0823 : k == 4 ? -0.0415 : 0.0; }
@@ -150,9 +174,50 @@ MARL_BDF_FN void bdf_sample_init(BdfSample& s, int64_t n_eval)
     s.n_eval = n_eval;
 }
 
+MARL_BDF_FN void bdf_roots_init(BdfRoots& r, int64_t max_events)
+{
+    r = BdfRoots{};
+    r.max_events = max_events;
+}
+
+// A_ROOTS, the search itself (solve_event_equation, ivp.py:51-76, as accepted_step_epilogue in marl_api.hip runs it for a single run):
+// for every monitor of r.mask in ascending e, a search of its own - both end values from the dense output (not the stored g), then the
+// exact sequence of brent_root: an end point whose value is zero as it is, otherwise brent_advance / evaluate for at most 100 passes and
+// the last iterate.  Equal signs at both ends are no special case (the loop is bounded).  eval(tq, e): monitor e of the step's
+// dense output at tq.  put(e, root): called once for every monitor searched.
+// On the device every thread of a workgroup runs this redundantly on the same values (eval holds the barriers): the control flow
+// depends on nothing but r and what eval returns.
+template <class Eval, class Put>
+MARL_BDF_FN void bdf_find_roots(const BdfRoots& r, Eval&& eval, Put&& put)
+{
+#if defined(__clang__)
+#pragma clang loop unroll(disable)
+#endif
+    for (int e = 0; e < 7; e++) {
+        if (!((r.mask >> e) & 1)) continue;
+        const double fa = eval(r.t_old, e), fb = eval(r.t, e);
+        if (fa == 0) { put(e, r.t_old); continue; }
+        if (fb == 0) { put(e, r.t); continue; }
+        BrentState s = {r.t_old, r.t, 0, fa, fb, 0, 0, 0};
+        for (int it = 0; it < 100; it++) {
+            if (brent_advance(s)) break;
+            s.fcur = eval(s.xcur, e);
+        }
+        put(e, s.xcur);
+    }
+}
+
+// The same with the roots stored: t_events = the instance's [7][max_events] root times.
+template <class Eval>
+MARL_BDF_FN void bdf_locate_roots(const BdfRoots& r, Eval&& eval, double* t_events)
+{
+    bdf_find_roots(r, eval, [&](int e, double root) { t_events[e * r.max_events + r.slot[e]] = root; });
+}
+
 // One instance from where it stopped to its next action word.  n: unknowns (5 N).  g0: the seven monitors of y0 (read at PC_INIT only).
 // s, t_eval: the instance's sampling state and the n_eval sorted sample times (NULL: no samples).
-MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSample* s = nullptr, const double* t_eval = nullptr)
+// r: the instance's root-location state (NULL, or max_events <= 0: sign changes are counted only).
+MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSample* s = nullptr, const double* t_eval = nullptr, BdfRoots* r = nullptr)
 {
     c.action = 0;
     int pc = c.pc;
@@ -237,12 +302,20 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSam
             }
             // accepted
             c.n_equal_steps++;
+            const double t_old = c.t;
             c.t = c.t_new;
             c.S_h_abs = c.h_abs;
             c.n_acc++;
-            for (int e = 0; e < 7; e++) {         // non-terminal events, both directions (ivp.py:131-156): counted, not located
+            for (int e = 0; e < 7; e++) {         // non-terminal events, both directions (ivp.py:131-156): counted; located at PC_STEP_END (r)
                 const bool up = c.g[e] <= 0 && c.g_new[e] >= 0, down = c.g[e] >= 0 && c.g_new[e] <= 0;
-                if (up || down) c.n_events[e]++;
+                if (up || down) {
+                    if (r && c.n_events[e] < r->max_events) {   // (max_events <= 0: never)
+                        r->pending |= 1 << e;
+                        r->slot[e] = c.n_events[e];
+                        r->t_old = t_old;
+                    }
+                    c.n_events[e]++;
+                }
                 c.g[e] = c.g_new[e];
             }
             c.action = A_ACCEPT;
@@ -277,7 +350,14 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSam
             continue;
         }
         if (pc == PC_STEP_END) {                  // the solve_ivp loop (ivp.py:667-668)
-            bool sampled = false;
+            bool sampled = false;                 // (or searched for roots: the cycle ends here either way)
+            if (r && r->pending) {                // ivp.py:673-694: the roots of this step, on the dense output the samples below read
+                r->mask = r->pending;
+                r->pending = 0;
+                r->t = c.t; r->h = c.S_h_abs; r->order = c.order;
+                c.action |= A_ROOTS;
+                sampled = true;
+            }
             if (s && s->next < s->n_eval && t_eval[s->next] <= c.t) {   // ivp.py:706-723: searchsorted(t_eval, t, side="right")
                 s->t = c.t; s->h = c.S_h_abs; s->order = c.order;
                 s->first = s->next;
@@ -289,7 +369,7 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSam
             }
             if (c.t - c.t_bound >= 0) { c.status = 0; pc = PC_DONE; break; }
             pc = PC_STEP;
-            if (sampled) break;                   // the next step may rescale D: not in the cycle that samples it
+            if (sampled) break;                   // the next step may rescale D: not in the cycle that reads it
             continue;
         }
         break;

@@ -121,25 +121,29 @@ class HipSweepEngine:
             r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
-    def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False, t_eval=None):
+    def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False, t_eval=None, events=False,
+                      max_events=64):
         """scipy BDF semantics (the other implicit method of the reference's Solver, marlpde/parameters.py:205-219) for every instance of
         the shard.  By default the instances run as concurrent SINGLE runs (marl_integrate_bdf, one context and one HIP stream per worker
         thread - ctypes releases the GIL, and a single BDF run of a small grid leaves the GPU mostly idle between its small launches),
         so each instance is bit for bit the single run.  ``batched=True`` runs the shard through the batched kernel set instead
         (marl_sweep_bdf_dev on the batched model, as :meth:`integrate_radau`: per-instance step control on the device, every launch
-        over all instances that need that work; N <= 409): the same decisions up to the controller's scalar arithmetic, no root
-        times.  Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries the samples that instance
+        over all instances that need that work; N <= 409): the same decisions up to the controller's scalar arithmetic.
+        Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries the samples that instance
         reached, ``t`` (n_t,) and ``y`` (5N, n_t), either way: the single runs take them from their own dense output, the batched
-        sweep writes them inside the sweep (marl_sweep_bdf_eval_dev), as :meth:`integrate_radau` does."""
+        sweep writes them inside the sweep (marl_sweep_bdf_eval_dev), as :meth:`integrate_radau` does.  With ``events`` every result
+        carries ``t_events``, the root times of the seven monitors (at most ``max_events`` each), either way too: the batched sweep
+        locates them inside the sweep (marl_sweep_bdf_events_dev), the single runs' are cut to ``max_events``."""
         if batched:
             yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
+            more = {"events": True, "max_events": max_events} if events else {}
             if t_eval is None:
-                res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts)
+                res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
                 return yd.cpu().numpy(), res
             n_eval = int(np.size(t_eval))
             frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
             res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
-                                              y_eval_dev_ptr=frames.data_ptr())
+                                              y_eval_dev_ptr=frames.data_ptr(), **more)
             frames = frames.cpu().numpy()
             for b, r in enumerate(res):
                 r.y = frames[b, :len(r.t)].T.copy()
@@ -165,6 +169,8 @@ class HipSweepEngine:
                     else:
                         one.set_scenario(p)
                     r = one.integrate_bdf(y0[b], t_span, first_step, rtol, atol, t_eval=t_eval, max_attempts=max_attempts)
+                    if events:
+                        r.t_events = [t[:max(int(max_events), 0)] for t in r.t_events]
                     out[b] = r
                     yf[b] = r.y_final
             finally:
@@ -211,13 +217,15 @@ def run_sweep_radau(base_parms, instances, t_span, first_step, rtol, atol, max_a
 
 
 def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                  device=None, engine_factory=None, gather=True, balance="cost", cost=None, batched=False, t_eval=None):
+                  device=None, engine_factory=None, gather=True, balance="cost", cost=None, batched=False, t_eval=None, events=False,
+                  max_events=64):
     """As :func:`run_sweep_radau` with scipy's BDF semantics; on a GPU the rank's instances run as concurrent single runs, or with
     ``batched=True`` (N <= 409) through the batched BDF kernels, all instances advanced together
-    (:meth:`HipSweepEngine.integrate_bdf`).  ``batched`` and ``t_eval`` reach the engine only when asked for; with ``t_eval`` two
-    more elements follow, ``n_frames`` and ``y_eval``, as documented for :func:`run_sweep_rk45` (either way of running the shard)."""
+    (:meth:`HipSweepEngine.integrate_bdf`).  ``batched``, ``t_eval``, ``events`` and ``max_events`` reach the engine only when asked
+    for; with ``t_eval`` two more elements follow, ``n_frames`` and ``y_eval``, and with ``events`` one last element, ``t_events``, as
+    documented for :func:`run_sweep_rk45` (either way of running the shard)."""
     return _run_sweep("integrate_bdf", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, t_eval, batched=batched)
+                      balance, cost, t_eval, events, max_events, batched=batched)
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
