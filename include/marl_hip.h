@@ -186,6 +186,33 @@ int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t
                                int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                                int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
+/* ---- adaptive Bogacki-Shampine RK23 -------------------------------------------------------------
+ * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="RK23", ...): the reference's Solver forwards any solve_ivp method
+ * (marlpde/parameters.py:212-213), and on these stability-limited equations RK23 reaches the same time with 1.6 - 3.1 times fewer
+ * RHS evaluations than RK45.  The method is scipy/integrate/_ivp/rk.py, class RK23 (tableau, order 3, error_estimator_order 2,
+ * n_stages 3) under RungeKutta._step_impl (rk.py:111-176): 3 evaluations per attempt (nfev), step factor 0.9 err^(-1/3), cubic
+ * dense output (RkDenseOutput with the 4 x 3 P) that costs no evaluation.  Arguments, results, argument checks and status codes
+ * are those of the RK45 entry of the same name; messages start with "rk23:".  Grids above one workgroup's window run one launch
+ * per attempt. */
+/* marl_integrate_rk45 with RK23 (rk.py, class RK23; marlpde/parameters.py:212-213) */
+int marl_integrate_rk23(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                        const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                        int64_t max_attempts, marl_stats* stats);
+/* marl_integrate_rk45_dev with RK23 (rk.py, class RK23; marlpde/parameters.py:212-213); synchronises */
+int marl_integrate_rk23_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step,
+                            double rtol, double atol, int64_t max_attempts, marl_stats* stats);
+/* marl_sweep_rk45_dev with RK23 (rk.py, class RK23; marlpde/parameters.py:212-213): N <= 1024 cells, else -1 */
+int marl_sweep_rk23_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol,
+                        double atol, int64_t max_attempts, marl_stats* stats);
+/* marl_sweep_rk45_eval_dev with RK23 (rk.py, class RK23 and RkDenseOutput :560-574; marlpde/parameters.py:212-213) */
+int marl_sweep_rk23_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                             int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                             int64_t* n_done, marl_stats* stats);
+/* marl_sweep_rk45_events_dev with RK23 (rk.py, class RK23; roots as ivp.py:673-694, :51-76; marlpde/parameters.py:212-213) */
+int marl_sweep_rk23_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                               int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,
  * rtol=, atol=, t_eval=, events=[7 monitors])  as called at marlpde/Evolve_scenario.py:104-109 with the defaults of

@@ -7,12 +7,14 @@ reference (Evolve_scenario.py:19) and returns the same tuple
 * ``solver_parms["backend"] == "hip"`` and ``method == "RK45"``: the whole adaptive loop
   (scipy-exact Dormand-Prince controller, the seven monitors with root finding, ``t_eval`` by dense
   output) runs on the GPU via ``marl_integrate_rk45``.
+* ``backend == "hip"`` and ``method == "RK23"``: the same loop with scipy's Bogacki-Shampine 3(2) pair (3 RHS evaluations per
+  attempt, step factor ``0.9 err^(-1/3)``, cubic dense output) via ``marl_integrate_rk23`` - no scipy in the loop.
 * ``backend == "hip"`` and ``method == "Radau"`` (the reference's default, parameters.py:213): scipy's Radau IIA step
   logic restated natively, with the RHS, the finite-difference Jacobian (the reference's 27-diagonal pattern), the
   block-tridiagonal LU factorisations and every vector operation on the GPU via ``marl_integrate_radau`` - no scipy in the loop.
 * ``backend == "hip"`` and ``method == "BDF"``: scipy's BDF step logic restated natively on the same Jacobian /
   factorisation kernels via ``marl_integrate_bdf`` - no scipy in the loop either.
-* ``backend == "hip"`` and any other scipy method (RK23, DOP853, LSODA with the reference's ``lband = uband = 1``; or any
+* ``backend == "hip"`` and any other scipy method (DOP853, LSODA with the reference's ``lband = uband = 1``; or any
   method with ``solver_parms["scipy_driver"] = True``): scipy's ``solve_ivp`` drives, exactly as in the reference
   (:104-109), with the HIP RHS and HIP monitors as callables
   (``test_every_other_method_of_the_reference_solver_runs_through_scipy_on_the_hip_rhs``).
@@ -62,9 +64,10 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     no_progress_updates = tracker_parms.get("no_progress_updates", 100_000)
     start = time.time()
     scipy_driver = bool(solver_parms.pop("scipy_driver", False))
-    if method == "RK45" and not scipy_driver:
-        res = eq.integrate_rk45(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"],
-                                t_eval=t_eval)
+    if method in ("RK45", "RK23") and not scipy_driver:
+        integrate = eq.integrate_rk45 if method == "RK45" else eq.integrate_rk23
+        res = integrate(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"],
+                        t_eval=t_eval)
         t_out, y_out, t_events = res.t, res.y, res.t_events
         nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
         if status not in (0, -1):

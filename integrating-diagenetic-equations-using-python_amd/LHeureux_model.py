@@ -331,6 +331,16 @@ class LMAHeureuxPorosityDiff:
 
         Returns an :class:`RK45Result` whose ``t``/``y`` hold the ``t_eval`` samples (``y``: (5N, n_t), as
         scipy) or, without ``t_eval``, the end point only; ``t_events`` is a list of 7 arrays."""
+        return self._integrate_rk("rk45", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
+    def integrate_rk23(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
+                       max_attempts=0):
+        """scipy ``solve_ivp(method="RK23")`` semantics for ONE instance, entirely on the device (marl_integrate_rk23):
+        :meth:`integrate_rk45` with Bogacki-Shampine 3(2) - 3 RHS evaluations per attempt, cubic dense output.  Same result."""
+        return self._integrate_rk("rk23", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
+    def _integrate_rk(self, method, y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts):
+        entry = getattr(self._lib, f"marl_integrate_{method}")
         y_start = self._host_state(y0)
         n = y_start.size
         te = None if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64)
@@ -340,11 +350,11 @@ class LMAHeureuxPorosityDiff:
             stats = MarlStats()
             y_eval = np.empty((max(n_eval, 1), n))
             tev = np.full((NEVENTS, max_events), np.nan) if events else None
-            rc = self._lib.marl_integrate_rk45(
+            rc = entry(
                 self._ctx, _as_ptr(y), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
                 _as_ptr(te) if n_eval else None, n_eval, _as_ptr(y_eval) if n_eval else None,
                 _as_ptr(tev) if events else None, max_events if events else 0, int(max_attempts), C.byref(stats))
-            self._check(rc, "marl_integrate_rk45")
+            self._check(rc, f"marl_integrate_{method}")
             most = max(stats.n_events[:]) if events else 0
             if most <= max_events:
                 break
@@ -453,10 +463,17 @@ class LMAHeureuxPorosityDiff:
         return x_r if b_c is None else (x_r, x_c)
 
     def integrate_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, layout=LAYOUT_FIELD_MAJOR, max_attempts=0):
+        return self._integrate_rk_device("rk45", y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts)
+
+    def integrate_rk23_device(self, y_dev_ptr, t_span, first_step, rtol, atol, layout=LAYOUT_FIELD_MAJOR, max_attempts=0):
+        """:meth:`integrate_rk45_device` with RK23 (marl_integrate_rk23_dev)."""
+        return self._integrate_rk_device("rk23", y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts)
+
+    def _integrate_rk_device(self, method, y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts):
         stats = MarlStats()
-        rc = self._lib.marl_integrate_rk45_dev(self._ctx, C.c_void_p(y_dev_ptr), layout, float(t_span[0]), float(t_span[1]),
+        rc = getattr(self._lib, f"marl_integrate_{method}_dev")(self._ctx, C.c_void_p(y_dev_ptr), layout, float(t_span[0]), float(t_span[1]),
                                                float(first_step), float(rtol), float(atol), int(max_attempts), C.byref(stats))
-        self._check(rc, "marl_integrate_rk45_dev")
+        self._check(rc, f"marl_integrate_{method}_dev")
         return RK45Result(stats)
 
     def sweep_radau_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None, events=False, max_events=64,
@@ -555,25 +572,34 @@ class LMAHeureuxPorosityDiff:
         ``events=True``: the monitors' root times are located inside the sweep (marl_sweep_rk45_events_dev) and returned as
         ``t_events`` - a list of 7 arrays per instance, ``min(n_events[e], max_events)`` long, what the reference prints and stores
         for every run (Evolve_scenario.py:118-145, 175-177); otherwise sign changes are only counted.  Combinable with ``t_eval``."""
+        return self._sweep_rk_device("rk45", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events)
+
+    def sweep_rk23_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
+                          events=False, max_events=64):
+        """:meth:`sweep_rk45_device` with RK23 (marl_sweep_rk23_dev / _eval_dev / _events_dev): the same arguments and results."""
+        return self._sweep_rk_device("rk23", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events)
+
+    def _sweep_rk_device(self, method, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events):
+        plain, with_eval, with_events = (f"marl_sweep_{method}_dev", f"marl_sweep_{method}_eval_dev", f"marl_sweep_{method}_events_dev")
         stats = (MarlStats * self.n_instances)()
         locate = bool(events) and int(max_events) > 0
         if t_eval is None and not locate:
-            rc = self._lib.marl_sweep_rk45_dev(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]),
+            rc = getattr(self._lib, plain)(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]),
                                                float(first_step), float(rtol), float(atol), int(max_attempts), stats)
-            self._check(rc, "marl_sweep_rk45_dev")
+            self._check(rc, plain)
             return [RK45Result(s) for s in stats]
         te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
         if te.size and not y_eval_dev_ptr:
-            raise ValueError("sweep_rk45_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
+            raise ValueError(f"sweep_{method}_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
         n_done = np.zeros(self.n_instances, dtype=np.int64)
         args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
                 int(max_attempts), _as_ptr(te) if te.size else None, te.size, C.c_void_p(y_eval_dev_ptr) if te.size else None,
                 _as_ptr(n_done))
         if not locate:
-            self._check(self._lib.marl_sweep_rk45_eval_dev(*args, stats), "marl_sweep_rk45_eval_dev")
+            self._check(getattr(self._lib, with_eval)(*args, stats), with_eval)
             return [RK45Result(s, t=te[:int(k)].copy()) for s, k in zip(stats, n_done)]
         tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan)
-        self._check(self._lib.marl_sweep_rk45_events_dev(*args, _as_ptr(tev), int(max_events), stats), "marl_sweep_rk45_events_dev")
+        self._check(getattr(self._lib, with_events)(*args, _as_ptr(tev), int(max_events), stats), with_events)
         return [RK45Result(s, t=None if t_eval is None else te[:int(k)].copy(),
                            t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
                 for b, (s, k) in enumerate(zip(stats, n_done))]

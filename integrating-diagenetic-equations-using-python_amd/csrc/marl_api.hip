@@ -14,6 +14,7 @@
 
 #include "../../include/marl_hip.h"
 #include "marl_kernels.h"
+#include "marl_rk23_ctl.h"
 #include "marl_radau.h"
 #include "marl_radau_cr.h"
 #include "marl_radau_batch.h"
@@ -820,12 +821,33 @@ static int sweep_block(const marl_ctx* ctx)
 
 // ---- fused RK45 --------------------------------------------------------------------------------
 // One shape: 256-thread windows that write 256 - 2 * 6 cells (option rk45_variant is accepted and ignored: only 0 ever existed).
-static int64_t rk45_blocks(const marl_ctx* ctx)
+static int64_t rk_blocks(const marl_ctx* ctx, int written)
 {
-    const int V = 256 - 12;
     const int64_t n = ctx->slab.out_hi - ctx->slab.out_lo;
-    return (n + V - 1) / V;
+    return (n + written - 1) / written;
 }
+static int64_t rk45_blocks(const marl_ctx* ctx) { return rk_blocks(ctx, 256 - 12); }
+
+// ---- the explicit adaptive methods behind one set of host drivers (rk_run, sweep_rk) --------------------------------------------
+// RK45: the kernels of marl_kernels.h, launched here.  RK23: those of marl_rk23.h, a translation unit of its own (marl_rk23.hip),
+// reached through its launchers.  What differs between the two on the host is in this table and nowhere else.
+enum : int { SWEEP_PLAIN = 0, SWEEP_EVENTS = 1, SWEEP_EVAL = 2, SWEEP_ROOTS = 3 };   // the four one-workgroup kernels of a method
+struct SweepLaunch {
+    double *Y, *Yold, *Fold;
+    const double* t_eval; int64_t n_eval; double* Yeval; int64_t* n_done;
+    double* t_events; int64_t max_events;
+};
+struct RkMethod {
+    const char* name;        // in front of error messages: "rk45", "rk23"
+    const char* sweep_entry; // the entry named when a grid does not fit one workgroup
+    int written;             // cells a 256-thread window of the attempt kernel writes: 256 - 2 * (evaluations after K1)
+    bool can_stream;         // has a persistent device-wide-barrier loop (rk45_stream_kernel)
+    int (*sweep)(marl_ctx*, int kind, int blk, unsigned batch, const SweepLaunch&);
+    int (*attempt)(marl_ctx*, int64_t nb, int layout);
+    int (*control)(marl_ctx*, const double* recs, int64_t nrec);
+    int (*dense)(marl_ctx*, int64_t nb, int layout, const double* yold, const double* fold, double h, const DenseWeights& dw, double* yout);
+    void (*weights)(double x, DenseWeights* dw);   // w_j(x) of the dense output
+};
 
 constexpr int64_t kReduceGroups = 64;
 template <bool VD = false>
@@ -852,17 +874,14 @@ static const double* reduce_first_level(marl_ctx* ctx, int64_t* nrec)
     return out;
 }
 
-static int launch_attempt(marl_ctx* ctx, int layout)
+static int launch_attempt(marl_ctx* ctx, int layout, const RkMethod& m)
 {
-    const int64_t nb = rk45_blocks(ctx);
-    if (ctx->var_dphi) launch_attempt_t<true>(ctx, nb, layout); else launch_attempt_t<>(ctx, nb, layout);
-    LAUNCH_OK(ctx);
+    const int64_t nb = rk_blocks(ctx, m.written);
+    if (int rc = m.attempt(ctx, nb, layout)) return rc;
     int64_t nrec = nb;
     const double* recs = reduce_first_level(ctx, &nrec);
     LAUNCH_OK(ctx);
-    hipLaunchKernelGGL(rk45_control_kernel, dim3(1), dim3(CONTROL_THREADS), 0, ctx->stream, recs, nrec, ctx->dctrl);
-    LAUNCH_OK(ctx);
-    return 0;
+    return m.control(ctx, recs, nrec);
 }
 
 // ---- the adaptive loop of one grid as ONE launch per batch of attempts (rk45_stream_kernel) ----------------------------------
@@ -979,24 +998,107 @@ static void launch_dense_t(marl_ctx* ctx, int64_t nb, int layout, const double* 
 // Dense output P (dp::P, marl_kernels.h): w_j(x) = sum_m P[j][m] x^(m+1)
 static constexpr auto& kDpP = dp::P;
 
-// Evaluate the dense output of the LAST accepted step at time t: state into yout (may be NULL) and the
-// seven monitors into g (may be NULL; synchronises when given).
-static int dense_eval(marl_ctx* ctx, int layout, bool small, const Rk45Ctrl& c, double t, double* yout, double* g)
+// ---- the method table's two rows ------------------------------------------------------------------------------------------------
+static int rk45_m_sweep(marl_ctx* ctx, int kind, int blk, unsigned batch, const SweepLaunch& a)
 {
-
-    const double x = (t - c.t_old) / c.h_prev;
-    DenseWeights dw;
+    const dim3 grid(batch);
+    switch (kind) {
+        case SWEEP_PLAIN: SWEEP_DISPATCH(rk45_sweep_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.Yold, a.Fold) break;
+        case SWEEP_EVENTS: SWEEP_DISPATCH(rk45_sweep_events_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.Yold, a.Fold) break;
+        case SWEEP_EVAL: SWEEP_DISPATCH(rk45_sweep_eval_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.t_eval, a.n_eval, a.Yeval, a.n_done) break;
+        default: SWEEP_DISPATCH(rk45_sweep_roots_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events,
+                                a.max_events) break;
+    }
+    LAUNCH_OK(ctx);
+    return 0;
+}
+static int rk45_m_attempt(marl_ctx* ctx, int64_t nb, int layout)
+{
+    if (ctx->var_dphi) launch_attempt_t<true>(ctx, nb, layout); else launch_attempt_t<>(ctx, nb, layout);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+static int rk45_m_control(marl_ctx* ctx, const double* recs, int64_t nrec)
+{
+    hipLaunchKernelGGL(rk45_control_kernel, dim3(1), dim3(CONTROL_THREADS), 0, ctx->stream, recs, nrec, ctx->dctrl);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+static int rk45_m_dense(marl_ctx* ctx, int64_t nb, int layout, const double* yold, const double* fold, double h, const DenseWeights& dw, double* yout)
+{
+    if (ctx->var_dphi) launch_dense_t<true>(ctx, nb, layout, yold, fold, h, dw, yout); else launch_dense_t<>(ctx, nb, layout, yold, fold, h, dw, yout);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+static void rk45_m_weights(double x, DenseWeights* dw)
+{
     double pw[4] = {x, x * x, x * x * x, x * x * x * x};
     for (int j = 0; j < 7; j++) {
         double a = 0;
         for (int m = 0; m < 4; m++) a += kDpP[j][m] * pw[m];
-        dw.w[j] = a;
+        dw->w[j] = a;
     }
+}
+static const RkMethod kRk45 = {"rk45", "marl_sweep_rk45_dev", 256 - 2 * 6, true, rk45_m_sweep, rk45_m_attempt, rk45_m_control, rk45_m_dense, rk45_m_weights};
+
+// marl_rk23.hip
+extern "C" {
+int marl_rk23_launch_sweep(int kind, int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls, int64_t N,
+                           double* Yold, double* Fold, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events,
+                           int64_t max_events);
+int marl_rk23_launch_attempt(int tiled, int vd, unsigned nb, hipStream_t stream, double* Y0, double* Y1, double* F0, double* F1, const void* consts,
+                             const int64_t slab5[5], const void* ctrl, double* part);
+int marl_rk23_launch_control(hipStream_t stream, const double* recs, int64_t nrec, void* ctrl);
+int marl_rk23_launch_dense(int tiled, int vd, unsigned nb, hipStream_t stream, const double* yold, const double* fold, const void* consts,
+                           const int64_t slab5[5], double h, const double w[7], double* yout, double* part);
+}
+static int rk23_launched(marl_ctx* ctx, int err)
+{
+    if (err != (int)hipSuccess) return fail(ctx, -3, "rk23: kernel launch failed: %s", hipGetErrorString((hipError_t)err));
+    return 0;
+}
+static int rk23_m_sweep(marl_ctx* ctx, int kind, int blk, unsigned batch, const SweepLaunch& a)
+{
+    return rk23_launched(ctx, marl_rk23_launch_sweep(kind, blk, ctx->var_dphi ? 1 : 0, batch, ctx->stream, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.Yold,
+                                                     a.Fold, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events));
+}
+static int rk23_m_attempt(marl_ctx* ctx, int64_t nb, int layout)
+{
+    const Slab& S = ctx->slab;
+    const int64_t slab5[5] = {S.n_buf, S.goff, S.ld, S.out_lo, S.out_hi};
+    return rk23_launched(ctx, marl_rk23_launch_attempt(layout == LAYOUT_TILED, ctx->var_dphi ? 1 : 0, (unsigned)nb, ctx->stream, ctx->buf[0], ctx->buf[1],
+                                                       ctx->buf[2], ctx->buf[3], ctx->dconsts, slab5, ctx->dctrl, ctx->part));
+}
+static int rk23_m_control(marl_ctx* ctx, const double* recs, int64_t nrec)
+{
+    return rk23_launched(ctx, marl_rk23_launch_control(ctx->stream, recs, nrec, ctx->dctrl));
+}
+static int rk23_m_dense(marl_ctx* ctx, int64_t nb, int layout, const double* yold, const double* fold, double h, const DenseWeights& dw, double* yout)
+{
+    const Slab& S = ctx->slab;
+    const int64_t slab5[5] = {S.n_buf, S.goff, S.ld, S.out_lo, S.out_hi};
+    return rk23_launched(ctx, marl_rk23_launch_dense(layout == LAYOUT_TILED, ctx->var_dphi ? 1 : 0, (unsigned)nb, ctx->stream, yold, fold, ctx->dconsts,
+                                                     slab5, h, dw.w, yout, ctx->part));
+}
+static void rk23_m_weights(double x, DenseWeights* dw)
+{
+    double w[4];
+    rk23_dense_weights(x, w);
+    for (int j = 0; j < 7; j++) dw->w[j] = j < 4 ? w[j] : 0.0;
+}
+// (large grids always go launch-per-attempt: three evaluations after K1, so a window writes 256 - 2 * 3 = 250 cells)
+static const RkMethod kRk23 = {"rk23", "marl_sweep_rk23_dev", 256 - 2 * 3, false, rk23_m_sweep, rk23_m_attempt, rk23_m_control, rk23_m_dense, rk23_m_weights};
+
+// Evaluate the dense output of the LAST accepted step at time t: state into yout (may be NULL) and the
+// seven monitors into g (may be NULL; synchronises when given).
+static int dense_eval(marl_ctx* ctx, const RkMethod& m, int layout, bool small, const Rk45Ctrl& c, double t, double* yout, double* g)
+{
+    DenseWeights dw;
+    m.weights((t - c.t_old) / c.h_prev, &dw);
     const double* yold = small ? ctx->buf[1] : ctx->buf[c.cur ^ 1];
     const double* fold = small ? ctx->buf[3] : ctx->buf[2 + (c.cur ^ 1)];
-    const int64_t nb = rk45_blocks(ctx);
-    if (ctx->var_dphi) launch_dense_t<true>(ctx, nb, layout, yold, fold, c.h_prev, dw, yout); else launch_dense_t<>(ctx, nb, layout, yold, fold, c.h_prev, dw, yout);
-    LAUNCH_OK(ctx);
+    const int64_t nb = rk_blocks(ctx, m.written);
+    if (int rc = m.dense(ctx, nb, layout, yold, fold, c.h_prev, dw, yout)) return rc;
     if (g) {
         hipLaunchKernelGGL(reduce_records_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->part, nb, ctx->rec);
         LAUNCH_OK(ctx);
@@ -1047,14 +1149,14 @@ static int check_ivp_args(marl_ctx* ctx, const char* name, double t0, double t1,
 // The adaptive loop on device buffers buf[0..3] (`layout`), state already in buf[0].
 // small = true: the grid fits one workgroup -> the persistent sweep kernel runs all attempts on-chip
 // (state in buf[0], FIELD-MAJOR; (y_old, f_old) of a paused step in buf[1], buf[3]).
-static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1, double first_step, double rtol, double atol,
+static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, double t0, double t1, double first_step, double rtol, double atol,
                     const double* t_eval, int64_t n_eval, double* y_eval_dev, double* t_events, int64_t max_events,
                     int64_t max_attempts, marl_stats* stats)
 {
-    if (int rc = check_ivp_args(ctx, "rk45", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
+    if (int rc = check_ivp_args(ctx, m.name, t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
     rtol = clamp_rtol(rtol);
     const int blk = small ? sweep_block(ctx) : 0;
-    const int64_t nb = rk45_blocks(ctx);
+    const int64_t nb = rk_blocks(ctx, m.written);
     if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(nb + kReduceGroups, 1024))) return rc;
     const int64_t sd = state_doubles(ctx->slab.n_buf, layout);
     // f(t0, y0) and the monitors at t0
@@ -1080,22 +1182,18 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
     int64_t seen_events[7] = {0, 0, 0, 0, 0, 0, 0};
     Rk45Ctrl& hc = *ctx->hctrl;
     int64_t executed = 0;   // attempts the device has finished, as of the last status read
-    const bool streamed = !small && rk45_use_stream(ctx);   // one launch per batch of attempts (rk45_stream_kernel)
+    const bool streamed = !small && m.can_stream && rk45_use_stream(ctx);   // one launch per batch of attempts (rk45_stream_kernel)
     while (true) {
         if (small) {
-            const dim3 grid(1);
-            if (events_on) {   // pauses on monitor sign changes (root finding): the loop shape that decides with this step's events
-                SWEEP_DISPATCH(rk45_sweep_events_kernel, ctx->buf[0], ctx->dconsts, ctx->dctrl, ctx->N, ctx->buf[1], ctx->buf[3])
-            } else {
-                SWEEP_DISPATCH(rk45_sweep_kernel, ctx->buf[0], ctx->dconsts, ctx->dctrl, ctx->N, ctx->buf[1], ctx->buf[3])
-            }
-            LAUNCH_OK(ctx);
+            // events: pauses on monitor sign changes (root finding) - the loop shape that decides with this step's events
+            const SweepLaunch a = {ctx->buf[0], ctx->buf[1], ctx->buf[3], nullptr, 0, nullptr, nullptr, nullptr, 0};
+            if (int rc = m.sweep(ctx, events_on ? SWEEP_EVENTS : SWEEP_PLAIN, blk, 1, a)) return rc;
         } else if (streamed) {
             if (int rc = launch_rk45_stream(ctx, layout, ctx->rk45_stream_attempts)) return rc;
         } else {
             const int64_t batch = attempts_per_batch(ctx->poll, max_attempts, executed);
             for (int64_t i = 0; i < batch; i++)
-                if (int rc = launch_attempt(ctx, layout)) return rc;
+                if (int rc = launch_attempt(ctx, layout, m)) return rc;
         }
         HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1111,11 +1209,11 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
                 if (hc.n_events[e] > seen_events[e]) {
                     // only the newest sign change can be refined (earlier ones were refined at their own pause)
                     double ga[7];
-                    if (int rc = dense_eval(ctx, layout, small, hc, hc.t_old, nullptr, ga)) return rc;
+                    if (int rc = dense_eval(ctx, m, layout, small, hc, hc.t_old, nullptr, ga)) return rc;
                     double root = hc.ev_last[e];
                     auto monitor_at = [&](double tq, double* v) -> int {   // monitor e on the step's dense output (solve_event_equation, ivp.py:51-76)
                         double gq[7];
-                        if (int rc = dense_eval(ctx, layout, small, hc, tq, nullptr, gq)) return rc;
+                        if (int rc = dense_eval(ctx, m, layout, small, hc, tq, nullptr, gq)) return rc;
                         *v = gq[e];
                         return 0;
                     };
@@ -1132,7 +1230,7 @@ static int rk45_run(marl_ctx* ctx, int layout, bool small, double t0, double t1,
                 double* dst = y_eval_dev + eval_i * sd;
                 if (t_eval[eval_i] <= hc.t_old && hc.n_acc == 1 && t_eval[eval_i] == t0) {
                     HIP_OK(ctx, hipMemcpyAsync(dst, small ? ctx->buf[1] : ctx->buf[hc.cur ^ 1], sizeof(double) * sd, hipMemcpyDeviceToDevice, ctx->stream));
-                } else if (int rc = dense_eval(ctx, layout, small, hc, t_eval[eval_i], dst, nullptr)) return rc;
+                } else if (int rc = dense_eval(ctx, m, layout, small, hc, t_eval[eval_i], dst, nullptr)) return rc;
                 eval_i++;
             }
         } else {
@@ -1170,7 +1268,7 @@ static int grow_dev(marl_ctx* ctx, double** buf, size_t* cap, size_t n)
 // The RK45 sweep behind marl_sweep_rk45_dev / _eval_dev / _events_dev (`entry`: the one the caller used).  Neither samples (n_eval == 0)
 // nor roots (no t_events or max_events <= 0): rk45_sweep_kernel; samples only: rk45_sweep_eval_kernel; roots, with samples or
 // without: rk45_sweep_roots_kernel.
-static int sweep_rk45(const char* entry, marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+static int sweep_rk(const RkMethod& m, const char* entry, marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                       int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, double* t_events,
                       int64_t max_events, marl_stats* stats)
 {
@@ -1178,14 +1276,14 @@ static int sweep_rk45(const char* entry, marl_ctx* ctx, double* y_dev, double t0
         return ctx ? fail(ctx, -1, "%s: invalid argument", entry) : -1;
     const bool frames = n_eval > 0, roots = t_events && max_events > 0;
     if (!frames && !roots && n_done) memset(n_done, 0, sizeof(int64_t) * ctx->batch);   // nothing to sample: the plain sweep itself
-    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "rk45: need first_step > 0 and t1 >= t0 (forward integration)");
-    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "rk45: `first_step` exceeds bounds");
+    if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "%s: need first_step > 0 and t1 >= t0 (forward integration)", m.name);
+    if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "%s: `first_step` exceeds bounds", m.name);
     for (int64_t i = 0; i < n_eval; i++)
         if (!(t_eval[i] >= t0) || !(t_eval[i] <= t1) || (i > 0 && t_eval[i] <= t_eval[i - 1]))
-            return fail(ctx, -1, "rk45: `t_eval` must be sorted and within t_span");  // ivp.py:603-609
+            return fail(ctx, -1, "%s: `t_eval` must be sorted and within t_span", m.name);  // ivp.py:603-609
     HIP_OK(ctx, hipSetDevice(ctx->device));
     const int blk = sweep_block(ctx);
-    if (!blk) return fail(ctx, -1, "marl_sweep_rk45_dev: N = %lld exceeds the largest one-workgroup window (1024 cells)", (long long)ctx->N);
+    if (!blk) return fail(ctx, -1, "%s: N = %lld exceeds the largest one-workgroup window (1024 cells)", m.sweep_entry, (long long)ctx->N);
     const size_t n_tev = roots ? (size_t)ctx->batch * 7 * (size_t)max_events : 0;
     if (frames)
         if (int rc = grow_dev(ctx, &ctx->sw_teval, &ctx->sw_teval_cap, (size_t)n_eval)) return rc;
@@ -1201,16 +1299,8 @@ static int sweep_rk45(const char* entry, marl_ctx* ctx, double* y_dev, double t0
     hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
                        atol, (int64_t)NF * ctx->N, max_attempts, 0);
     LAUNCH_OK(ctx);
-    const dim3 grid((unsigned)ctx->batch);
-    if (roots) {
-        SWEEP_DISPATCH(rk45_sweep_roots_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone,
-                       ctx->sw_tev, max_events)
-    } else if (frames) {
-        SWEEP_DISPATCH(rk45_sweep_eval_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (const double*)ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone)
-    } else {
-        SWEEP_DISPATCH(rk45_sweep_kernel, y_dev, ctx->dconsts, ctx->dctrl, ctx->N, (double*)nullptr, (double*)nullptr)
-    }
-    LAUNCH_OK(ctx);
+    const SweepLaunch a = {y_dev, nullptr, nullptr, ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone, ctx->sw_tev, max_events};
+    if (int rc = m.sweep(ctx, roots ? SWEEP_ROOTS : (frames ? SWEEP_EVAL : SWEEP_PLAIN), blk, (unsigned)ctx->batch, a)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
     if ((frames || roots) && n_done) HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
     if (roots) HIP_OK(ctx, hipMemcpyAsync(t_events, ctx->sw_tev, sizeof(double) * n_tev, hipMemcpyDeviceToHost, ctx->stream));
@@ -1342,14 +1432,14 @@ int marl_integrate_rk4(marl_ctx* ctx, double* y, double dt, int64_t nsteps)
 int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                         int64_t max_attempts, marl_stats* stats)
 {
-    return sweep_rk45("marl_sweep_rk45_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
+    return sweep_rk(kRk45, "marl_sweep_rk45_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
 }
 
 int marl_sweep_rk45_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                              int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
                              marl_stats* stats)
 {
-    return sweep_rk45("marl_sweep_rk45_eval_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+    return sweep_rk(kRk45, "marl_sweep_rk45_eval_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
                       nullptr, 0, stats);
 }
 
@@ -1357,32 +1447,36 @@ int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t
                                int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
                                double* t_events, int64_t max_events, marl_stats* stats)
 {
-    return sweep_rk45("marl_sweep_rk45_events_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+    return sweep_rk(kRk45, "marl_sweep_rk45_events_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
                       t_events, max_events, stats);
 }
 
-int marl_integrate_rk45_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
+// marl_integrate_<method>_dev
+static int integrate_rk_dev(const RkMethod& m, marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
                             double atol, int64_t max_attempts, marl_stats* stats)
 {
-    if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_integrate_rk45_dev: invalid argument") : -1;
-    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_rk45_dev: single-instance context required (use marl_sweep_rk45_dev)");
+    if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_integrate_%s_dev: invalid argument", m.name) : -1;
+    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s_dev: single-instance context required (use %s)", m.name, m.sweep_entry);
+    if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
     const size_t sd = (size_t)state_doubles(ctx->slab.n_buf, layout);
     for (int i = 0; i < 4; i++)
         if (int rc = ensure(ctx, i, sd)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(ctx->buf[0], y_dev, sd * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    if (int rc = rk45_run(ctx, layout, false, t0, t1, first_step, rtol, atol, nullptr, 0, nullptr, nullptr, 0, max_attempts, stats)) return rc;
+    if (int rc = rk_run(m, ctx, layout, false, t0, t1, first_step, rtol, atol, nullptr, 0, nullptr, nullptr, 0, max_attempts, stats)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(y_dev, ctx->buf[0], sd * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
-int marl_integrate_rk45(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+// marl_integrate_<method>
+static int integrate_rk(const RkMethod& m, marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
                         const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
                         int64_t max_attempts, marl_stats* stats)
 {
-    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_rk45: invalid argument") : -1;
-    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_rk45: single-instance context required (use marl_sweep_rk45_dev)");
+    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_%s: invalid argument", m.name) : -1;
+    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s: single-instance context required (use %s)", m.name, m.sweep_entry);
+    if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
     const bool small = sweep_block(ctx) > 0;
     const int layout = small ? LAYOUT_FIELD_MAJOR : (int)ctx->host_layout;
@@ -1395,7 +1489,7 @@ int marl_integrate_rk45(marl_ctx* ctx, double* y, double t0, double t1, double f
     if (int rc = launch_convert(ctx, ctx->buf[1], ctx->buf[0], LAYOUT_FIELD_MAJOR, layout)) return rc;
     double* yev = nullptr;
     if (n_eval > 0) HIP_OK(ctx, hipMalloc((void**)&yev, sizeof(double) * sd * (size_t)(n_eval + 1)));
-    int rc = rk45_run(ctx, layout, small, t0, t1, first_step, rtol, atol, t_eval, n_eval, yev, t_events, max_events, max_attempts, stats);
+    int rc = rk_run(m, ctx, layout, small, t0, t1, first_step, rtol, atol, t_eval, n_eval, yev, t_events, max_events, max_attempts, stats);
     if (rc == 0) {
         // results back to field-major through a spare slot
         for (int64_t i = 0; i < n_eval && rc == 0; i++) {
@@ -1411,6 +1505,55 @@ int marl_integrate_rk45(marl_ctx* ctx, double* y, double t0, double t1, double f
     }
     if (yev) (void)hipFree(yev);
     return rc;
+}
+
+int marl_integrate_rk45_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
+                            double atol, int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk_dev(kRk45, ctx, y_dev, layout, t0, t1, first_step, rtol, atol, max_attempts, stats);
+}
+
+int marl_integrate_rk45(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                        const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                        int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk(kRk45, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats);
+}
+
+// ---- RK23: the RK45 entries with the method swapped (include/marl_hip.h) ----
+int marl_integrate_rk23_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
+                            double atol, int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk_dev(kRk23, ctx, y_dev, layout, t0, t1, first_step, rtol, atol, max_attempts, stats);
+}
+
+int marl_integrate_rk23(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                        const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                        int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk(kRk23, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats);
+}
+
+int marl_sweep_rk23_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                        int64_t max_attempts, marl_stats* stats)
+{
+    return sweep_rk(kRk23, "marl_sweep_rk23_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
+}
+
+int marl_sweep_rk23_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                             int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                             marl_stats* stats)
+{
+    return sweep_rk(kRk23, "marl_sweep_rk23_eval_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    nullptr, 0, stats);
+}
+
+int marl_sweep_rk23_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                               double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_rk(kRk23, "marl_sweep_rk23_events_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    t_events, max_events, stats);
 }
 
 
@@ -1687,7 +1830,7 @@ int marl_slab_run(marl_ctx* ctx, marl_stats* stats)
             } else {
                 const int64_t batch = attempts_per_batch(ctx->poll, ctx->dd_max_attempts, executed);
                 for (int64_t i = 0; i < batch; i++)
-                    if (int rc = launch_attempt(ctx, LAYOUT_FIELD_MAJOR)) return rc;
+                    if (int rc = launch_attempt(ctx, LAYOUT_FIELD_MAJOR, kRk45)) return rc;
             }
             HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl), hipMemcpyDeviceToHost, ctx->stream));
             HIP_OK(ctx, hipStreamSynchronize(ctx->stream));

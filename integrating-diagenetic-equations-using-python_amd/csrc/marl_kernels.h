@@ -29,6 +29,7 @@
 
 #include "marl_math.h"
 #include "marl_brent.h"
+#include "marl_rk_ctrl.h"
 
 namespace marl {
 
@@ -994,30 +995,7 @@ constexpr double P[7][4] = {
 }  // namespace dp
 
 
-enum : int { ST_DONE = 0, ST_RUNNING = 1, ST_BUDGET = 2, ST_PAUSED = 3, ST_TOO_SMALL = -1 };
-
-// Device-resident step controller: the scalar state of scipy's RungeKutta._step_impl
-// (rk.py:111-176) plus the driver's event bookkeeping (ivp.py:673-694).  One per instance.
-// Plain data; mirrored field for field by the ctypes structure in _abi.py.
-struct Rk45Ctrl {
-    double t, h_abs, t_bound, rtol, atol;
-    double h_try, t_new;     // the attempt in flight (h_try = t_new - t, clipped at t_bound)
-    double t_old, h_prev;    // last accepted step [t_old, t_old + h_prev] (dense output)
-    double err_norm;         // error norm of the last attempt
-    double pause_t;          // pause (ST_PAUSED) after the accepted step that reaches this time; +inf = never
-    double g[7];             // monitors at the last accepted state (ivp.py:645, :694)
-    double ev_first[7];      // first / latest sign change per monitor, located by linear interpolation
-    double ev_last[7];       //   inside the bracketing step (the host refines with dense output + Brent)
-    int64_t n_events[7];
-    int64_t nfev, n_acc, n_rej, attempts, max_attempts;
-    int64_t n_total;         // 5 * N of the global grid: size of the RMS norm (common.py:63-65)
-    int32_t status;          // ST_*
-    int32_t cur;             // which of the two state / FSAL buffers holds (y, f) at time t
-    int32_t rejected;        // a rejection happened in the step in progress (rk.py:128,163-165)
-    int32_t accepted_last;   // the last attempt was accepted
-    int32_t pause_on_event;  // pause after an accepted step in which a monitor changed sign
-    int32_t event_fired;     // set with ST_PAUSED when that was the reason
-};
+// (ST_* and struct Rk45Ctrl, the device-resident step controller: marl_rk_ctrl.h)
 
 // Top of RungeKutta._step_impl: choose the step of the next attempt (rk.py:119-142).
 __device__ __forceinline__ void rk45_prepare_attempt(Rk45Ctrl& c)
@@ -2106,17 +2084,25 @@ __device__ __forceinline__ DenseWeights dense_weights(double x)
     return dw;
 }
 
+// What rk45_sweep_body asks of a method M other than Dormand-Prince (Bs23Method, marl_rk23.h): N_WEIGHTS, the slots of DenseWeights
+// its dense output fills, and static members attempt<BLK, SB, PARK, EITHER> (the arguments of dp45_attempt), finish_attempt,
+// decide_lean, prepare_attempt_lean and weights, the counterparts of dp45_attempt, rk45_finish_attempt, rk45_decide_lean, rk45_prepare_attempt_lean and dense_weights.  For Dp45Method
+// itself the body calls those functions BY NAME, as it did before it had this parameter: through forwarding members the RK45 kernels
+// came out with the same instructions in another order (the ghost-cell arithmetic of the boundary branch moved), and they are pinned.
+struct Dp45Method { static constexpr int N_WEIGHTS = 7; };
+
 // EVAL (FAST only; rk45_sweep_eval_kernel): the t_eval samples that fall into an accepted step are written by dense-output replays of
 // that step inside the loop (see there); without it the four trailing arguments are unused and the code is what it was without them.
 // ROOTS (FAST and EVAL only; rk45_sweep_roots_kernel): the root times of the monitors that change sign in an accepted step are located
 // by Brent's method on dense-output replays of that step, before its samples and its commit (see there); two more arguments.
-template <int BLK, bool VD, bool FAST, bool EVAL = false, bool ROOTS = false>
+template <int BLK, bool VD, bool FAST, bool EVAL = false, bool ROOTS = false, class M = Dp45Method>
 __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls, int64_t N,
                                                 double* __restrict__ Yold, double* __restrict__ Fold,
                                                 const double* __restrict__ t_eval = nullptr, int64_t n_eval = 0,
                                                 double* __restrict__ Yeval = nullptr, int64_t* __restrict__ n_done = nullptr,
                                                 double* __restrict__ t_events = nullptr, int64_t max_events = 0)
 {
+    constexpr bool DP = std::is_same_v<M, Dp45Method>;
     static_assert(FAST || !EVAL, "the sampling loop is built on the replicated controller");
     static_assert((FAST && EVAL) || !ROOTS, "a Brent function evaluation is a dense-output replay");
     using SB = StencilBlock<BLK, false, VD>;
@@ -2158,7 +2144,8 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
     if constexpr (!FAST) {
         while (true) {
             const double h = sc.h_try;
-            dp45_attempt<BLK, false, SB>(sb, h, y, k1, yn, k7, esum, aux);
+            if constexpr (DP) dp45_attempt<BLK, false, SB>(sb, h, y, k1, yn, k7, esum, aux);
+            else M::template attempt<BLK, SB, 0, false>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, nullptr, false);
             double q[NQ];
             monitors_init(q);
             MARL_ONCE if (l0 < N) {
@@ -2167,7 +2154,9 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                 monitors_accumulate(q, yn, aux.U, aux.W);
             }
             block_reduce<BLK, NQ, NQMIN>(q, lds);   // the edge-exchange buffers are free now
-            if (threadIdx.x == 0) rk45_finish_attempt(sc, q, &sb.T);
+            if (threadIdx.x == 0) {
+                if constexpr (DP) rk45_finish_attempt(sc, q, &sb.T); else M::finish_attempt(sc, q, &sb.T);
+            }
             __syncthreads();
             const int status = sc.status;
             if (sc.accepted_last) {
@@ -2217,13 +2206,16 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         bool sampling = false;                       // this trip of the loop replays the step just accepted for sample ie
         double te = 0.0;                             // t_eval[ie] of that replay
         DenseWeights dw = {};                        // w_j(x) of that replay (SGPRs)
+        auto weights_of = [&](double x) -> DenseWeights {
+            if constexpr (DP) return dense_weights(x); else return M::weights(x);
+        };
         auto next_sample = [&]() -> bool {           // is sample ie inside the step just accepted?  then dw = its weights
             if (!(ie < n_eval)) return false;
             te = to_sgpr(t_eval[ie]);
             if (!(te <= c.t)) return false;
-            const DenseWeights w = dense_weights((te - c.t_old) / c.h_prev);
+            const DenseWeights w = weights_of((te - c.t_old) / c.h_prev);
 #pragma unroll
-            for (int j = 0; j < 7; j++) dw.w[j] = to_sgpr(w.w[j]);
+            for (int j = 0; j < M::N_WEIGHTS; j++) dw.w[j] = to_sgpr(w.w[j]);
             return true;
         };
         auto event_bookkeeping = [&]() {             // lanes 0..6 of wave 0: one monitor each; sc.t_old / sc.h_prev / sc.t describe that step
@@ -2247,9 +2239,9 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         BrentState bs = {};
         auto probe_at = [&](double tp) {             // the next trip evaluates the monitors at time tp of the step just accepted
             br_t = to_sgpr(tp);
-            const DenseWeights w = dense_weights((br_t - c.t_old) / c.h_prev);
+            const DenseWeights w = weights_of((br_t - c.t_old) / c.h_prev);
 #pragma unroll
-            for (int j = 0; j < 7; j++) dw.w[j] = to_sgpr(w.w[j]);
+            for (int j = 0; j < M::N_WEIGHTS; j++) dw.w[j] = to_sgpr(w.w[j]);
         };
         auto first_probe = [&]() {                   // Brent on the lowest monitor of ev_mask over [t_old, t]: f(a) first
             br_e = to_sgpr((int32_t)__builtin_ctz((unsigned)ev_mask));
@@ -2264,8 +2256,13 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
             // (the first evaluation's exchange barrier also orders the monitor reduction of the previous attempt before the
             // event bookkeeping below; dp45_attempt is opaque, so the bookkeeping follows the whole attempt's evaluations -
             // still before this attempt's own decision changes c.t_old / c.h_prev / c.t)
-            if constexpr (EVAL) dp45_attempt<BLK, false, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, replay);
-            else dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            if constexpr (DP) {
+                if constexpr (EVAL) dp45_attempt<BLK, false, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, replay);
+                else dp45_attempt<BLK, false, SB, PARK>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk);
+            } else {
+                if constexpr (EVAL) M::template attempt<BLK, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, replay);
+                else M::template attempt<BLK, SB, PARK, false>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk, false);
+            }
             if constexpr (ROOTS) {
                 if (br_phase != 0) {                 // workgroup-uniform
                     double q[NQ];
@@ -2384,13 +2381,16 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
 #pragma unroll
             for (int w = 0; w < NW; w++) sumsq += wsum[w];                          // wave order: the same sum in every wave
             sumsq = to_sgpr(sumsq);
-            const bool accepted = rk45_decide_lean(c, sumsq, inv_n, sb.T);
+            bool accepted;
+            if constexpr (DP) accepted = rk45_decide_lean(c, sumsq, inv_n, sb.T); else accepted = M::decide_lean(c, sumsq, inv_n, sb.T);
             if (accepted) {
                 if (threadIdx.x == 0) { sc.t_old = c.t_old; sc.h_prev = c.h_prev; sc.t = c.t; }   // the step the pending events belong to
                 if (c.t - c.t_bound >= 0.0) c.status = ST_DONE;   // (rk45_advance_status without the event pause, which this loop shape does not have)
                 else if (c.t >= c.pause_t) c.status = ST_PAUSED;
             }
-            if (c.status == ST_RUNNING) rk45_prepare_attempt_lean(c);
+            if (c.status == ST_RUNNING) {
+                if constexpr (DP) rk45_prepare_attempt_lean(c); else M::prepare_attempt_lean(c);
+            }
             c.t = to_sgpr(c.t); c.h_abs = to_sgpr(c.h_abs); c.h_try = to_sgpr(c.h_try); c.t_new = to_sgpr(c.t_new);
             const int status = c.status;
             if (accepted) {

@@ -89,15 +89,22 @@ class HipSweepEngine:
         """y0: (n_local, 5N) host array.  Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries
         the samples that instance reached, as a single run's does: ``t`` (n_t,) and ``y`` (5N, n_t).  With ``events`` every result
         carries ``t_events``, the root times of the seven monitors located inside the sweep (at most ``max_events`` each)."""
+        return self._integrate_rk("sweep_rk45_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events)
+
+    def integrate_rk23(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64):
+        """:meth:`integrate_rk45` with RK23 (marl_sweep_rk23_dev / _eval_dev / _events_dev): the same arguments and results."""
+        return self._integrate_rk("sweep_rk23_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events)
+
+    def _integrate_rk(self, sweep, y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events):
+        sweep = getattr(self.model, sweep)
         yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
         more = {"events": True, "max_events": max_events} if events else {}
         if t_eval is None:
-            res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
+            res = sweep(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
             return yd.cpu().numpy(), res
         n_eval = int(np.size(t_eval))
         frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
-        res = self.model.sweep_rk45_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
-                                           y_eval_dev_ptr=frames.data_ptr(), **more)
+        res = sweep(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval, y_eval_dev_ptr=frames.data_ptr(), **more)
         frames = frames.cpu().numpy()
         for b, r in enumerate(res):
             r.y = frames[b, :len(r.t)].T.copy()
@@ -243,6 +250,14 @@ def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_at
     With ``events`` one last element follows: ``t_events``, per instance a list of 7 arrays - the root times of the reference's monitors
     (Evolve_scenario.py:118-145, 175-177), at most ``max_events`` each, located inside the sweep; ordered like the states."""
     return _run_sweep("integrate_rk45", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
+                      balance, cost, t_eval, events, max_events)
+
+
+def run_sweep_rk23(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
+                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64):
+    """As :func:`run_sweep_rk45` with adaptive RK23 (scipy's Bogacki-Shampine 3(2) pair; every instance costs about the same, so
+    contiguous shards): the same arguments and the same returned tuple, ``t_eval`` and ``events`` included."""
+    return _run_sweep("integrate_rk23", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
                       balance, cost, t_eval, events, max_events)
 
 
