@@ -137,6 +137,34 @@ int marl_debug_num_jac(marl_ctx* ctx, const double* y, double threshold, const i
                        double* J_out);
 int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jscale, double mu_r, double mu_c_re, double mu_c_im, int systems,
                            int64_t nrhs, const double* b_r, const double* b_c, double* x_r, double* x_c);
+/* Test hook of the BDF sweep (the marl_sweep_bdf entries below): ONE launch of one of its five data-parallel kernels, through the launcher
+ * the sweep itself calls, on the sweep's arena (one per instance of the context, B = n_instances, at the sweep's stride).  HOST pointers;
+ * whole-grid context with 5N <= 2048; synchronises.  n = 5N.
+ *   op: MARL_BDF_INIT_D        D[0] = y, D[1] = f h
+ *       MARL_BDF_CHANGE_D      D[:order + 1] = RU^T D[:order + 1]
+ *       MARL_BDF_ACCEPT_NORMS  the accepted step's update of the differences from d (bdf.py:414-418), y = ynew, and the sums
+ *                              sum (coef v / (atol + rtol |y|))^2 that want_norms asks for: bit 0 -> ss_m from D[order] with err_coef_m,
+ *                              bit 1 -> ss_p from D[order + 2] with err_coef_p
+ *       MARL_BDF_SAMPLE        frames [first, min(end, n_eval)) of the instance = D[0] + sum_j D[j + 1] p[j] at t_eval[k], p the weights of
+ *                              BdfDenseOutput(t - h, t, h, order, D)
+ *       MARL_BDF_ROOTS         the root times over [t_old, t] of the monitors in `mask` on the same dense output, monitor e's into
+ *                              t_events[instance][e][slot[e]]
+ *   list, n_list: the instances launched, in this order (grid.z = n_list), each in [0, B), n_list <= B; NULL, 0: all B in order.
+ *   iargs: int64[B][MARL_BDF_DEBUG_INTS] per instance {order, want_norms, first, end, mask, slot[0 .. 6]}.
+ *   dargs: float64[B][MARL_BDF_DEBUG_DOUBLES] per instance {h, rtol, atol, err_coef_m, err_coef_p, t, t_old, RU[6][6] row-major}.
+ *   D_in: float64[B][8][n], all eight rows of every instance's differences; vec_in: float64[B][4][n], the instance's y, f, d, ynew.
+ *   t_eval: float64[n_eval] (SAMPLE; n_eval may be 0).  max_events: root slots per monitor (ROOTS: > 0).
+ *   Out - everything the kernel may write and its surroundings: D_out [B][8][n]; y_out [B][n]; frames [B][n_eval][n], t_events
+ *   [B][7][max_events] and ss [B][2] = (ss_m, ss_p) are IN-OUT: what the caller puts there is on the device before the launch and
+ *   comes back where the kernel wrote nothing.
+ *   Returns -1 with a message, launching nothing, when an argument is out of range: an order outside 1 .. 5 (every op but INIT_D), a list
+ *   entry outside [0, B) or n_list > B, first > end or first < 0, want_norms outside 0 .. 3, a mask outside 0 .. 127, ROOTS with
+ *   max_events <= 0 or a searched monitor's slot outside [0, max_events), 5N > 2048. */
+enum { MARL_BDF_INIT_D = 0, MARL_BDF_CHANGE_D = 1, MARL_BDF_ACCEPT_NORMS = 2, MARL_BDF_SAMPLE = 3, MARL_BDF_ROOTS = 4 };
+enum { MARL_BDF_DEBUG_INTS = 12, MARL_BDF_DEBUG_DOUBLES = 43 };
+int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, int64_t n_list, const int64_t* iargs, const double* dargs,
+                         const double* D_in, const double* vec_in, const double* t_eval, int64_t n_eval, int64_t max_events,
+                         double* D_out, double* y_out, double* frames, double* t_events, double* ss);
 
 /* ---- fixed-step classical RK4 (BASELINE config 2; no counterpart in the reference, which only
  * remarks that forward Euler fails: README.md:9).  y is advanced in place by nsteps steps of dt. */

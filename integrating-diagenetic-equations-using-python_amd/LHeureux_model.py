@@ -462,6 +462,52 @@ class LMAHeureuxPorosityDiff:
                                                      _as_ptr(x_c) if b_c is not None else None), "marl_debug_block_solve")
         return x_r if b_c is None else (x_r, x_c)
 
+    BDF_BATCH_OPS = {"INIT_D": 0, "CHANGE_D": 1, "ACCEPT_NORMS": 2, "SAMPLE": 3, "ROOTS": 4}   # include/marl_hip.h: MARL_BDF_*
+
+    def debug_bdf_batch(self, op, D, y=None, f=None, d=None, ynew=None, *, instances=None, order=1, h=1.0, RU=None, rtol=1e-3, atol=1e-3,
+                        want_norms=0, err_coef_m=0.0, err_coef_p=0.0, t=0.0, t_old=0.0, first=0, end=0, mask=0, slot=None, t_eval=None,
+                        frames=None, t_events=None, ss=None):
+        """ONE launch of one vector kernel of the BDF sweep on the sweep's arena of this model's B instances (marl_debug_bdf_batch).
+        ``op``: a key of ``BDF_BATCH_OPS``.  ``D``: (B, 8, 5N), every row of every instance's differences; ``y``, ``f``, ``d``, ``ynew``:
+        (B, 5N) or None (zeros).  ``instances``: the work list (instance indices in launch order) or None for all in order.  The scalars
+        ``order`` .. ``mask`` are one value or one per instance, ``RU``: (B, 6, 6) or (6, 6), ``slot``: (B, 7) or (7,).  ``frames``
+        (B, n_eval, 5N), ``t_events`` (B, 7, max_events) and ``ss`` (B, 2) hold what is on the device before the launch (sentinels);
+        None: no frames / no root slots / zeros.  Returns a dict of copies - D, y, frames, t_events, ss - as the launch left them."""
+        B, n = self.n_instances, 5 * self.Depths.N
+        D = np.array(D, dtype=np.float64)
+        if D.shape != (B, 8, n):
+            raise ValueError(f"D has shape {D.shape}, expected {(B, 8, n)}")
+        vec = np.zeros((B, 4, n))
+        for k, v in enumerate((y, f, d, ynew)):
+            if v is not None:
+                vec[:, k] = np.asarray(v, dtype=np.float64).reshape(B, n)
+        per = lambda v, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (B,)))  # noqa: E731
+        ia = np.zeros((B, 12), dtype=np.int64)
+        for k, v in enumerate((order, want_norms, first, end, mask)):
+            ia[:, k] = per(v, np.int64)
+        ia[:, 5:] = np.broadcast_to(np.asarray(0 if slot is None else slot, dtype=np.int64), (B, 7))
+        da = np.zeros((B, 43))
+        for k, v in enumerate((h, rtol, atol, err_coef_m, err_coef_p, t, t_old)):
+            da[:, k] = per(v, np.float64)
+        da[:, 7:] = np.broadcast_to(np.asarray(0.0 if RU is None else RU, dtype=np.float64), (B, 6, 6)).reshape(B, 36)
+        lst = None if instances is None else np.ascontiguousarray(instances, dtype=np.int32)
+        te = np.ascontiguousarray([] if t_eval is None else t_eval, dtype=np.float64)
+        fr = np.empty((B, 0, n)) if frames is None else np.array(frames, dtype=np.float64)
+        if fr.shape != (B, te.size, n):
+            raise ValueError(f"frames has shape {fr.shape}, expected {(B, te.size, n)}")
+        tev = np.empty((B, 7, 0)) if t_events is None else np.array(t_events, dtype=np.float64)
+        if tev.ndim != 3 or tev.shape[:2] != (B, 7):
+            raise ValueError(f"t_events has shape {tev.shape}, expected {(B, 7)} + (max_events,)")
+        ss = np.zeros((B, 2)) if ss is None else np.array(ss, dtype=np.float64)
+        if ss.shape != (B, 2):
+            raise ValueError(f"ss has shape {ss.shape}, expected {(B, 2)}")
+        D_out, y_out = np.empty_like(D), np.empty((B, n))
+        self._check(self._lib.marl_debug_bdf_batch(
+            self._ctx, self.BDF_BATCH_OPS[op], _as_ptr(lst) if lst is not None else None, 0 if lst is None else lst.size, _as_ptr(ia), _as_ptr(da),
+            _as_ptr(D), _as_ptr(vec), _as_ptr(te) if te.size else None, te.size, tev.shape[2], _as_ptr(D_out), _as_ptr(y_out),
+            _as_ptr(fr) if fr.size else None, _as_ptr(tev) if tev.size else None, _as_ptr(ss)), "marl_debug_bdf_batch")
+        return dict(D=D_out, y=y_out, frames=fr, t_events=tev, ss=ss)
+
     def integrate_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, layout=LAYOUT_FIELD_MAJOR, max_attempts=0):
         return self._integrate_rk_device("rk45", y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts)
 

@@ -83,6 +83,7 @@ PROTOTYPES = {
     "marl_debug_math": (_I, [_P, _I, _P, _P, _L, _D]),
     "marl_debug_num_jac": (_I, [_P, _P, _D, _P, _P, _I, _P]),
     "marl_debug_block_solve": (_I, [_P, _P, _D, _D, _D, _D, _I, _L, _P, _P, _P, _P]),
+    "marl_debug_bdf_batch": (_I, [_P, _I, _P, _L, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P]),
     "marl_integrate_rk4": (_I, [_P, _P, _D, _L]),
     "marl_integrate_rk4_dev": (_I, [_P, _P, _I, _D, _L]),
     "marl_sweep_rk4_dev": (_I, [_P, _P, _P, _L]),

@@ -3253,6 +3253,49 @@ extern "C" int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0
     return sweep_radau(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats);
 }
 
+// ---- the launches of the BDF sweep's vector kernels (marl_bdf_batch.h): one launcher each, called by sweep_bdf and by the test hook
+// marl_debug_bdf_batch below, so that a test launches what a sweep launches.  zb: the instances' stride, their controllers and the work
+// list (NULL: every instance in order); cnt: the instances launched (grid.z).
+struct BdfArena { double *D, *f, *ypred, *psi, *d; };   // where bdf_run's vectors live in an instance's arena (marl_bdf_batch.h)
+static BdfArena bdf_arena_of(const RadauWork& w, int64_t n) { return BdfArena{w.Z, w.Z0, w.Q, w.Q + n, w.Q + 2 * n}; }
+
+static int bdf_launch_init_D(marl_ctx* ctx, const RadauWork& w, int64_t n, unsigned cnt, const bdf::BdfBatch& zb)
+{
+    hipLaunchKernelGGL(bdf::init_D_batch_kernel, dim3(blocks256(n), 1, cnt), dim3(256), 0, ctx->stream, w.y, w.f, n, bdf_arena_of(w, n).D, zb);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
+static int bdf_launch_accept_norms(marl_ctx* ctx, const RadauWork& w, int64_t n, unsigned cnt, const bdf::BdfBatch& zb)
+{
+    const BdfArena a = bdf_arena_of(w, n);
+    hipLaunchKernelGGL(bdf::accept_norms_batch_kernel, dim3(1, 1, cnt), dim3(1024), 0, ctx->stream, a.D, a.d, w.ynew, n, w.y, zb);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
+static int bdf_launch_change_D(marl_ctx* ctx, const RadauWork& w, int64_t n, unsigned cnt, const bdf::BdfBatch& zb)
+{
+    hipLaunchKernelGGL(bdf::change_D_batch_kernel, dim3(blocks256(n), 1, cnt), dim3(256), 0, ctx->stream, bdf_arena_of(w, n).D, n, zb);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
+static int bdf_launch_roots(marl_ctx* ctx, const RadauWork& w, int64_t N, const bdfctl::BdfRoots* droots, double* dtev, unsigned cnt, const bdf::BdfBatch& zb)
+{
+    hipLaunchKernelGGL(bdf::roots_batch_kernel, dim3(1, 1, cnt), dim3(radau::WG_THREADS), 0, ctx->stream, bdf_arena_of(w, NF * N).D, N, droots, dtev, ctx->dconsts, zb);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
+static int bdf_launch_sample(marl_ctx* ctx, const RadauWork& w, int64_t n, const double* dteval, int64_t n_eval, const bdfctl::BdfSample* dsmp, double* y_eval_dev,
+                             unsigned cnt, const bdf::BdfBatch& zb)
+{
+    hipLaunchKernelGGL(bdf::sample_batch_kernel, dim3(blocks256(n), 1, cnt), dim3(256), 0, ctx->stream, bdf_arena_of(w, n).D, n, dteval, n_eval, dsmp, y_eval_dev, zb);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
 // ---- a sweep of BDF instances (marl_bdf_batch.h, marl_bdf_ctl.h) ---------------------------------------------------------------
 // BDF.__init__ of every instance (f, the first Jacobian, D, the monitors) in front of the cycle, then the cycle of sweep_radau's
 // launch-per-action mode: controllers, the list lengths (sweep_read_counts), then every kind of work over its list in the order
@@ -3326,11 +3369,9 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));   // (sweep_read_counts keeps them zero between cycles)
     bdf::Vec6 gamma = {};
     for (int k = 1; k <= bdf::MAX_ORDER; k++) gamma.v[k] = gamma.v[k - 1] + 1.0 / k;
-    double* D = w.Z;
-    double* f = w.Z0;
-    double *ypred = w.Q, *psi = w.Q + n, *d = w.Q + 2 * n;
+    const BdfArena arena = bdf_arena_of(w, n);
+    double *const D = arena.D, *const f = arena.f, *const ypred = arena.ypred, *const psi = arena.psi, *const d = arena.d;
     const dim3 b256(256);
-    const unsigned gx = blocks256(n);
     const int64_t nbm = std::min<int64_t>((N + 255) / 256, 1024);
     if (int rc = ensure_part(ctx, (size_t)(nbm * B))) return rc;
     auto L = [&](int which) { return BdfBatch{zs, dctl, dlists + (int64_t)which * B}; };
@@ -3340,8 +3381,7 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         const ZBatch all{zs, nullptr, 0, 0, nullptr};
         if (int rc = launch_rhs_fm(ctx, w.y, w.f, 1, (unsigned)B, all)) return rc;
         if (int rc = radau_num_jac(ctx, w, w.y, w.f, atol, 1, (unsigned)B, all)) return rc;
-        hipLaunchKernelGGL(init_D_batch_kernel, dim3(gx, 1, (unsigned)B), b256, 0, ctx->stream, w.y, w.f, n, D, BdfBatch{zs, dctl, nullptr});
-        LAUNCH_OK(ctx);
+        if (int rc = bdf_launch_init_D(ctx, w, n, (unsigned)B, BdfBatch{zs, dctl, nullptr})) return rc;
         hipLaunchKernelGGL(monitors_kernel<LAYOUT_FIELD_MAJOR>, dim3((unsigned)nbm, (unsigned)B), b256, 0, ctx->stream, w.y, ctx->dconsts, ctx->slab, zs / 8, ctx->part);
         LAUNCH_OK(ctx);
         hipLaunchKernelGGL(reduce_records_kernel, dim3((unsigned)B), b256, 0, ctx->stream, ctx->part, nbm, drec);
@@ -3363,22 +3403,14 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         stalled = hcounts[BL_PROGRESS] ? 0 : stalled + 1;
         if (stalled >= kStallCycles)
             return fail(ctx, -3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
-        if (nA) {   // the accepted step: differences, y = y_new, the norms of the order selection
-            hipLaunchKernelGGL(accept_norms_batch_kernel, dim3(1, 1, nA), dim3(1024), 0, ctx->stream, D, d, w.ynew, n, w.y, L(BL_ACCEPT));
-            LAUNCH_OK(ctx);
-        }
-        if (nC) {
-            hipLaunchKernelGGL(change_D_batch_kernel, dim3(gx, 1, nC), b256, 0, ctx->stream, D, n, L(BL_CHANGE_D));
-            LAUNCH_OK(ctx);
-        }
-        if (nR) {   // root times of the step just accepted: the same D as the samples below, events first (ivp.py:673-723)
-            hipLaunchKernelGGL(roots_batch_kernel, dim3(1, 1, nR), dim3(radau::WG_THREADS), 0, ctx->stream, D, N, droots, dtev, ctx->dconsts, L(BL_ROOTS));
-            LAUNCH_OK(ctx);
-        }
-        if (nP) {   // t_eval samples of the step just accepted: D after the selection's rescaling, before the next step's
-            hipLaunchKernelGGL(sample_batch_kernel, dim3(gx, 1, nP), b256, 0, ctx->stream, D, n, dteval, n_eval, dsmp, y_eval_dev, L(BL_SAMPLE));
-            LAUNCH_OK(ctx);
-        }
+        if (nA)   // the accepted step: differences, y = y_new, the norms of the order selection
+            if (int rc = bdf_launch_accept_norms(ctx, w, n, nA, L(BL_ACCEPT))) return rc;
+        if (nC)
+            if (int rc = bdf_launch_change_D(ctx, w, n, nC, L(BL_CHANGE_D))) return rc;
+        if (nR)   // root times of the step just accepted: the same D as the samples below, events first (ivp.py:673-723)
+            if (int rc = bdf_launch_roots(ctx, w, N, droots, dtev, nR, L(BL_ROOTS))) return rc;
+        if (nP)   // t_eval samples of the step just accepted: D after the selection's rescaling, before the next step's
+            if (int rc = bdf_launch_sample(ctx, w, n, dteval, n_eval, dsmp, y_eval_dev, nP, L(BL_SAMPLE))) return rc;
         if (nJ) {   // J = jac(t_new, y_predict), with f = fun(t_new, y_predict) (not counted)
             if (int rc = launch_rhs_fm(ctx, ypred, w.fnew, 1, nJ, Z(BL_JAC))) return rc;
             if (int rc = radau_num_jac(ctx, w, ypred, w.fnew, atol, 0, nJ, Z(BL_JAC))) return rc;
@@ -3446,6 +3478,115 @@ extern "C" int marl_sweep_bdf_events_dev(marl_ctx* ctx, double* y_dev, double t0
                                          int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
 {
     return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats);
+}
+
+// ---- test hook of the BDF sweep's vector kernels: ONE launch (tests/test_gpu_bdf_batch_parts.py) ------------------------------------
+// The sweep's arena (radau_alloc with the context's instances: the real stride), each instance's BdfCtl / BdfSample / BdfRoots built
+// here from plain scalars, one launch through the launcher sweep_bdf calls, and everything the kernel may write - with its
+// surroundings - back to the host.  Every argument a kernel would index with is checked first: nothing out of range reaches the device.
+extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, int64_t n_list, const int64_t* iargs, const double* dargs,
+                                    const double* D_in, const double* vec_in, const double* t_eval, int64_t n_eval, int64_t max_events,
+                                    double* D_out, double* y_out, double* frames, double* t_events, double* ss)
+{
+    using namespace bdf;
+    if (!ctx || !iargs || !dargs || !D_in || !vec_in || !D_out || !y_out || !ss) return ctx ? fail(ctx, -1, "marl_debug_bdf_batch: invalid argument") : -1;
+    if (op < MARL_BDF_INIT_D || op > MARL_BDF_ROOTS) return fail(ctx, -1, "marl_debug_bdf_batch: unknown op %d", op);
+    if (ctx->halo > 0) return fail(ctx, -1, "marl_debug_bdf_batch: whole-grid context required");
+    if (ctx->batch > 65535) return fail(ctx, -1, "marl_debug_bdf_batch: at most 65535 instances per call");
+    const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
+    if (n > radau::PCR_FUSED_MAX) return fail(ctx, -1, "marl_debug_bdf_batch: the BDF sweep takes N <= %d", (int)(radau::PCR_FUSED_MAX / NF));
+    if (list ? (n_list < 1 || n_list > B) : n_list != 0) return fail(ctx, -1, "marl_debug_bdf_batch: a list holds 1 .. %lld instances (no list: n_list = 0)", (long long)B);
+    for (int64_t k = 0; list && k < n_list; k++)
+        if (list[k] < 0 || list[k] >= B) return fail(ctx, -1, "marl_debug_bdf_batch: list entry %lld = %d is no instance", (long long)k, (int)list[k]);
+    if (n_eval < 0 || (n_eval > 0 && (!t_eval || !frames))) return fail(ctx, -1, "marl_debug_bdf_batch: n_eval samples need t_eval and frames");
+    if (max_events < 0 || (max_events > 0 && !t_events)) return fail(ctx, -1, "marl_debug_bdf_batch: max_events root slots need t_events");
+    if (op == MARL_BDF_ROOTS && max_events <= 0) return fail(ctx, -1, "marl_debug_bdf_batch: ROOTS needs max_events > 0");
+    std::vector<BdfCtl> hctl((size_t)B);   // (before the device buffers, as in sweep_bdf)
+    std::vector<BdfSample> hsmp((size_t)B);
+    std::vector<BdfRoots> hroots((size_t)B);
+    for (int64_t b = 0; b < B; b++) {
+        const int64_t* ia = iargs + b * MARL_BDF_DEBUG_INTS;
+        const double* da = dargs + b * MARL_BDF_DEBUG_DOUBLES;
+        const int64_t order = ia[0], want = ia[1], first = ia[2], end = ia[3], mask = ia[4];
+        if (op != MARL_BDF_INIT_D && (order < 1 || order > MAX_ORDER)) return fail(ctx, -1, "marl_debug_bdf_batch: instance %lld: order %lld outside 1 .. 5", (long long)b, (long long)order);
+        if (want < 0 || want > 3) return fail(ctx, -1, "marl_debug_bdf_batch: instance %lld: want_norms outside 0 .. 3", (long long)b);
+        if (first < 0 || first > end) return fail(ctx, -1, "marl_debug_bdf_batch: instance %lld: samples [first, end) need 0 <= first <= end", (long long)b);
+        if (mask < 0 || mask > 127) return fail(ctx, -1, "marl_debug_bdf_batch: instance %lld: mask outside 0 .. 127", (long long)b);
+        BdfCtl& c = hctl[(size_t)b];
+        bdfctl::bdf_control_init(c, 0.0, 1.0, da[0], da[1], da[2], 0);
+        c.order = c.ru_order = (int32_t)order;
+        c.want_norms = (int32_t)want;
+        c.err_coef_m = da[3]; c.err_coef_p = da[4];
+        for (int j = 0; j <= MAX_ORDER; j++)
+            for (int k = 0; k <= MAX_ORDER; k++) c.RU[j][k] = da[7 + j * (MAX_ORDER + 1) + k];
+        c.ss_m = ss[2 * b]; c.ss_p = ss[2 * b + 1];
+        BdfSample& s = hsmp[(size_t)b];
+        bdfctl::bdf_sample_init(s, n_eval);
+        s.t = da[5]; s.h = da[0]; s.order = (int32_t)order; s.first = first; s.end = end;
+        BdfRoots& r = hroots[(size_t)b];
+        bdfctl::bdf_roots_init(r, max_events);
+        r.t_old = da[6]; r.t = da[5]; r.h = da[0]; r.order = (int32_t)order; r.mask = (int32_t)mask;
+        for (int e = 0; e < 7; e++) {
+            r.slot[e] = ia[5 + e];
+            if (op == MARL_BDF_ROOTS && ((mask >> e) & 1) && (r.slot[e] < 0 || r.slot[e] >= max_events))
+                return fail(ctx, -1, "marl_debug_bdf_batch: instance %lld: slot of monitor %d outside [0, max_events)", (long long)b, e);
+        }
+    }
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    RadauWork w;
+    int64_t zs = 0;
+    if (int rc = radau_alloc(ctx, w, nullptr, B, &zs)) return rc;
+    const size_t nb = (size_t)n * sizeof(double), fr_bytes = (size_t)B * (size_t)n_eval * nb, tev_bytes = sizeof(double) * (size_t)B * 7 * (size_t)max_events;
+    DevBuf b_ctl(ctx->stream), b_smp(ctx->stream), b_roots(ctx->stream), b_list(ctx->stream), b_teval(ctx->stream), b_fr(ctx->stream), b_tev(ctx->stream);
+    HIP_OK(ctx, b_ctl.alloc(sizeof(BdfCtl) * B));
+    HIP_OK(ctx, b_smp.alloc(sizeof(BdfSample) * B));
+    HIP_OK(ctx, b_roots.alloc(sizeof(BdfRoots) * B));
+    HIP_OK(ctx, hipMemcpyAsync(b_ctl.p, hctl.data(), sizeof(BdfCtl) * B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(b_smp.p, hsmp.data(), sizeof(BdfSample) * B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(ctx, hipMemcpyAsync(b_roots.p, hroots.data(), sizeof(BdfRoots) * B, hipMemcpyHostToDevice, ctx->stream));
+    if (list) {
+        HIP_OK(ctx, b_list.alloc(sizeof(int32_t) * (size_t)n_list));
+        HIP_OK(ctx, hipMemcpyAsync(b_list.p, list, sizeof(int32_t) * (size_t)n_list, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n_eval > 0) {
+        HIP_OK(ctx, b_teval.alloc(sizeof(double) * (size_t)n_eval));
+        HIP_OK(ctx, b_fr.alloc(fr_bytes));
+        HIP_OK(ctx, hipMemcpyAsync(b_teval.p, t_eval, sizeof(double) * (size_t)n_eval, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(b_fr.p, frames, fr_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (max_events > 0) {
+        HIP_OK(ctx, b_tev.alloc(tev_bytes));
+        HIP_OK(ctx, hipMemcpyAsync(b_tev.p, t_events, tev_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const BdfArena a = bdf_arena_of(w, n);
+    auto at = [&](double* p, int64_t b) { return reinterpret_cast<double*>(reinterpret_cast<char*>(p) + b * zs); };   // p of instance b
+    for (int64_t b = 0; b < B; b++) {
+        const double* v = vec_in + b * 4 * n;   // y, f, d, ynew
+        HIP_OK(ctx, hipMemcpyAsync(at(a.D, b), D_in + b * 8 * n, 8 * nb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(at(w.y, b), v, nb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(at(w.f, b), v + n, nb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(at(a.d, b), v + 2 * n, nb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(at(w.ynew, b), v + 3 * n, nb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const BdfBatch zb{zs, b_ctl.as<BdfCtl>(), list ? b_list.as<int32_t>() : nullptr};
+    const unsigned cnt = (unsigned)(list ? n_list : B);
+    int rc = 0;
+    if (op == MARL_BDF_INIT_D) rc = bdf_launch_init_D(ctx, w, n, cnt, zb);
+    else if (op == MARL_BDF_CHANGE_D) rc = bdf_launch_change_D(ctx, w, n, cnt, zb);
+    else if (op == MARL_BDF_ACCEPT_NORMS) rc = bdf_launch_accept_norms(ctx, w, n, cnt, zb);
+    else if (op == MARL_BDF_SAMPLE) rc = bdf_launch_sample(ctx, w, n, b_teval.as<double>(), n_eval, b_smp.as<BdfSample>(), b_fr.as<double>(), cnt, zb);
+    else rc = bdf_launch_roots(ctx, w, N, b_roots.as<BdfRoots>(), b_tev.as<double>(), cnt, zb);
+    if (rc) return rc;
+    for (int64_t b = 0; b < B; b++) {
+        HIP_OK(ctx, hipMemcpyAsync(D_out + b * 8 * n, at(a.D, b), 8 * nb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(ctx, hipMemcpyAsync(y_out + b * n, at(w.y, b), nb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_OK(ctx, hipMemcpyAsync(hctl.data(), b_ctl.p, sizeof(BdfCtl) * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_eval > 0) HIP_OK(ctx, hipMemcpyAsync(frames, b_fr.p, fr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (max_events > 0) HIP_OK(ctx, hipMemcpyAsync(t_events, b_tev.p, tev_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < B; b++) { ss[2 * b] = hctl[(size_t)b].ss_m; ss[2 * b + 1] = hctl[(size_t)b].ss_p; }
+    return 0;
 }
 
 #endif  // MARL_LAB

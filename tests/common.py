@@ -111,6 +111,20 @@ IMPLICIT_SOLVE_E = {
     "N5003|levels-1":  dict(measured=8.3e-06, over_bound=0.034),
 }
 
+# The BDF sweep's vector kernels, one launch at a time (tests/test_gpu_bdf_batch_parts.py; references and bounds: tests/bdf_batch_ref.py).
+# Every bound but one is derived (bdf_batch_ref: change_D_ref, sample_ref, norm_bound; the rest is equal to the last bit); `over_bound` is the
+# worst |device - reference| / bound over the launches of an op on an MI355X - all below 1.
+BDF_BATCH_PARTS = {
+    # op                    measured on MI355X: worst ratio over grids, lists, orders
+    "CHANGE_D":        dict(over_bound=0.33),     # N = 409; 0.27 .. 0.32 on the others
+    "SAMPLE":          dict(over_bound=0.34),     # N = 64; the float64 restatement makes the same figures
+    "ACCEPT_NORMS_ss": dict(over_bound=0.031),    # N = 64
+}
+# ROOTS is measured: |t_device - t_brentq| / h of the step, brentq on the oracle's monitors of the same dense state with solve_ivp's
+# tolerances (xtol = rtol = 4 eps).  `measured`: the largest value over both grids, the lists and the order sets on an MI355X; `bound` is
+# 10 x that (the margin of INCR_TOL and IMPLICIT_JAC_K), which covers the kernel's table-driven exp in F(Phi), a few ulp off libm.
+BDF_BATCH_ROOTS = dict(bound=1.3e-13, measured=1.3e-14)   # N = 33: monitor 5 at order 5 (7.2e-15 at N = 409)
+
 # fixed-step configurations at N >= 65 536 (the GPU tests run these; the sensitivity test perturbs the oracle at the same ones)
 RK4_FINE_CONFIGS = {
     "rk4_config2": dict(scenario="default", N=65536, nsteps=37, amplitude=0.01, dtf=0.25),
