@@ -53,6 +53,27 @@ const char* marl_last_error(const marl_ctx* ctx); /* ctx may be NULL: error of t
  * torch.cuda.current_stream().cuda_stream; NULL selects the default stream again). */
 int marl_set_stream(marl_ctx* ctx, void* hip_stream);
 int marl_synchronize(marl_ctx* ctx);
+/* Terminal monitors: a property of the model, as in the reference, where `terminal` is an attribute of the model's event methods
+ * (marlpde/LHeureux_model.py:113-122: "Make sure integration stops when we field values become less than zero or more than one, in some
+ * cases. Or just register that this is happening and continue integration, which corresponds to `False`.").
+ * terminal[e], e in the order of marl_events: 0 - monitor e only records (the reference's setting, and a new context's);
+ * k > 0 - the run ends at the k-th occurrence of monitor e (scipy >= 1.13 takes an int for event.terminal; True is 1).
+ * NULL: all zeros.  A negative entry: -1, nothing changed.  ctx == NULL: -1.
+ * A run that a terminal monitor ends follows solve_ivp (ivp.py:79-130 handle_events, :681-723; the rule: csrc/marl_terminal.h):
+ *   stats->status = 1 ("A termination event occurred."), stats->t = t_stop, the root of the terminal monitor;
+ *   the state returned is the accepted step's dense output at t_stop - the expression that writes a t_eval frame, so it equals a
+ *   frame at t_eval = t_stop bit for bit - and stats->event_value holds that state's monitors;
+ *   t_events / n_events hold the roots up to and including the terminal one in the order of root times (equal roots: monitor order);
+ *   a sign change after it in the same step is neither stored nor counted, so n_events[e] stays the number of roots scipy returns;
+ *   t_eval samples with t_eval[k] <= t_stop are written from that step (n_done counts them), later frames are untouched;
+ *   nfev / njev / nlu / n_accepted / n_rejected are those after the accepted step: roots and samples cost no evaluation.
+ * In such a step the roots of ALL active monitors are located (the order needs them), with or without a free slot and also when the
+ * caller passed no t_events; they are stored only where a slot is free.  A step that meets no limit runs exactly as without limits.
+ * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev.  Every other
+ * integrator entry (marl_integrate_rk45 / rk23 [_dev], marl_sweep_rk45* / rk23*, marl_sweep_bdf*, marl_slab_init_control,
+ * marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
+ * before it touches the state, and is unchanged when none is. */
+int marl_set_terminal(marl_ctx* ctx, const int64_t terminal[7]);
 /* Tuning knobs; unknown names are an error.  See DESIGN.md.
  *   rk4_variant (fused RK4 steps per launch: 0..4 = 1 / 2 / 4 / 8 / 16; anything else, e.g. -1: chosen by grid size; with dPhi_variable
  *   always 4), sweep_variant (one-workgroup window: 0 / 1 / 2 = 256 / 512 / 1024 cells, used when it holds N; otherwise, e.g. -1, the
@@ -251,7 +272,7 @@ int marl_sweep_rk23_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t
  * groups (may be NULL): int32[5N], the column grouping scipy derives from the pattern (scipy.optimize._numdiff.group_columns);
  * NULL selects a structured 15-colouring - the Jacobian entries are the same either way (and scipy's nfev does not count the
  * finite-difference columns).  stats->nfev / njev / nlu are counted as scipy counts them.  Other arguments as for
- * marl_integrate_rk45.  Single-instance contexts only. */
+ * marl_integrate_rk45.  Single-instance contexts only.  Terminal monitors (marl_set_terminal) end the run: status 1. */
 int marl_integrate_radau(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
                          const int32_t* groups, const double* t_eval, int64_t n_eval, double* y_eval, double* t_events,
                          int64_t max_events, int64_t max_attempts, marl_stats* stats);
@@ -268,14 +289,19 @@ int marl_integrate_bdf(marl_ctx* ctx, double* y, double t0, double t1, double fi
  * history and Newton convergence, advanced together - each instance's step logic runs as a state machine on the device, every
  * launch works on all instances that currently need that kind of work (csrc/marl_radau_batch.h).  y_dev: [n_instances][5N] FIELD-MAJOR
  * device states, advanced in place; stats: host array of n_instances entries (nfev / njev / nlu / status / t as scipy counts them;
- * monitor sign changes are counted in n_events, root times are not located in a sweep).  N <= 1638.  Synchronises. */
+ * monitor sign changes are counted in n_events, root times are not located in a sweep).  N <= 1638.  Synchronises.
+ * Terminal monitors (marl_set_terminal): an instance whose monitor meets its limit ends there with status 1 - its controller locates
+ * the roots of that step although this entry stores none, and one more action (A_STOP) writes the dense output at t_stop into its
+ * state; the other instances are bit for bit what they are without the limit. */
 int marl_sweep_radau_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                          const int32_t* groups, int64_t max_attempts, marl_stats* stats);
 /* The same sweep with the monitors' ROOT TIMES located inside it, as solve_ivp returns them for every run (sol.t_events,
  * marlpde/Evolve_scenario.py:118-145, 175-177; scipy ivp.py:673-694 with solve_event_equation :51-76): after an accepted step in
  * which a monitor changed sign, the instance's device-side controller runs Brent's method on the step's dense output - one
  * dense-output evaluation + monitors per function evaluation.  t_events: host array [instances][7][max_events]; entry k of
- * monitor e of instance b is valid for k < stats[b].n_events[e], the rest is NaN; sign changes beyond max_events are counted only. */
+ * monitor e of instance b is valid for k < stats[b].n_events[e], the rest is NaN; sign changes beyond max_events are counted only.
+ * Terminal monitors (marl_set_terminal): in the step that ends an instance's run only the roots up to the terminal one are stored
+ * and counted; a kept root without a free slot is counted. */
 int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                 const int32_t* groups, int64_t max_attempts, double* t_events, int64_t max_events, marl_stats* stats);
 /* The same sweep with t_eval: what the reference keeps of every run is the time series that solve_ivp(..., t_eval=) fills with its
@@ -288,7 +314,9 @@ int marl_sweep_radau_events_dev(marl_ctx* ctx, double* y_dev, double t0, double 
  * written for that instance (the samples with t_eval[k] <= the time it reached); its later frames are not touched.
  * t_events, max_events: as for marl_sweep_radau_events_dev; may be NULL / 0 (sign changes are then only counted).
  * n_eval = 0 (t_eval, y_eval_dev, n_done may then be NULL) is marl_sweep_radau_events_dev, or marl_sweep_radau_dev without t_events.
- * t1 == t0: no step is taken; a sample at t0 receives y0.  Synchronises. */
+ * t1 == t0: no step is taken; a sample at t0 receives y0.  Synchronises.
+ * Terminal monitors (marl_set_terminal): roots, then the stop, then the samples - an instance that ends at t_stop has the frames with
+ * t_eval[k] <= t_stop, the last of them written from the step that ended it, and its state equals a frame at t_stop bit for bit. */
 int marl_sweep_radau_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                               const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                               int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);

@@ -50,12 +50,13 @@ typedef struct marl_stats {
                            finite-difference Jacobian columns) */
     int64_t n_accepted; /* accepted steps */
     int64_t n_rejected; /* rejected attempts */
-    int32_t status;     /* 0 reached t1; -1 step size too small (scipy status -1); 2 attempt budget exhausted */
+    int32_t status;     /* 0 reached t1; -1 step size too small (scipy status -1); 2 attempt budget exhausted;
+                           1 a terminal monitor ended the run at t (scipy status 1; marl_set_terminal) */
     int32_t reserved;
     double t;           /* time reached */
     double h_next;      /* step size the controller would try next */
     double event_value[MARL_NEVENTS];   /* the 7 monitors evaluated at the final state */
-    int64_t n_events[MARL_NEVENTS];     /* sign changes seen per monitor (both directions, non-terminal) */
+    int64_t n_events[MARL_NEVENTS];     /* sign changes seen per monitor (both directions; up to the terminal one, marl_set_terminal) */
     int64_t njev;       /* Jacobian evaluations (implicit Radau path; 0 for the explicit integrators) - scipy's sol.njev */
     int64_t nlu;        /* LU decompositions, counted as scipy does (real and complex system separately) - sol.nlu */
 } marl_stats;

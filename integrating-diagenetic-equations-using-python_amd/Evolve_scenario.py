@@ -29,7 +29,7 @@ from datetime import datetime
 
 import numpy as np
 
-from .LHeureux_model import DepthGrid, LMAHeureuxPorosityDiff
+from .LHeureux_model import EVENT_NAMES, DepthGrid, LMAHeureuxPorosityDiff, terminal_counts
 
 EVENT_TEXT = (
     "any field at any depth crossed zero", "CA at any depth crossed zero", "CC at any depth crossed zero",
@@ -44,7 +44,22 @@ class _NoBar:
         self.n += k
 
 
-def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="../Results/", verbose=True, device=0):
+def _scipy_events(eq, limits):
+    """The model's seven event callables for solve_ivp, each carrying its ``terminal`` as scipy reads it (False, or the count)."""
+    def make(name, limit):
+        bound = getattr(eq, name)
+
+        def event(t, y, *args):
+            return bound(t, y, *args)
+        event.terminal = limit if limit else False
+        return event
+    return [make(name, limit) for name, limit in zip(EVENT_NAMES, limits)]
+
+
+def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="../Results/", verbose=True, device=0, terminal=None):
+    """``terminal``: the reference's switch (LHeureux_model.py:113-122) - which monitors end the run at their root, as
+    :func:`marlpde_amd.LHeureux_model.terminal_counts` reads it.  Native for Radau and BDF; RK45 / RK23 need ``scipy_driver``."""
+    limits = terminal_counts(terminal)
     solver_parms = dict(solver_parms)
     Xstar, Tstar = pde_parms["Xstar"], pde_parms["Tstar"]
     N = int(pde_parms["N"])
@@ -65,6 +80,10 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     start = time.time()
     scipy_driver = bool(solver_parms.pop("scipy_driver", False))
     if method in ("RK45", "RK23") and not scipy_driver:
+        if any(limits):
+            eq.close()
+            raise ValueError(f"terminal monitors are not built into the native {method} loop: pass scipy_driver=True in the solver "
+                             "parameters, or use method 'Radau' or 'BDF'")
         integrate = eq.integrate_rk45 if method == "RK45" else eq.integrate_rk23
         res = integrate(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"],
                         t_eval=t_eval)
@@ -84,10 +103,11 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
             from scipy.sparse import csc_matrix
             groups = group_columns(csc_matrix(sp))
         integrate = eq.integrate_radau if method == "Radau" else eq.integrate_bdf   # (marl_integrate_bdf: the same machinery, scipy's BDF step logic)
+        eq.set_terminal(limits)
         res = integrate(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval, groups=groups)
         t_out, y_out, t_events = res.t, res.y, res.t_events
         nfev, njev, nlu, status, message = res.nfev, res.njev, res.nlu, res.status, res.message
-        if status not in (0, -1):
+        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached - without t_eval the state there is the last profile)
             status = -1
         covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
     else:
@@ -99,12 +119,13 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
         opts = {k: v for k, v in solver_parms.items() if k not in drop and v is not None}
         bar = _NoBar()
         args = [bar, (t_span[1] - t_span[0]) / no_progress_updates, t_span[0]]
-        sol = solve_ivp(eq.fun, t_span, y0, method=method, t_eval=t_eval,
-                        events=[eq.zeros, eq.zeros_CA, eq.zeros_CC, eq.ones_CA_plus_CC, eq.ones_Phi, eq.zeros_U,
-                                eq.zeros_W], args=args, **opts)
+        sol = solve_ivp(eq.fun, t_span, y0, method=method, t_eval=t_eval, events=_scipy_events(eq, limits), args=args, **opts)
         t_out, y_out, t_events = sol.t, sol.y, sol.t_events
         nfev, njev, nlu, status, message = sol.nfev, sol.njev, sol.nlu, sol.status, sol.message
-        covered = Tstar * t_span[1] if status == 0 else bar.n * Tstar * t_span[1] / no_progress_updates
+        if status == 1:   # a terminal monitor ended the run at its root: the latest of the roots kept (ivp.py:696-704)
+            covered = Tstar * max(float(te[-1]) for te in t_events if len(te))
+        else:
+            covered = Tstar * t_span[1] if status == 0 else bar.n * Tstar * t_span[1] / no_progress_updates
     wall = time.time() - start
 
     if verbose:

@@ -58,10 +58,12 @@ class RK45Result:
         self.nlu = int(stats.nlu)
         self.n_accepted = int(stats.n_accepted)
         self.n_rejected = int(stats.n_rejected)
-        # library status -> scipy status: 0 finished; -1 step size too small; 2 attempt budget (no scipy analogue)
+        # library status -> scipy status: 0 finished; 1 a terminal monitor ended the run; -1 step size too small; 2 attempt budget
+        # (no scipy analogue)
         self.status = int(stats.status)
         self.success = self.status == 0
         self.message = {0: "The solver successfully reached the end of the integration interval.",
+                        1: "A termination event occurred.",
                         -1: "Required step size is less than spacing between numbers.",
                         2: "Attempt budget exhausted before the end of the interval."}.get(self.status, "?")
         self.t_reached = float(stats.t)
@@ -71,6 +73,36 @@ class RK45Result:
         self.t = t
         self.y = y
         self.t_events = t_events
+
+
+EVENT_NAMES = ("zeros", "zeros_CA", "zeros_CC", "ones_CA_plus_CC", "ones_Phi", "zeros_U", "zeros_W")   # Evolve_scenario.py:107-109
+
+
+def terminal_counts(spec):
+    """The limits marl_set_terminal takes, a tuple of 7 ints, from what a user of the reference would write (its switch:
+    LHeureux_model.py:113-122).  ``spec``: None (no monitor is terminal: the reference's setting), a sequence of 7 bools / ints in the
+    monitors' order, or a dict keyed by the monitors' names ``zeros ... zeros_W``.  As scipy >= 1.13 reads ``event.terminal``: False
+    or 0 - the monitor only records; True - the run ends at its first occurrence; an int k > 0 - at its k-th.  A pure function."""
+    def one(v, what):
+        if isinstance(v, (bool, np.bool_)):
+            return int(v)
+        if not isinstance(v, (int, np.integer)):
+            raise ValueError(f"terminal: {what} must be a bool or an int, not {v!r}")
+        if v < 0:
+            raise ValueError(f"terminal: {what} is negative ({v}); 0 never stops, k > 0 stops at the k-th occurrence")
+        return int(v)
+
+    if spec is None:
+        return (0,) * NEVENTS
+    if isinstance(spec, dict):
+        unknown = [k for k in spec if k not in EVENT_NAMES]
+        if unknown:
+            raise ValueError(f"terminal: unknown monitors {unknown}; the monitors are {list(EVENT_NAMES)}")
+        return tuple(one(spec.get(name, 0), name) for name in EVENT_NAMES)
+    spec = list(spec)
+    if len(spec) != NEVENTS:
+        raise ValueError(f"terminal: {len(spec)} entries, expected {NEVENTS} (one per monitor) or a dict keyed by monitor names")
+    return tuple(one(v, name) for v, name in zip(spec, EVENT_NAMES))
 
 
 def pack_blocks(instances, length):
@@ -232,6 +264,19 @@ class LMAHeureuxPorosityDiff:
 
     def set_option(self, name, value):
         self._check(self._lib.marl_set_option(self._ctx, name.encode(), int(value)), "marl_set_option")
+
+    def set_terminal(self, spec):
+        """Make monitors terminal - the reference's ``terminal`` switch (LHeureux_model.py:113-122), for every run of this model from
+        now on (marl_set_terminal).  ``spec`` as for :func:`terminal_counts`; None switches it off again.  Radau and BDF single runs and
+        Radau sweeps end at the root with ``status`` 1; the other integrators raise while a monitor is terminal."""
+        counts = terminal_counts(spec)
+        self._check(self._lib.marl_set_terminal(self._ctx, (C.c_int64 * NEVENTS)(*counts)), "marl_set_terminal")
+        self._terminal = counts
+
+    @property
+    def terminal(self):
+        """The limits in force, a tuple of 7 ints (0: the monitor only records)."""
+        return getattr(self, "_terminal", (0,) * NEVENTS)
 
     def use_stream(self, stream_handle):
         """Run on an existing HIP stream, e.g. ``torch.cuda.current_stream().cuda_stream``."""
@@ -651,4 +696,4 @@ class LMAHeureuxPorosityDiff:
                 for b, (s, k) in enumerate(zip(stats, n_done))]
 
 
-__all__ = ["LMAHeureuxPorosityDiff", "DepthGrid", "RK45Result", "FIELD_NAMES", "LAYOUT_FIELD_MAJOR", "LAYOUT_TILED"]
+__all__ = ["LMAHeureuxPorosityDiff", "DepthGrid", "RK45Result", "FIELD_NAMES", "EVENT_NAMES", "terminal_counts", "LAYOUT_FIELD_MAJOR", "LAYOUT_TILED"]

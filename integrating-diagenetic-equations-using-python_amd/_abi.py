@@ -72,6 +72,7 @@ PROTOTYPES = {
     "marl_last_error": (C.c_char_p, [_P]),
     "marl_set_stream": (_I, [_P, _P]),
     "marl_synchronize": (_I, [_P]),
+    "marl_set_terminal": (_I, [_P, _P]),
     "marl_set_option": (_I, [_P, C.c_char_p, _L]),
     "marl_get_constants": (_I, [_P, _L, C.POINTER(_D)]),
     "marl_state_doubles": (_L, [_P, _I]),

@@ -121,8 +121,21 @@ struct marl_ctx {
     int64_t bdf_solve_wg = 1;   // small grids: solve_bdf_system as one launch of one workgroup (marl_bdf_wg.h); 0: one launch + wait per Newton iteration
     int64_t radau_cr_tail = 1;  // the launch-bound levels of a cyclic-reduction solve in one launch each way (0: one launch per level)
     int64_t radau_sweep_wg = 3; // sweeps of small grids: 3 hybrid (workgroup per instance for the sequential work and Jacobians, launch kernels for factorisations), 1 hybrid with launch kernels for Jacobians too, 2 all in the workgroup, 0 launch per action
+    int64_t terminal[7] = {0, 0, 0, 0, 0, 0, 0};   // marl_set_terminal: monitor e ends a run at its terminal[e]-th occurrence (0: never - the reference's `terminal = False`)
     std::string err;
 };
+
+static bool has_terminal(const marl_ctx* ctx)
+{
+    for (int e = 0; e < 7; e++)
+        if (ctx->terminal[e] > 0) return true;
+    return false;
+}
+
+static int fail(marl_ctx* ctx, int code, const char* fmt, ...);
+// the entries that do not stop at a terminal monitor yet refuse a context that has one, before they touch anything
+#define NO_TERMINAL(ctx, entry) \
+    if (has_terminal(ctx)) return fail(ctx, -1, "%s: terminal monitors are not supported by this entry (marl_set_terminal)", entry);
 
 static int fail(marl_ctx* ctx, int code, const char* fmt, ...)
 {
@@ -388,6 +401,15 @@ static int stream_check(marl_ctx* ctx)
         ctx->sq_item_base = ctx->sq_level_base = 0;
         return fail(ctx, -2, "rk4: the streamed time loop gave up waiting for a neighbouring tile (rk4_stream_kernel); the state is invalid");
     }
+    return 0;
+}
+
+int marl_set_terminal(marl_ctx* ctx, const int64_t terminal[7])
+{
+    if (!ctx) return -1;
+    for (int e = 0; terminal && e < 7; e++)
+        if (terminal[e] < 0) return fail(ctx, -1, "marl_set_terminal: limit %d is negative (0: never terminal; k > 0: stop at the k-th occurrence)", e);
+    for (int e = 0; e < 7; e++) ctx->terminal[e] = terminal ? terminal[e] : 0;
     return 0;
 }
 
@@ -1274,6 +1296,7 @@ static int sweep_rk(const RkMethod& m, const char* entry, marl_ctx* ctx, double*
 {
     if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
         return ctx ? fail(ctx, -1, "%s: invalid argument", entry) : -1;
+    NO_TERMINAL(ctx, entry)
     const bool frames = n_eval > 0, roots = t_events && max_events > 0;
     if (!frames && !roots && n_done) memset(n_done, 0, sizeof(int64_t) * ctx->batch);   // nothing to sample: the plain sweep itself
     if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "%s: need first_step > 0 and t1 >= t0 (forward integration)", m.name);
@@ -1456,6 +1479,7 @@ static int integrate_rk_dev(const RkMethod& m, marl_ctx* ctx, double* y_dev, int
                             double atol, int64_t max_attempts, marl_stats* stats)
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_integrate_%s_dev: invalid argument", m.name) : -1;
+    NO_TERMINAL(ctx, (std::string("marl_integrate_") + m.name + "_dev").c_str())
     if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s_dev: single-instance context required (use %s)", m.name, m.sweep_entry);
     if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -1475,6 +1499,7 @@ static int integrate_rk(const RkMethod& m, marl_ctx* ctx, double* y, double t0, 
                         int64_t max_attempts, marl_stats* stats)
 {
     if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_%s: invalid argument", m.name) : -1;
+    NO_TERMINAL(ctx, (std::string("marl_integrate_") + m.name).c_str())
     if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s: single-instance context required (use %s)", m.name, m.sweep_entry);
     if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -1647,6 +1672,7 @@ int marl_slab_init_control(marl_ctx* ctx, const double* recs_dev, int64_t nrec, 
                            double atol, int64_t max_attempts)
 {
     SLAB_OK(ctx, "marl_slab_init_control")
+    NO_TERMINAL(ctx, "marl_slab_init_control")
     if (!recs_dev) recs_dev = ctx->dd_recs;   // library-side exchange: the records gathered by marl_slab_exchange
     if (!recs_dev || nrec < 1) return fail(ctx, -1, "marl_slab_init_control: invalid argument");
     if (!(first_step > 0) || !(t1 >= t0) || (t1 > t0 && first_step > t1 - t0)) return fail(ctx, -1, "rk45: `first_step` must be in (0, t1 - t0]");
@@ -1813,6 +1839,7 @@ int marl_slab_exchange(marl_ctx* ctx, int which)
 int marl_slab_run(marl_ctx* ctx, marl_stats* stats)
 {
     SLAB_OK(ctx, "marl_slab_run")
+    NO_TERMINAL(ctx, "marl_slab_run")
     if (!stats) return fail(ctx, -1, "marl_slab_run: invalid argument");
     if (!ctx->dd_send) return fail(ctx, -1, "marl_slab_run: call marl_slab_comm_init first");
     const int64_t nb = rk45_blocks(ctx);
@@ -2295,33 +2322,65 @@ int radau_monitors(marl_ctx* ctx, const double* y, double g[7])
 // The tail of an accepted step in the solve_ivp loop of the implicit single runs: events (ivp.py:673-694), their roots by Brent's
 // method on the step's dense output (solve_event_equation, ivp.py:51-76), and the t_eval samples (ivp.py:706-723).  g: the monitors at
 // t_old, on return g_new, those at t; dense(tq, out): the state of the step's dense output at tq -> out (device).
+// Terminal monitors (ctx->terminal, marl_terminal.h): in a step where an active monitor meets its limit the roots of all active monitors
+// are located, terminal_select says which of them happened, and *t_stop < +inf on return is where the run ends: the samples stop there,
+// and the caller writes dense(*t_stop) into its state.  Every other step: *t_stop = +inf, and exactly what happened without limits.
 template <class Dense>
 int accepted_step_epilogue(marl_ctx* ctx, RadauWork& w, double g[7], const double g_new[7], double t_old, double t, Dense&& dense,
                            const double* t_eval, int64_t n_eval, int64_t& eval_i, double* y_eval_host, double* t_events, int64_t max_events,
-                           marl_stats* st)
+                           marl_stats* st, double* t_stop)
 {
     const int64_t n = NF * ctx->N;
+    auto locate = [&](int e, double* root) -> int {
+        auto monitor_at = [&](double tq, double* v) -> int {
+            double gq[7];
+            if (int rc = dense(tq, w.tmp)) return rc;
+            if (int rc = radau_monitors(ctx, w.tmp, gq)) return rc;
+            *v = gq[e];
+            return 0;
+        };
+        double fa, fb;
+        if (int rc = monitor_at(t_old, &fa)) return rc;
+        if (int rc = monitor_at(t, &fb)) return rc;
+        return brent_root(monitor_at, t_old, fa, t, fb, root);
+    };
+    *t_stop = INFINITY;
+    uint32_t active = 0;
+    bool met = false;
     for (int e = 0; e < 7; e++) {
         const bool up = g[e] <= 0 && g_new[e] >= 0, down = g[e] >= 0 && g_new[e] <= 0;
         if (up || down) {
+            active |= 1u << e;
+            if (terminal_met(st->n_events[e] + 1, ctx->terminal[e])) met = true;
+        }
+        g[e] = g_new[e];
+    }
+    if (met) {
+        double roots[7] = {0, 0, 0, 0, 0, 0, 0};
+        int64_t counts[7];
+        for (int e = 0; e < 7; e++) {
+            counts[e] = st->n_events[e] + 1;
+            if ((active >> e) & 1)
+                if (int rc = locate(e, &roots[e])) return rc;
+        }
+        uint32_t keep = 0;
+        terminal_select(active, roots, counts, ctx->terminal, &keep, t_stop);
+        for (int e = 0; e < 7; e++) {
+            if (!((keep >> e) & 1)) continue;
+            if (t_events && st->n_events[e] < max_events) t_events[e * max_events + st->n_events[e]] = roots[e];
+            st->n_events[e]++;
+        }
+        t = *t_stop;
+    } else
+        for (int e = 0; e < 7; e++) {
+            if (!((active >> e) & 1)) continue;
             if (t_events && st->n_events[e] < max_events) {
-                auto monitor_at = [&](double tq, double* v) -> int {
-                    double gq[7];
-                    if (int rc = dense(tq, w.tmp)) return rc;
-                    if (int rc = radau_monitors(ctx, w.tmp, gq)) return rc;
-                    *v = gq[e];
-                    return 0;
-                };
-                double fa, fb, root;
-                if (int rc = monitor_at(t_old, &fa)) return rc;
-                if (int rc = monitor_at(t, &fb)) return rc;
-                if (int rc = brent_root(monitor_at, t_old, fa, t, fb, &root)) return rc;
+                double root;
+                if (int rc = locate(e, &root)) return rc;
                 t_events[e * max_events + st->n_events[e]] = root;
             }
             st->n_events[e]++;
         }
-        g[e] = g_new[e];
-    }
     while (t_eval && eval_i < n_eval && t_eval[eval_i] <= t) {
         if (int rc = dense(t_eval[eval_i], w.tmp)) return rc;
         HIP_OK(ctx, hipMemcpyAsync(y_eval_host + eval_i * n, w.tmp, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2384,7 +2443,8 @@ int radau_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_st
     double g[7], g_new[7];
     if (int rc = radau_monitors(ctx, w.y, g)) return rc;   // ivp.py:645
     int64_t eval_i = 0, attempts = 0;
-    int status = 1;
+    int status = 1;   // (running; what a run returns with status 1 is `stopped`)
+    bool stopped = false;
 
     while (status == 1) {
         if (t == t1) { status = 0; break; }
@@ -2574,9 +2634,17 @@ int radau_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_st
             for (int e = 0; e < 7; e++) g_new[e] = const_cast<const volatile double*>(ctx->zc_h)[16 + e];
         } else if (int rc = radau_monitors(ctx, w.y, g_new)) return rc;
         auto dense_at = [&](double tq, double* out) { return radau_dense(ctx, w, dense, tq, out); };
-        if (int rc = accepted_step_epilogue(ctx, w, g, g_new, t_old, t, dense_at, t_eval, n_eval, eval_i, y_eval_host, t_events, max_events, st))
+        double t_stop;
+        if (int rc = accepted_step_epilogue(ctx, w, g, g_new, t_old, t, dense_at, t_eval, n_eval, eval_i, y_eval_host, t_events, max_events, st, &t_stop))
             return rc;
+        if (t_stop <= t) {   // a terminal monitor ended the run inside this step (ivp.py:696-704): the state there, scipy's status 1
+            if (int rc = dense_at(t_stop, w.y)) return rc;
+            t = t_stop;
+            stopped = true;
+            break;
+        }
     }
+    if (stopped) status = 1;
     st->status = status;
     st->t = t;
     st->h_next = S_h_abs;
@@ -2681,7 +2749,8 @@ int bdf_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_step
     const bool solve_wg = ctx->bdf_solve_wg && ctx->zc_on && (!w.cr_k || w.plan.k) && n <= radau::PCR_FUSED_MAX && ctx->radau_fused_solve;
     if (int rc = radau_monitors(ctx, w.y, g)) return rc;
     int64_t eval_i = 0, attempts = 0;
-    int status = 1;
+    int status = 1;   // (running; what a run returns with status 1 is `stopped`)
+    bool stopped = false;
 
     while (status == 1) {
         if (t == t1) { status = 0; break; }
@@ -2879,9 +2948,17 @@ int bdf_run(marl_ctx* ctx, RadauWork& w, double t0, double t1, double first_step
         } else if (int rc = radau_monitors(ctx, w.y, g_new)) return rc;
         have_g_spec = false;
         auto dense_at = [&](double tq, double* out) { return bdf_dense(ctx, dense, tq, out); };
-        if (int rc = accepted_step_epilogue(ctx, w, g, g_new, t_old, t, dense_at, t_eval, n_eval, eval_i, y_eval_host, t_events, max_events, st))
+        double t_stop;
+        if (int rc = accepted_step_epilogue(ctx, w, g, g_new, t_old, t, dense_at, t_eval, n_eval, eval_i, y_eval_host, t_events, max_events, st, &t_stop))
             return rc;
+        if (t_stop <= t) {   // a terminal monitor ended the run inside this step (ivp.py:696-704): the state there, scipy's status 1
+            if (int rc = dense_at(t_stop, w.y)) return rc;
+            t = t_stop;
+            stopped = true;
+            break;
+        }
     }
+    if (stopped) status = 1;
     st->status = status;
     st->t = t;
     st->h_next = S_h_abs;
@@ -3031,7 +3108,7 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_radau_dev: invalid argument") : -1;
     if (n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done))) return fail(ctx, -1, "marl_sweep_radau_eval_dev: invalid argument");
-    const bool locate = t_events != nullptr && max_events > 0, frames = n_eval > 0;
+    const bool locate = t_events != nullptr && max_events > 0, frames = n_eval > 0, term = has_terminal(ctx);
     if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_radau_dev: whole-grid context required");
     if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "radau: need first_step > 0 and t1 >= t0 (forward integration)");
     if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "radau: `first_step` exceeds bounds");
@@ -3059,10 +3136,12 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     double* const drec = b_rec.as<double>();
     int32_t* const dcounts = b_counts.as<int32_t>();   // [L_COUNT] then lists [L_COUNT][B]
     int32_t* dlists = dcounts + radau::L_COUNT;
-    if (locate) {   // event root finding: monitors of the dense-output states, the root times
+    if (locate || term) {   // event root finding: monitors of the dense-output states (a step that meets a limit locates its roots with no t_events too)
         HIP_OK(ctx, b_rec_dense.alloc(sizeof(double) * NQ * B));
-        HIP_OK(ctx, b_tev.alloc(sizeof(double) * (size_t)(7 * max_events) * B));
         HIP_OK(ctx, hipMemsetAsync(b_rec_dense.p, 0, sizeof(double) * NQ * B, ctx->stream));
+    }
+    if (locate) {   // the root times
+        HIP_OK(ctx, b_tev.alloc(sizeof(double) * (size_t)(7 * max_events) * B));
         HIP_OK(ctx, hipMemsetAsync(b_tev.p, 0xff, sizeof(double) * (size_t)(7 * max_events) * B, ctx->stream));   // (all bits set: NaN)
     }
     if (frames) {   // the sample times, for the controllers (pageable host memory: the copy has left the caller's array when the call returns)
@@ -3075,9 +3154,10 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
         c.t_bound = t1; c.rtol = rtol; c.atol = atol; c.max_attempts = max_attempts;
         c.newton_tol = std::fmax(10 * radau::EPS / rtol, std::fmin(0.03, std::sqrt(rtol)));
         c.t = t0; c.S_h_abs = first_step; c.S_h_abs_old = -1; c.S_err_old = -1;
-        c.pc = radau::PC_INIT; c.status = 1;
+        c.pc = radau::PC_INIT; c.status = radau::STATUS_RUNNING;
         c.locate_events = locate ? 1 : 0; c.max_events = max_events;
         c.n_eval = n_eval;
+        for (int e = 0; e < 7; e++) c.terminal[e] = ctx->terminal[e];
     }
     HIP_OK(ctx, hipMemcpyAsync(dctl, hctl.data(), sizeof(RadauCtl) * B, hipMemcpyHostToDevice, ctx->stream));
     HIP_OK(ctx, hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
@@ -3107,7 +3187,7 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     //   2            the workgroup does those as well (no host in the loop; measured slower: cyclic reduction on ONE compute unit);
     //   0            the launch-per-action cycle (larger grids always take it).
     const int wg_mode = (n <= PCR_FUSED_MAX) ? (int)ctx->radau_sweep_wg : 0;
-    const bool use_wg = wg_mode == 2 && !locate && !frames;
+    const bool use_wg = wg_mode == 2 && !locate && !frames && !term;
     const WgWork ww = wg_mode ? wg_work_of(w, zs) : WgWork{};
     if (wg_mode) {
         if (!ctx->cus) {
@@ -3124,13 +3204,18 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
         const int64_t todo = nrun < 0 ? B : nrun;
         const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(todo, (int64_t)ctx->cus)));
         const int32_t* run_list = nrun < 0 ? nullptr : reinterpret_cast<const int32_t*>(wg_next + 2);
-#define MARL_WG_LAUNCH(VD_, H_)                                                                                                             \
-        hipLaunchKernelGGL((radau_wg_kernel<VD_, H_>), grid, dim3(WG_THREADS), 0, ctx->stream, dctl, B, N, ww, ctx->dconsts, atol, P, E3[0], E3[1], E3[2], \
+#define MARL_WG_LAUNCH(VD_, H_, T_)                                                                                                         \
+        hipLaunchKernelGGL((radau_wg_kernel<VD_, H_, T_>), grid, dim3(WG_THREADS), 0, ctx->stream, dctl, B, N, ww, ctx->dconsts, atol, P, E3[0], E3[1], E3[2], \
                            wg_next, dcounts, dlists, dtev, run_list, todo, (const double*)dteval, y_eval_dev)
+        // (a sweep with a terminal monitor never takes hybrid == 0: use_wg below; its two hybrid kinds have instantiations of their own)
         if (ctx->var_dphi) {
-            if (hybrid == 0) MARL_WG_LAUNCH(true, 0); else if (hybrid == 1) MARL_WG_LAUNCH(true, 1); else MARL_WG_LAUNCH(true, 2);
+            if (hybrid == 0) MARL_WG_LAUNCH(true, 0, false);
+            else if (hybrid == 1) { if (term) MARL_WG_LAUNCH(true, 1, true); else MARL_WG_LAUNCH(true, 1, false); }
+            else { if (term) MARL_WG_LAUNCH(true, 2, true); else MARL_WG_LAUNCH(true, 2, false); }
         } else {
-            if (hybrid == 0) MARL_WG_LAUNCH(false, 0); else if (hybrid == 1) MARL_WG_LAUNCH(false, 1); else MARL_WG_LAUNCH(false, 2);
+            if (hybrid == 0) MARL_WG_LAUNCH(false, 0, false);
+            else if (hybrid == 1) { if (term) MARL_WG_LAUNCH(false, 1, true); else MARL_WG_LAUNCH(false, 1, false); }
+            else { if (term) MARL_WG_LAUNCH(false, 2, true); else MARL_WG_LAUNCH(false, 2, false); }
         }
 #undef MARL_WG_LAUNCH
     };
@@ -3139,13 +3224,14 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
         LAUNCH_OK(ctx);
     }
     int64_t wg_nrun = -1;
-    const bool hybrid = wg_mode == 1 || wg_mode == 3 || (wg_mode == 2 && (locate || frames));
+    const bool hybrid = wg_mode == 1 || wg_mode == 3 || (wg_mode == 2 && (locate || frames || term));
     const int hybrid_kind = wg_mode == 3 ? 2 : 1;   // 2: Jacobians stay in the workgroup, only factorisations come back to the host cycle
     for (int64_t cycle = 0; !use_wg; cycle++) {
         // the controllers advance every instance to its next piece of work and sort the instances into work lists; the host
         // reads the list lengths (sweep_read_counts) and launches each kind of work over its list only
         if (hybrid) launch_wg(hybrid_kind, wg_nrun);   // every running instance up to its next Jacobian / factorisation (or its end)
-        else hipLaunchKernelGGL(radau_control_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, drec_dense, dtev, dteval);
+        else if (term) hipLaunchKernelGGL(radau_control_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, drec_dense, dtev, dteval);
+        else hipLaunchKernelGGL(radau_control_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, drec_dense, dtev, dteval);
         LAUNCH_OK(ctx);
         if (int rc = sweep_read_counts(ctx, dcounts, L_COUNT, cycle, hcounts)) return rc;
         if (hcounts[L_RUNNING] == 0) break;
@@ -3157,7 +3243,8 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
             wg_nrun = nj + nl;
         }
         const unsigned nR = (unsigned)hcounts[L_RHS1], nA = (unsigned)hcounts[L_ACCEPT], nJ = (unsigned)hcounts[L_JAC], nL = (unsigned)hcounts[L_LU],
-                       nN = (unsigned)hcounts[L_NEWTON], nE = (unsigned)hcounts[L_ERR], nD = (unsigned)hcounts[L_DENSE], nF = (unsigned)hcounts[L_FRAME];
+                       nN = (unsigned)hcounts[L_NEWTON], nE = (unsigned)hcounts[L_ERR], nD = (unsigned)hcounts[L_DENSE], nF = (unsigned)hcounts[L_FRAME],
+                       nS = (unsigned)hcounts[L_STOP];
         if (nF) {   // t_eval samples inside the accepted step: its dense output into the instances' frames (no monitors: nothing reads a frame)
             hipLaunchKernelGGL(frame_eval_batch_kernel, dim3(gx, 1, nF), b256, 0, ctx->stream, w.Q, w.yold, n, y_eval_dev, n_eval, Z(L_FRAME));
             LAUNCH_OK(ctx);
@@ -3183,7 +3270,11 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
             hipLaunchKernelGGL(accept_kernel, dim3(gx, 1, nA), b256, 0, ctx->stream, w.Z, w.Q, w.y, w.yold, w.ynew, w.f, w.fnew, n, P, Z(L_ACCEPT));
             LAUNCH_OK(ctx);
         }
-        if ((nA || cycle == 0) && !hybrid) {   // monitors of every instance's y (read by the controllers after the start and after each accepted step)
+        if (nS) {   // a terminal monitor ended these instances' runs inside the step just accepted: its dense output at t_stop is their state
+            hipLaunchKernelGGL(stop_state_batch_kernel, dim3(gx, 1, nS), b256, 0, ctx->stream, w.Q, w.yold, n, w.y, Z(L_STOP));
+            LAUNCH_OK(ctx);
+        }
+        if ((nA || nS || cycle == 0) && !hybrid) {   // monitors of every instance's y (read by the controllers after the start, after each accepted step and after a stop)
             hipLaunchKernelGGL(monitors_kernel<LAYOUT_FIELD_MAJOR>, dim3((unsigned)nbm, (unsigned)B), b256, 0, ctx->stream, w.y, ctx->dconsts, ctx->slab, zs / 8, ctx->part);
             LAUNCH_OK(ctx);
             hipLaunchKernelGGL(reduce_records_kernel, dim3((unsigned)B), b256, 0, ctx->stream, ctx->part, nbm, drec);
@@ -3223,6 +3314,7 @@ static int sweep_radau(marl_ctx* ctx, double* y_dev, double t0, double t1, doubl
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < B; b++) {
         ctl_to_stats(hctl[(size_t)b], stats[b]);
+        if (hctl[(size_t)b].pc != radau::PC_DONE) return fail(ctx, -3, "marl_sweep_radau_dev: instance %lld did not finish", (long long)b);
         if (frames) n_done[b] = hctl[(size_t)b].fr_next;
     }
     if (t1 == t0 && frames && t_eval[0] == t0) {   // no step is taken (base.py:189-194): the sample at t0 is y0, as the single run gives it
@@ -3314,6 +3406,7 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_bdf_dev: invalid argument") : -1;
     if (n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done))) return fail(ctx, -1, "marl_sweep_bdf_eval_dev: invalid argument");
+    NO_TERMINAL(ctx, "marl_sweep_bdf_dev")
     if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_bdf_dev: whole-grid context required");
     if (int rc = check_ivp_args(ctx, "bdf", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
     const bool frames = n_eval > 0, locate = t_events && max_events > 0;

@@ -69,7 +69,7 @@ __device__ inline cplx lift(double a, cplx) { return {a, 0.0}; }
 // Batched sweeps of Radau instances (marl_radau_batch.h): every instance follows its own control flow, advanced one ACTION per
 // cycle by a device-side controller; the kernels below serve the single-instance driver (ctl == NULL, scalar arguments) and the
 // batched one (blockIdx.z = instance; per-instance scalars from ctl[z]; ZBatch masks out instances that need something else).
-enum : int32_t { A_RHS_Y = 1, A_JAC = 2, A_LU = 4, A_NEWTON = 8, A_ERR = 16, A_ACCEPT = 32, A_ERR2 = 64, A_DENSE = 128, A_FRAME = 256 };
+enum : int32_t { A_RHS_Y = 1, A_JAC = 2, A_LU = 4, A_NEWTON = 8, A_ERR = 16, A_ACCEPT = 32, A_ERR2 = 64, A_DENSE = 128, A_FRAME = 256, A_STOP = 512 };
 struct RadauCtl {
     // set once
     double t_bound, rtol, atol, newton_tol;
@@ -89,17 +89,24 @@ struct RadauCtl {
     int32_t current_jac, have_lu, have_sol, have_factor, rejected, k, n_iter, recompute_jac, newton_begin, err_second;
     // results the kernels leave for the controller
     double sumsq;                    // sum of squares of the last norm kernel
-    int32_t nonfinite, pad;
+    int32_t nonfinite;
+    int32_t tm_step;                 // terminal monitors: the step just accepted meets a limit - every active monitor's root goes to tm_root first
     // event root finding inside a sweep (round 3; ivp.py:673-694 + solve_event_equation :51-76, Brent as in scipy's brentq): a resumable
     // state machine - every function evaluation is one A_DENSE action (dense output at dense_x, monitors of that state)
-    int32_t locate_events, ev_pending, br_e, br_phase, br_iter, pad2;   // ev_pending: bit e = monitor e changed sign in the step just accepted
+    int32_t locate_events, ev_pending, br_e, br_phase, br_iter;   // ev_pending: bit e = monitor e changed sign in the step just accepted
+    int32_t tm_active;               // terminal monitors: the monitors that changed sign in a step with tm_step (ev_pending empties as roots arrive)
     int64_t max_events;
     double dense_x;                  // (t - sol_t_old) / sol_h of the state the A_DENSE kernels evaluate
     double br_a, br_b, br_fa, xpre, xcur, xblk, fpre, fcur, fblk, spre, scur;
     // t_eval frames inside a sweep (ivp.py:706-723): after the roots of an accepted step, one A_FRAME action per sample inside it - the
     // dense output at dense_x written to frame fr_next of the instance.  n_eval = 0: no samples (set once)
     int64_t n_eval, fr_next;         // fr_next: the frames written so far = the index of the next sample
-    int32_t fr_wait, pad3;           // fr_wait: an A_FRAME action is out; count it on resume
+    int32_t fr_wait;                 // fr_wait: an A_FRAME action is out; count it on resume
+    int32_t stopped;                 // a terminal monitor ended the run at t (marl_terminal.h): status 1 once the samples <= t are written
+    // terminal monitors (marl_set_terminal; ivp.py:79-130, 681-704): the limits (set once; 0: never terminal) and, in a step that meets
+    // one, the roots of all its active monitors until terminal_select has said which of them happened
+    int64_t terminal[7];
+    double tm_root[7];
 };
 __device__ __forceinline__ const RadauCtl* ctl_of(const ZBatch& B)
 {

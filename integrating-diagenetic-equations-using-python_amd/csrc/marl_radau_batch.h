@@ -11,12 +11,14 @@
 // (ZBatch) - and reads one counter of still-running instances every few cycles.  Instances desynchronise freely.
 #pragma once
 #include "marl_radau.h"
+#include "marl_terminal.h"
 
 namespace marl {
 namespace radau {
 
 enum : int32_t { PC_INIT = 0, PC_GOT_F0, PC_STEP, PC_ATTEMPT, PC_NEWTON_START, PC_NEWTON_LU_DONE, PC_NEWTON_ITER, PC_ERR_DONE, PC_ACCEPTED, PC_ACCEPTED_JAC_DONE, PC_DONE,
-                 PC_EVENTS, PC_BRENT, PC_FRAMES };
+                 PC_EVENTS, PC_BRENT, PC_FRAMES, PC_STOPPED };
+constexpr int32_t STATUS_RUNNING = -2;   // RadauCtl::status until PC_DONE (1 is scipy's "a termination event occurred": marl_stats.status)
 constexpr int NEWTON_MAXITER = 6;
 
 __device__ __forceinline__ double predict_factor(double h_abs, double h_abs_old, double error_norm, double error_norm_old)   // radau.py:133-173
@@ -31,13 +33,18 @@ __device__ __forceinline__ double predict_factor(double h_abs, double h_abs_old,
 // Work lists: the controller appends each instance to the list of every kernel group that serves its action; counts[L_*] are read by
 // the host, which sizes the launches by them (masked-out workgroups are not free: at 512 instances a cycle that launched every kernel
 // over every instance spent 2.4 ms dispatching ~320 000 workgroups that returned at once).
-enum : int { L_RHS1 = 0, L_ACCEPT, L_JAC, L_LU, L_NEWTON, L_ERR, L_RUNNING, L_DENSE, L_FRAME, L_COUNT };
+enum : int { L_RHS1 = 0, L_ACCEPT, L_JAC, L_LU, L_NEWTON, L_ERR, L_RUNNING, L_DENSE, L_FRAME, L_STOP, L_COUNT };
 static_assert(L_COUNT + 1 <= 32, "the host's two count buffers hold 32 words (the lengths, then the sequence word)");
 
 // One instance's step logic from where it stopped to its next action (c.action, c.pc).  g_now: the seven monitors of the instance's y.
 // (Brent's method: brent_advance, marl_brent.h - shared with the RK45 sweep that locates roots, on RadauCtl's own fields here.)
 // g_dense: the seven monitors of the dense-output state the last A_DENSE action evaluated (event root finding); t_events: this
 // instance's root times [7][max_events] (NULL: sign changes are only counted).  t_eval: the c.n_eval sample times of the sweep.
+// Terminal monitors (c.terminal, marl_terminal.h): a step in which an active monitor meets its limit locates the roots of ALL its active
+// monitors (slot or no slot, t_events or none - g_dense is needed then), lets terminal_select say which happened, and ends the run with
+// one A_STOP action: roots -> stop -> samples <= t_stop -> status 1.  Every other step runs exactly as without limits.
+// TERM = false compiles none of that: a sweep without limits runs the controller and the kernels it had before there were any.
+template <bool TERM = false>
 __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g_now)[7], int64_t n, const double* g_dense = nullptr, double* t_events = nullptr,
                                                    const double* t_eval = nullptr)
 {
@@ -194,7 +201,23 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
             c.sol_h = c.t - c.sol_t_old;
             c.have_sol = 1;
             c.ev_pending = 0;
-            for (int e = 0; e < 7; e++) {        // non-terminal events, both directions (ivp.py:131-156)
+            if constexpr (TERM) {                // does an active monitor meet its limit with this occurrence? (ivp.py:680-683; one compare per monitor)
+                c.tm_step = 0; c.tm_active = 0;
+                for (int e = 0; e < 7; e++) {
+                    const bool up = c.g[e] <= 0 && g_now[e] >= 0, down = c.g[e] >= 0 && g_now[e] <= 0;
+                    if (up || down) {
+                        c.tm_active |= 1 << e;
+                        if (terminal_met(c.n_events[e] + 1, c.terminal[e])) c.tm_step = 1;
+                    }
+                }
+                if (c.tm_step) {                 // the order of ALL the step's roots decides what happened: locate every one, count none yet
+                    c.ev_pending = c.tm_active;
+                    for (int e = 0; e < 7; e++) c.g[e] = g_now[e];
+                    pc = PC_EVENTS;
+                    continue;
+                }
+            }
+            for (int e = 0; e < 7; e++) {        // events that do not end the run, both directions (ivp.py:131-156)
                 const bool up = c.g[e] <= 0 && g_now[e] >= 0, down = c.g[e] >= 0 && g_now[e] <= 0;
                 if (up || down) {
                     if (c.locate_events && t_events && c.n_events[e] < c.max_events) c.ev_pending |= 1 << e;   // located below; the count moves with the root
@@ -206,6 +229,23 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
             continue;
         }
         if (pc == PC_EVENTS) {                   // the next monitor whose root in (sol_t_old, t] is still to be located (ivp.py:686-694)
+            if (TERM && c.ev_pending == 0 && c.tm_step) {   // every root of a step that meets a limit is known: which monitors happened, and where it ends
+                int64_t counts[7];
+                for (int e = 0; e < 7; e++) counts[e] = c.n_events[e] + 1;
+                uint32_t keep = 0;
+                double t_stop = c.t;
+                terminal_select((uint32_t)c.tm_active, c.tm_root, counts, c.terminal, &keep, &t_stop);
+                for (int e = 0; e < 7; e++) {    // a monitor after the terminal one is neither stored nor counted
+                    if (!((keep >> e) & 1)) continue;
+                    if (c.locate_events && t_events && c.n_events[e] < c.max_events) t_events[(int64_t)e * c.max_events + c.n_events[e]] = c.tm_root[e];
+                    c.n_events[e]++;
+                }
+                c.tm_step = 0;
+                c.t = t_stop;
+                c.dense_x = (t_stop - c.sol_t_old) / c.sol_h;   // (the expression of a sample at t_stop: PC_FRAMES)
+                c.action = A_STOP; pc = PC_STOPPED;   // kernels: y <- the step's dense output at t_stop, monitors(y)
+                break;
+            }
             if (c.ev_pending == 0) { pc = PC_FRAMES; continue; }
             int e = 0;
             while (!((c.ev_pending >> e) & 1)) e++;
@@ -247,10 +287,19 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
                     break;
                 }
             }
-            t_events[(int64_t)c.br_e * c.max_events + c.n_events[c.br_e]] = root;
-            c.n_events[c.br_e]++;
+            if (TERM && c.tm_step) c.tm_root[c.br_e] = root;   // (stored and counted once terminal_select has kept it: PC_EVENTS)
+            else {
+                t_events[(int64_t)c.br_e * c.max_events + c.n_events[c.br_e]] = root;
+                c.n_events[c.br_e]++;
+            }
             c.ev_pending &= ~(1 << c.br_e);
             pc = PC_EVENTS;
+            continue;
+        }
+        if (TERM && pc == PC_STOPPED) {          // y is the state at t = t_stop, g_now its monitors; then the samples up to t_stop, and the end
+            for (int e = 0; e < 7; e++) c.g[e] = g_now[e];
+            c.stopped = 1;
+            pc = PC_FRAMES;
             continue;
         }
         if (pc == PC_FRAMES) {                   // the samples in (sol_t_old, t] - and t0 with the first step - by dense output (ivp.py:706-723)
@@ -261,6 +310,7 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
                 c.action = A_FRAME;              // frame fr_next of this instance
                 break;
             }
+            if (TERM && c.stopped) { c.status = 1; pc = PC_DONE; break; }   // scipy's status 1: "A termination event occurred." (ivp.py:701-704)
             if (c.t - c.t_bound >= 0) { c.status = 0; pc = PC_DONE; break; }   // (no samples: reached in the cycle that accepted the step, as before)
             pc = PC_STEP;
             continue;
@@ -270,6 +320,7 @@ __device__ __forceinline__ void radau_control_step(RadauCtl& c, const double (&g
     c.pc = pc;
 }
 
+template <bool TERM>
 __global__ void __launch_bounds__(64) radau_control_kernel(RadauCtl* __restrict__ ctls, const double* __restrict__ rec, int64_t B, int64_t n,
                                                            int32_t* __restrict__ counts, int32_t* __restrict__ lists,
                                                            const double* __restrict__ rec_dense = nullptr, double* __restrict__ t_events = nullptr,
@@ -287,7 +338,7 @@ __global__ void __launch_bounds__(64) radau_control_kernel(RadauCtl* __restrict_
         const double gd[7] = {d[1], d[2], d[3], d[5] - 1.0, d[6] - 1.0, d[4], d[7]};
         for (int e = 0; e < 7; e++) g_dense[e] = gd[e];
     }
-    radau_control_step(c, g_now, n, g_dense, t_events ? t_events + b * 7 * c.max_events : nullptr, t_eval);
+    radau_control_step<TERM>(c, g_now, n, g_dense, t_events ? t_events + b * 7 * c.max_events : nullptr, t_eval);
     const int pc = c.pc;
     ctls[b] = c;
     if (pc != PC_DONE) atomicAdd(&counts[L_RUNNING], 1);
@@ -300,6 +351,7 @@ __global__ void __launch_bounds__(64) radau_control_kernel(RadauCtl* __restrict_
     if (c.action & (A_ERR | A_ERR2)) push(L_ERR);
     if (c.action & A_DENSE) push(L_DENSE);
     if (c.action & A_FRAME) push(L_FRAME);
+    if (TERM && (c.action & A_STOP)) push(L_STOP);
 }
 
 // A_DENSE: the dense output of the step just accepted at x = ctl.dense_x (RadauDenseOutput, radau.py:557-572; dense_eval_kernel) -> out
@@ -330,6 +382,21 @@ __global__ void __launch_bounds__(256) frame_eval_batch_kernel(const double* __r
     const double q0 = Q[3 * i], q1 = Q[3 * i + 1], q2 = Q[3 * i + 2], yo = yold[i];
     const double p1 = c->dense_x, p2 = p1 * p1, p3 = p2 * p1;
     out[i] = dot3(q0, p1, q1, p2, q2, p3) + yo;
+}
+
+// A_STOP: a terminal monitor ended the run inside the step just accepted: the same dense output at t_stop -> the instance's y (what a
+// frame at t_eval = t_stop holds, bit for bit).  The monitors of every y follow, as after an accepted step.
+__global__ void __launch_bounds__(256) stop_state_batch_kernel(const double* __restrict__ Q, const double* __restrict__ yold, int64_t n, double* __restrict__ y,
+                                                               ZBatch B)
+{
+    if (z_masked_out(B)) return;
+    const RadauCtl* c = ctl_of(B);
+    Q = z_shift(Q, B); yold = z_shift(yold, B); y = z_shift(y, B);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double q0 = Q[3 * i], q1 = Q[3 * i + 1], q2 = Q[3 * i + 2], yo = yold[i];
+    const double p1 = c->dense_x, p2 = p1 * p1, p3 = p2 * p1;
+    y[i] = dot3(q0, p1, q1, p2, q2, p3) + yo;
 }
 
 // ---- element-wise kernels of the batch (blockIdx.z = instance; scalars from the instance's controller) ---------------------

@@ -149,7 +149,9 @@ __device__ __forceinline__ double wg_sum(double ss, double* red)
 // counts / lists: the work lists of marl_radau_batch.h (L_JAC, L_LU, L_RUNNING); g_dense / t_events: event root finding (may be NULL).
 // HYBRID is a template parameter (round 4): the instantiation the sweeps use by default (2) then carries neither the in-workgroup
 // factorisation (a 5 x 5 Gauss-Jordan per lane group: the register-hungriest piece) nor its share of the kernel's spills.
-template <bool VD, int HYBRID = 0>
+// TERM (terminal monitors, marl_set_terminal): the controller's terminal steps and the A_STOP block exist in the instantiations a sweep
+// with a limit launches, and nowhere else - without limits the kernel is the one it was.
+template <bool VD, int HYBRID = 0, bool TERM = false>
 __global__ void __launch_bounds__(WG_THREADS) radau_wg_kernel(RadauCtl* __restrict__ ctls, int64_t B, int64_t N, WgWork w, const DevConsts* __restrict__ consts,
                                                               double fd_threshold, P33 P, double E0, double E1, double E2, unsigned* __restrict__ next_instance,
                                                               int32_t* __restrict__ counts = nullptr, int32_t* __restrict__ lists = nullptr,
@@ -194,7 +196,7 @@ __global__ void __launch_bounds__(WG_THREADS) radau_wg_kernel(RadauCtl* __restri
             if (tid == 0) {
                 double g[7], gd[7];
                 for (int e = 0; e < 7; e++) { g[e] = g_now[e]; gd[e] = g_dense[e]; }
-                radau_control_step(sc, g, n, gd, t_events ? t_events + b * 7 * sc.max_events : nullptr, t_eval);
+                radau_control_step<TERM>(sc, g, n, gd, t_events ? t_events + b * 7 * sc.max_events : nullptr, t_eval);
             }
             __syncthreads();
             WG_TICK(0);
@@ -224,6 +226,15 @@ __global__ void __launch_bounds__(WG_THREADS) radau_wg_kernel(RadauCtl* __restri
                 double* out = y_eval + (b * sc.n_eval + sc.fr_next) * n;
                 const double p1 = sc.dense_x, p2 = p1 * p1, p3 = p2 * p1;
                 for (int64_t i = tid; i < n; i += WG_THREADS) out[i] = dot3(Q[3 * i], p1, Q[3 * i + 1], p2, Q[3 * i + 2], p3) + yold[i];
+            }
+            // ---- a terminal monitor ended the run inside the accepted step: the same dense output at t_stop -> y, and that state's monitors
+            // (stop_state_batch_kernel, then the monitors of y as after an accepted step)
+            if (TERM && (action & A_STOP)) {
+                const double *Q = wg_at(w.Q, off), *yold = wg_at(w.yold, off);
+                const double p1 = sc.dense_x, p2 = p1 * p1, p3 = p2 * p1;
+                for (int64_t i = tid; i < n; i += WG_THREADS) y[i] = dot3(Q[3 * i], p1, Q[3 * i + 1], p2, Q[3 * i + 2], p3) + yold[i];
+                __syncthreads();
+                wg_monitors(y, N, C, T, buf.red, g_now);
             }
 
             // ---- a single state -> its derivative: y -> f (start), y + err -> tmp (second error estimate), y_new -> f_new (accepted step)

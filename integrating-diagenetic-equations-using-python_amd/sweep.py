@@ -110,10 +110,13 @@ class HipSweepEngine:
             r.y = frames[b, :len(r.t)].T.copy()
         return yd.cpu().numpy(), res
 
-    def integrate_radau(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64):
+    def integrate_radau(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
         """The reference's default solver over the shard: every instance its own Radau step logic, advanced together on the device
         (marl_sweep_radau_dev).  Returns (y_final (n_local, 5N), list of RK45Result); ``t_eval`` and ``events`` as for
-        :meth:`integrate_rk45` (marl_sweep_radau_eval_dev: samples and roots on the accepted step's dense output, inside the sweep)."""
+        :meth:`integrate_rk45` (marl_sweep_radau_eval_dev: samples and roots on the accepted step's dense output, inside the sweep).
+        ``terminal`` (see :func:`marlpde_amd.LHeureux_model.terminal_counts`): monitors that end an instance's run at their root -
+        status 1, ``t_reached`` the root, the state the dense output there; None: none, whatever an earlier call set."""
+        self.model.set_terminal(terminal)
         yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
         more = {"events": True, "max_events": max_events} if events else {}
         if t_eval is None:
@@ -212,15 +215,18 @@ def initial_states(base_parms, instances):
 
 
 def run_sweep_radau(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                    device=None, engine_factory=None, gather=True, balance="cost", cost=None, t_eval=None, events=False, max_events=64):
+                    device=None, engine_factory=None, gather=True, balance="cost", cost=None, t_eval=None, events=False, max_events=64,
+                    terminal=None):
     """As :func:`run_sweep_rk45` with the reference's DEFAULT solver (scipy Radau semantics, marlpde/parameters.py:213): what the
     reference does one scenario per process (its tests loop over scenarios), spread over the ranks with no data-path collective.
     An implicit run's cost depends on the scenario (20x between the fastest and the slowest of a parameter grid), and the slowest
     rank sets the wall time: ``balance`` = ``"cost"`` (default: :func:`assign` by ``cost``, or by :func:`implicit_cost_proxy` when
     none is given), ``"round_robin"`` or ``"contiguous"``.  Results come back in the order of ``instances`` whatever the assignment.
-    ``t_eval``, ``events``, ``max_events`` and what they add to the returned tuple: as documented for :func:`run_sweep_rk45`."""
+    ``t_eval``, ``events``, ``max_events`` and what they add to the returned tuple: as documented for :func:`run_sweep_rk45`.
+    ``terminal`` (the reference's switch, marlpde/LHeureux_model.py:113-122; see :func:`marlpde_amd.LHeureux_model.terminal_counts`):
+    an instance whose terminal monitor fires ends there - ``status`` 1, ``t_reached`` the root - and stops bounding the sweep."""
     return _run_sweep("integrate_radau", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, t_eval, events, max_events)
+                      balance, cost, t_eval, events, max_events, terminal=terminal)
 
 
 def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
@@ -262,7 +268,7 @@ def run_sweep_rk23(base_parms, instances, t_span, first_step, rtol, atol, max_at
 
 
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64, batched=False):
+               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64, batched=False, terminal=None):
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -287,6 +293,8 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
             more |= {"events": True, "max_events": max_events}
         if batched:   # (the BDF driver; passed only when asked for, like `events`)
             more |= {"batched": True}
+        if terminal is not None:   # (the Radau driver; passed only when asked for)
+            more |= {"terminal": terminal}
         y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()
     else:   # (more ranks than instances)
