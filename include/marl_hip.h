@@ -69,8 +69,9 @@ int marl_synchronize(marl_ctx* ctx);
  *   nfev / njev / nlu / n_accepted / n_rejected are those after the accepted step: roots and samples cost no evaluation.
  * In such a step the roots of ALL active monitors are located (the order needs them), with or without a free slot and also when the
  * caller passed no t_events; they are stored only where a slot is free.  A step that meets no limit runs exactly as without limits.
- * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev.  Every other
- * integrator entry (marl_integrate_rk45 / rk23 [_dev], marl_sweep_rk45* / rk23*, marl_sweep_bdf*, marl_slab_init_control,
+ * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev,
+ * marl_sweep_bdf_terminal_dev.  Every other
+ * integrator entry (marl_integrate_rk45 / rk23 [_dev], marl_sweep_rk45* / rk23*, marl_sweep_bdf_dev / _eval_dev / _events_dev, marl_slab_init_control,
  * marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
  * before it touches the state, and is unchanged when none is. */
 int marl_set_terminal(marl_ctx* ctx, const int64_t terminal[7]);
@@ -158,7 +159,7 @@ int marl_debug_num_jac(marl_ctx* ctx, const double* y, double threshold, const i
                        double* J_out);
 int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jscale, double mu_r, double mu_c_re, double mu_c_im, int systems,
                            int64_t nrhs, const double* b_r, const double* b_c, double* x_r, double* x_c);
-/* Test hook of the BDF sweep (the marl_sweep_bdf entries below): ONE launch of one of its five data-parallel kernels, through the launcher
+/* Test hook of the BDF sweep (the marl_sweep_bdf entries below): ONE launch of one of its six data-parallel kernels, through the launcher
  * the sweep itself calls, on the sweep's arena (one per instance of the context, B = n_instances, at the sweep's stride).  HOST pointers;
  * whole-grid context with 5N <= 2048; synchronises.  n = 5N.
  *   op: MARL_BDF_INIT_D        D[0] = y, D[1] = f h
@@ -170,9 +171,12 @@ int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jscale, double
  *                              BdfDenseOutput(t - h, t, h, order, D)
  *       MARL_BDF_ROOTS         the root times over [t_old, t] of the monitors in `mask` on the same dense output, monitor e's into
  *                              t_events[instance][e][slot[e]]
+ *       MARL_BDF_STOP          the state a terminal monitor leaves (marl_sweep_bdf_terminal_dev): y = the same dense output at t_stop,
+ *                              which dargs passes in the place of t_old, and that state's seven monitors, monitor e's into
+ *                              t_events[instance][e][0] (max_events > 0)
  *   list, n_list: the instances launched, in this order (grid.z = n_list), each in [0, B), n_list <= B; NULL, 0: all B in order.
  *   iargs: int64[B][MARL_BDF_DEBUG_INTS] per instance {order, want_norms, first, end, mask, slot[0 .. 6]}.
- *   dargs: float64[B][MARL_BDF_DEBUG_DOUBLES] per instance {h, rtol, atol, err_coef_m, err_coef_p, t, t_old, RU[6][6] row-major}.
+ *   dargs: float64[B][MARL_BDF_DEBUG_DOUBLES] per instance {h, rtol, atol, err_coef_m, err_coef_p, t, t_old (STOP: t_stop), RU[6][6] row-major}.
  *   D_in: float64[B][8][n], all eight rows of every instance's differences; vec_in: float64[B][4][n], the instance's y, f, d, ynew.
  *   t_eval: float64[n_eval] (SAMPLE; n_eval may be 0).  max_events: root slots per monitor (ROOTS: > 0).
  *   Out - everything the kernel may write and its surroundings: D_out [B][8][n]; y_out [B][n]; frames [B][n_eval][n], t_events
@@ -180,8 +184,8 @@ int marl_debug_block_solve(marl_ctx* ctx, const double* J, double jscale, double
  *   comes back where the kernel wrote nothing.
  *   Returns -1 with a message, launching nothing, when an argument is out of range: an order outside 1 .. 5 (every op but INIT_D), a list
  *   entry outside [0, B) or n_list > B, first > end or first < 0, want_norms outside 0 .. 3, a mask outside 0 .. 127, ROOTS with
- *   max_events <= 0 or a searched monitor's slot outside [0, max_events), 5N > 2048. */
-enum { MARL_BDF_INIT_D = 0, MARL_BDF_CHANGE_D = 1, MARL_BDF_ACCEPT_NORMS = 2, MARL_BDF_SAMPLE = 3, MARL_BDF_ROOTS = 4 };
+ *   max_events <= 0 or a searched monitor's slot outside [0, max_events), STOP with max_events <= 0, 5N > 2048. */
+enum { MARL_BDF_INIT_D = 0, MARL_BDF_CHANGE_D = 1, MARL_BDF_ACCEPT_NORMS = 2, MARL_BDF_SAMPLE = 3, MARL_BDF_ROOTS = 4, MARL_BDF_STOP = 5 };
 enum { MARL_BDF_DEBUG_INTS = 12, MARL_BDF_DEBUG_DOUBLES = 43 };
 int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, int64_t n_list, const int64_t* iargs, const double* dargs,
                          const double* D_in, const double* vec_in, const double* t_eval, int64_t n_eval, int64_t max_events,
@@ -359,6 +363,23 @@ int marl_sweep_bdf_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, 
 int marl_sweep_bdf_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                               const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                               int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* The same sweep HONOURING TERMINAL MONITORS (marl_set_terminal; scipy's handle_events and the end of a terminated run, ivp.py:79-130,
+ * 681-723; the rule: csrc/marl_terminal.h): the reference's `terminal` switch (marlpde/LHeureux_model.py:113-122) for BDF sweeps.  The
+ * three entries above refuse a context with limits; this one stops every instance at its terminal monitor's root on the device.
+ * In an accepted step over which a monitor changed sign that thereby meets its limit, the instance's controller (csrc/marl_bdf_ctl.h,
+ * BdfTerm) has the roots of ALL monitors that changed sign located on the step's dense output - the search of the entry above, one
+ * workgroup, with or without root slots or t_events - and in its next cycle applies the rule: the monitors up to and including the
+ * terminal one in the order of root times are counted and, where a slot is free, stored; later ones never happened.  Then
+ * stats[b].status = 1, stats[b].t = t_stop, the state of instance b is the step's dense output at t_stop (stop_state_batch_kernel: the
+ * expression that writes a frame, so a frame at t_eval = t_stop equals it bit for bit), stats[b].event_value are that state's monitors,
+ * the samples with t_eval[k] <= t_stop are written and counted in n_done[b], later frames stay untouched, and the counters are those
+ * after the accepted step.  A stopped instance costs one cycle more and takes no further part: the sweep ends with its last live
+ * instance.  Instances that meet no limit, and every step before the terminal one, run exactly as under marl_sweep_bdf_events_dev;
+ * with no limit set this entry IS that one, bit for bit.  Arguments as for marl_sweep_bdf_events_dev (t_eval / n_eval = 0 and
+ * t_events == NULL / max_events <= 0 allowed).  Synchronises. */
+int marl_sweep_bdf_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
 /* ---- 1-D domain decomposition of ONE large grid (BASELINE config 5; the reference never decomposes the depth
  * axis).  One process per GPU holds a slab [g_begin, g_end) of the N_global cells in a slab context; the host

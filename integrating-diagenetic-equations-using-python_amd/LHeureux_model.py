@@ -268,7 +268,7 @@ class LMAHeureuxPorosityDiff:
     def set_terminal(self, spec):
         """Make monitors terminal - the reference's ``terminal`` switch (LHeureux_model.py:113-122), for every run of this model from
         now on (marl_set_terminal).  ``spec`` as for :func:`terminal_counts`; None switches it off again.  Radau and BDF single runs and
-        Radau sweeps end at the root with ``status`` 1; the other integrators raise while a monitor is terminal."""
+        Radau and BDF sweeps end at the root with ``status`` 1; the other integrators raise while a monitor is terminal."""
         counts = terminal_counts(spec)
         self._check(self._lib.marl_set_terminal(self._ctx, (C.c_int64 * NEVENTS)(*counts)), "marl_set_terminal")
         self._terminal = counts
@@ -507,7 +507,7 @@ class LMAHeureuxPorosityDiff:
                                                      _as_ptr(x_c) if b_c is not None else None), "marl_debug_block_solve")
         return x_r if b_c is None else (x_r, x_c)
 
-    BDF_BATCH_OPS = {"INIT_D": 0, "CHANGE_D": 1, "ACCEPT_NORMS": 2, "SAMPLE": 3, "ROOTS": 4}   # include/marl_hip.h: MARL_BDF_*
+    BDF_BATCH_OPS = {"INIT_D": 0, "CHANGE_D": 1, "ACCEPT_NORMS": 2, "SAMPLE": 3, "ROOTS": 4, "STOP": 5}   # include/marl_hip.h: MARL_BDF_*
 
     def debug_bdf_batch(self, op, D, y=None, f=None, d=None, ynew=None, *, instances=None, order=1, h=1.0, RU=None, rtol=1e-3, atol=1e-3,
                         want_norms=0, err_coef_m=0.0, err_coef_p=0.0, t=0.0, t_old=0.0, first=0, end=0, mask=0, slot=None, t_eval=None,
@@ -517,7 +517,9 @@ class LMAHeureuxPorosityDiff:
         (B, 5N) or None (zeros).  ``instances``: the work list (instance indices in launch order) or None for all in order.  The scalars
         ``order`` .. ``mask`` are one value or one per instance, ``RU``: (B, 6, 6) or (6, 6), ``slot``: (B, 7) or (7,).  ``frames``
         (B, n_eval, 5N), ``t_events`` (B, 7, max_events) and ``ss`` (B, 2) hold what is on the device before the launch (sentinels);
-        None: no frames / no root slots / zeros.  Returns a dict of copies - D, y, frames, t_events, ss - as the launch left them."""
+        None: no frames / no root slots / zeros.  Returns a dict of copies - D, y, frames, t_events, ss - as the launch left them.
+        ``"STOP"`` (the state a terminal monitor leaves) reads its ``t_stop`` from ``t_old`` and returns the seven monitors of the
+        listed instances' states in ``t_events[:, :, 0]`` (it needs ``t_events`` with at least one slot)."""
         B, n = self.n_instances, 5 * self.Depths.N
         D = np.array(D, dtype=np.float64)
         if D.shape != (B, 8, n):
@@ -620,11 +622,29 @@ class LMAHeureuxPorosityDiff:
         ``events=True``: the monitors' root times are located inside the sweep (marl_sweep_bdf_events_dev) and returned as
         ``t_events`` - a list of 7 arrays per instance, ``min(n_events[e], max_events)`` long, what the reference prints and stores
         for every run (Evolve_scenario.py:118-145, 175-177); otherwise (or with ``max_events`` = 0) sign changes are only counted and
-        ``t_events`` is None.  Combinable with ``t_eval``."""
+        ``t_events`` is None.  Combinable with ``t_eval``.
+
+        While a monitor is terminal (:meth:`set_terminal`) the sweep runs through marl_sweep_bdf_terminal_dev: an instance whose
+        terminal monitor occurs ends at that root on the device with ``status`` 1, ``t_reached`` = the root and the state there; the
+        results are built as above, with or without ``t_eval`` and ``events``."""
         grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
         stats = (MarlStats * self.n_instances)()
         args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
                 _as_ptr(grp) if grp is not None else None, int(max_attempts))
+        if any(self.terminal):
+            te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
+            if te.size and not y_eval_dev_ptr:
+                raise ValueError("sweep_bdf_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
+            n_done = np.zeros(self.n_instances, dtype=np.int64)
+            locate = bool(events) and int(max_events) > 0
+            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan) if locate else None
+            rc = self._lib.marl_sweep_bdf_terminal_dev(*args, _as_ptr(te) if te.size else None, te.size,
+                                                       C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
+                                                       _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
+            self._check(rc, "marl_sweep_bdf_terminal_dev")
+            return [RK45Result(s, t=te[:int(k)].copy() if t_eval is not None else None,
+                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
+                    for b, (s, k) in enumerate(zip(stats, n_done))]
         if bool(events) and int(max_events) > 0:
             te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
             if te.size and not y_eval_dev_ptr:

@@ -3373,9 +3373,23 @@ static int bdf_launch_change_D(marl_ctx* ctx, const RadauWork& w, int64_t n, uns
     return 0;
 }
 
-static int bdf_launch_roots(marl_ctx* ctx, const RadauWork& w, int64_t N, const bdfctl::BdfRoots* droots, double* dtev, unsigned cnt, const bdf::BdfBatch& zb)
+// dterm: the instances' terminal-monitor states in a sweep that has limits (listed instances with A_TERM_ROOTS search on theirs), else NULL
+static int bdf_launch_roots(marl_ctx* ctx, const RadauWork& w, int64_t N, const bdfctl::BdfRoots* droots, double* dtev, unsigned cnt, const bdf::BdfBatch& zb,
+                            bdfctl::BdfTerm* dterm = nullptr)
 {
-    hipLaunchKernelGGL(bdf::roots_batch_kernel, dim3(1, 1, cnt), dim3(radau::WG_THREADS), 0, ctx->stream, bdf_arena_of(w, NF * N).D, N, droots, dtev, ctx->dconsts, zb);
+    if (dterm)
+        hipLaunchKernelGGL(bdf::roots_batch_kernel<true>, dim3(1, 1, cnt), dim3(radau::WG_THREADS), 0, ctx->stream, bdf_arena_of(w, NF * N).D, N, droots, dtev, ctx->dconsts,
+                           zb, dterm);
+    else
+        hipLaunchKernelGGL(bdf::roots_batch_kernel<false>, dim3(1, 1, cnt), dim3(radau::WG_THREADS), 0, ctx->stream, bdf_arena_of(w, NF * N).D, N, droots, dtev, ctx->dconsts,
+                           zb, dterm);
+    LAUNCH_OK(ctx);
+    return 0;
+}
+
+static int bdf_launch_stop_state(marl_ctx* ctx, const RadauWork& w, int64_t N, const bdfctl::BdfTerm* dterm, unsigned cnt, const bdf::BdfBatch& zb)
+{
+    hipLaunchKernelGGL(bdf::stop_state_batch_kernel, dim3(1, 1, cnt), dim3(radau::WG_THREADS), 0, ctx->stream, bdf_arena_of(w, NF * N).D, N, dterm, w.y, ctx->dconsts, zb);
     LAUNCH_OK(ctx);
     return 0;
 }
@@ -3400,16 +3414,21 @@ static int bdf_launch_sample(marl_ctx* ctx, const RadauWork& w, int64_t n, const
 // samples (A_ROOTS: roots_batch_kernel runs the whole search of a step's monitors in one launch) into a NaN-filled device buffer that
 // comes back once at the end; NULL or max_events <= 0: sign changes are counted only, and neither the buffer nor the instances'
 // BdfRoots exist - the kernels and cycles are those of the sweep without roots.
+// terminal_ok: the entry honours ctx->terminal (marl_sweep_bdf_terminal_dev; the others refuse a context with limits).  With limits the
+// instances get a BdfTerm each, the controllers are the TERM instantiations, and a cycle's work reads
+//     A_ACCEPT  ->  A_CHANGE_D  ->  A_ROOTS / A_TERM_ROOTS  ->  A_SAMPLE  ->  A_STOP  ->  A_JAC  ->  A_LU  ->  A_SOLVE
+// (marl_bdf_ctl.h); a stopped instance is PC_DONE and leaves BL_RUNNING, so the sweep ends with its last live instance.  Without limits
+// nothing of this exists and the launches are those of the other entries.
 static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol, const int32_t* groups,
                      int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, double* t_events,
-                     int64_t max_events, marl_stats* stats)
+                     int64_t max_events, marl_stats* stats, bool terminal_ok = false)
 {
     if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_sweep_bdf_dev: invalid argument") : -1;
     if (n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done))) return fail(ctx, -1, "marl_sweep_bdf_eval_dev: invalid argument");
-    NO_TERMINAL(ctx, "marl_sweep_bdf_dev")
+    if (!terminal_ok) { NO_TERMINAL(ctx, "marl_sweep_bdf_dev") }
     if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_bdf_dev: whole-grid context required");
     if (int rc = check_ivp_args(ctx, "bdf", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
-    const bool frames = n_eval > 0, locate = t_events && max_events > 0;
+    const bool frames = n_eval > 0, locate = t_events && max_events > 0, term = has_terminal(ctx);
     if (ctx->batch > 65535) return fail(ctx, -1, "marl_sweep_bdf_dev: at most 65535 instances per call");
     const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
     if (n > radau::PCR_FUSED_MAX)
@@ -3431,9 +3450,11 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     for (auto& s : hsmp) bdfctl::bdf_sample_init(s, n_eval);
     std::vector<BdfRoots> hroots(locate ? (size_t)B : 0);
     for (auto& r : hroots) bdfctl::bdf_roots_init(r, max_events);
+    std::vector<bdfctl::BdfTerm> hterm(term ? (size_t)B : 0);
+    for (auto& m : hterm) bdfctl::bdf_term_init(m, ctx->terminal);
     const size_t tev_bytes = locate ? sizeof(double) * (size_t)B * 7 * (size_t)max_events : 0;
     DevBuf b_ctl(ctx->stream), b_rec(ctx->stream), b_counts(ctx->stream), b_smp(ctx->stream), b_teval(ctx->stream), b_roots(ctx->stream),
-        b_tev(ctx->stream);   // every return from here on frees them
+        b_tev(ctx->stream), b_term(ctx->stream);   // every return from here on frees them
     HIP_OK(ctx, b_ctl.alloc(sizeof(BdfCtl) * B));
     HIP_OK(ctx, b_rec.alloc(sizeof(double) * NQ * B));
     HIP_OK(ctx, b_counts.alloc(sizeof(int32_t) * (size_t)(radau::L_COUNT + BL_COUNT * B)));
@@ -3454,10 +3475,15 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         HIP_OK(ctx, hipMemcpyAsync(b_roots.p, hroots.data(), sizeof(BdfRoots) * B, hipMemcpyHostToDevice, ctx->stream));
         HIP_OK(ctx, hipMemsetAsync(b_tev.p, 0xFF, tev_bytes, ctx->stream));
     }
+    if (term) {   // the instances' terminal-monitor states
+        HIP_OK(ctx, b_term.alloc(sizeof(bdfctl::BdfTerm) * B));
+        HIP_OK(ctx, hipMemcpyAsync(b_term.p, hterm.data(), sizeof(bdfctl::BdfTerm) * B, hipMemcpyHostToDevice, ctx->stream));
+    }
     BdfSample* const dsmp = b_smp.as<BdfSample>();
     const double* const dteval = b_teval.as<double>();
     BdfRoots* const droots = b_roots.as<BdfRoots>();
     double* const dtev = b_tev.as<double>();
+    bdfctl::BdfTerm* const dterm = b_term.as<bdfctl::BdfTerm>();
     HIP_OK(ctx, hipMemcpy2DAsync(w.y, (size_t)zs, y_dev, n * sizeof(double), n * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_OK(ctx, hipMemsetAsync(dcounts, 0, sizeof(int32_t) * radau::L_COUNT, ctx->stream));   // (sweep_read_counts keeps them zero between cycles)
     bdf::Vec6 gamma = {};
@@ -3485,14 +3511,23 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
     int64_t stalled = 0;
     for (int64_t cycle = 0;; cycle++) {
         const dim3 gctl((unsigned)((B + 63) / 64)), bctl(64);
-        if (frames && locate) hipLaunchKernelGGL((bdf_control_kernel<true, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
-        else if (locate) hipLaunchKernelGGL((bdf_control_kernel<false, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
-        else if (frames) hipLaunchKernelGGL((bdf_control_kernel<true, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
-        else hipLaunchKernelGGL((bdf_control_kernel<false, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots);
+        double* const no_tev = nullptr;   // (the controllers without TERM store no root themselves)
+        bdfctl::BdfTerm* const no_term = nullptr;
+        if (term) {
+            if (frames && locate) hipLaunchKernelGGL((bdf_control_kernel<true, true, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, dterm, dtev);
+            else if (locate) hipLaunchKernelGGL((bdf_control_kernel<false, true, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, dterm, dtev);
+            else if (frames) hipLaunchKernelGGL((bdf_control_kernel<true, false, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, dterm, dtev);
+            else hipLaunchKernelGGL((bdf_control_kernel<false, false, true>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, dterm, dtev);
+        }
+        else if (frames && locate) hipLaunchKernelGGL((bdf_control_kernel<true, true, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, no_term, no_tev);
+        else if (locate) hipLaunchKernelGGL((bdf_control_kernel<false, true, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, no_term, no_tev);
+        else if (frames) hipLaunchKernelGGL((bdf_control_kernel<true, false, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, no_term, no_tev);
+        else hipLaunchKernelGGL((bdf_control_kernel<false, false, false>), gctl, bctl, 0, ctx->stream, dctl, drec, B, n, dcounts, dlists, dsmp, dteval, droots, no_term, no_tev);
         LAUNCH_OK(ctx);
         if (int rc = sweep_read_counts(ctx, dcounts, BL_COUNT, cycle, hcounts)) return rc;
         const unsigned nA = (unsigned)hcounts[BL_ACCEPT], nC = (unsigned)hcounts[BL_CHANGE_D], nJ = (unsigned)hcounts[BL_JAC], nL = (unsigned)hcounts[BL_LU],
-                       nS = (unsigned)hcounts[BL_SOLVE], nP = (unsigned)hcounts[BL_SAMPLE], nR = locate ? (unsigned)hcounts[BL_ROOTS] : 0u;
+                       nS = (unsigned)hcounts[BL_SOLVE], nP = (unsigned)hcounts[BL_SAMPLE], nR = (locate || term) ? (unsigned)hcounts[BL_ROOTS] : 0u,
+                       nT = term ? (unsigned)hcounts[BL_STOP] : 0u;
         stalled = hcounts[BL_PROGRESS] ? 0 : stalled + 1;
         if (stalled >= kStallCycles)
             return fail(ctx, -3, "marl_sweep_bdf_dev: no instance moved for %lld cycles (%d still running)", (long long)kStallCycles, (int)hcounts[BL_RUNNING]);
@@ -3501,9 +3536,11 @@ static int sweep_bdf(marl_ctx* ctx, double* y_dev, double t0, double t1, double 
         if (nC)
             if (int rc = bdf_launch_change_D(ctx, w, n, nC, L(BL_CHANGE_D))) return rc;
         if (nR)   // root times of the step just accepted: the same D as the samples below, events first (ivp.py:673-723)
-            if (int rc = bdf_launch_roots(ctx, w, N, droots, dtev, nR, L(BL_ROOTS))) return rc;
+            if (int rc = bdf_launch_roots(ctx, w, N, droots, dtev, nR, L(BL_ROOTS), dterm)) return rc;   // (with limits: a terminal step's roots too)
         if (nP)   // t_eval samples of the step just accepted: D after the selection's rescaling, before the next step's
             if (int rc = bdf_launch_sample(ctx, w, n, dteval, n_eval, dsmp, y_eval_dev, nP, L(BL_SAMPLE))) return rc;
+        if (nT)   // a terminal monitor ended these runs inside the step just accepted: the dense output at t_stop is their state
+            if (int rc = bdf_launch_stop_state(ctx, w, N, dterm, nT, L(BL_STOP))) return rc;
         if (nJ) {   // J = jac(t_new, y_predict), with f = fun(t_new, y_predict) (not counted)
             if (int rc = launch_rhs_fm(ctx, ypred, w.fnew, 1, nJ, Z(BL_JAC))) return rc;
             if (int rc = radau_num_jac(ctx, w, ypred, w.fnew, atol, 0, nJ, Z(BL_JAC))) return rc;
@@ -3573,6 +3610,13 @@ extern "C" int marl_sweep_bdf_events_dev(marl_ctx* ctx, double* y_dev, double t0
     return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats);
 }
 
+extern "C" int marl_sweep_bdf_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                           const int32_t* groups, int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                           int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_bdf(ctx, y_dev, t0, t1, first_step, rtol, atol, groups, max_attempts, t_eval, n_eval, y_eval_dev, n_done, t_events, max_events, stats, true);
+}
+
 // ---- test hook of the BDF sweep's vector kernels: ONE launch (tests/test_gpu_bdf_batch_parts.py) ------------------------------------
 // The sweep's arena (radau_alloc with the context's instances: the real stride), each instance's BdfCtl / BdfSample / BdfRoots built
 // here from plain scalars, one launch through the launcher sweep_bdf calls, and everything the kernel may write - with its
@@ -3583,7 +3627,7 @@ extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, 
 {
     using namespace bdf;
     if (!ctx || !iargs || !dargs || !D_in || !vec_in || !D_out || !y_out || !ss) return ctx ? fail(ctx, -1, "marl_debug_bdf_batch: invalid argument") : -1;
-    if (op < MARL_BDF_INIT_D || op > MARL_BDF_ROOTS) return fail(ctx, -1, "marl_debug_bdf_batch: unknown op %d", op);
+    if (op < MARL_BDF_INIT_D || op > MARL_BDF_STOP) return fail(ctx, -1, "marl_debug_bdf_batch: unknown op %d", op);
     if (ctx->halo > 0) return fail(ctx, -1, "marl_debug_bdf_batch: whole-grid context required");
     if (ctx->batch > 65535) return fail(ctx, -1, "marl_debug_bdf_batch: at most 65535 instances per call");
     const int64_t N = ctx->N, n = NF * N, B = ctx->batch;
@@ -3594,9 +3638,11 @@ extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, 
     if (n_eval < 0 || (n_eval > 0 && (!t_eval || !frames))) return fail(ctx, -1, "marl_debug_bdf_batch: n_eval samples need t_eval and frames");
     if (max_events < 0 || (max_events > 0 && !t_events)) return fail(ctx, -1, "marl_debug_bdf_batch: max_events root slots need t_events");
     if (op == MARL_BDF_ROOTS && max_events <= 0) return fail(ctx, -1, "marl_debug_bdf_batch: ROOTS needs max_events > 0");
+    if (op == MARL_BDF_STOP && max_events <= 0) return fail(ctx, -1, "marl_debug_bdf_batch: STOP needs max_events > 0 (the monitors come back in slot 0)");
     std::vector<BdfCtl> hctl((size_t)B);   // (before the device buffers, as in sweep_bdf)
     std::vector<BdfSample> hsmp((size_t)B);
     std::vector<BdfRoots> hroots((size_t)B);
+    std::vector<BdfTerm> hterm((size_t)B);
     for (int64_t b = 0; b < B; b++) {
         const int64_t* ia = iargs + b * MARL_BDF_DEBUG_INTS;
         const double* da = dargs + b * MARL_BDF_DEBUG_DOUBLES;
@@ -3619,6 +3665,9 @@ extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, 
         BdfRoots& r = hroots[(size_t)b];
         bdfctl::bdf_roots_init(r, max_events);
         r.t_old = da[6]; r.t = da[5]; r.h = da[0]; r.order = (int32_t)order; r.mask = (int32_t)mask;
+        BdfTerm& m = hterm[(size_t)b];   // STOP: the terminal step's snapshot; da[6] is t_stop
+        bdfctl::bdf_term_init(m, ctx->terminal);
+        m.t = da[5]; m.h = da[0]; m.order = (int32_t)order; m.t_stop = da[6];
         for (int e = 0; e < 7; e++) {
             r.slot[e] = ia[5 + e];
             if (op == MARL_BDF_ROOTS && ((mask >> e) & 1) && (r.slot[e] < 0 || r.slot[e] >= max_events))
@@ -3630,13 +3679,18 @@ extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, 
     int64_t zs = 0;
     if (int rc = radau_alloc(ctx, w, nullptr, B, &zs)) return rc;
     const size_t nb = (size_t)n * sizeof(double), fr_bytes = (size_t)B * (size_t)n_eval * nb, tev_bytes = sizeof(double) * (size_t)B * 7 * (size_t)max_events;
-    DevBuf b_ctl(ctx->stream), b_smp(ctx->stream), b_roots(ctx->stream), b_list(ctx->stream), b_teval(ctx->stream), b_fr(ctx->stream), b_tev(ctx->stream);
+    DevBuf b_ctl(ctx->stream), b_smp(ctx->stream), b_roots(ctx->stream), b_list(ctx->stream), b_teval(ctx->stream), b_fr(ctx->stream), b_tev(ctx->stream),
+        b_term(ctx->stream);
     HIP_OK(ctx, b_ctl.alloc(sizeof(BdfCtl) * B));
     HIP_OK(ctx, b_smp.alloc(sizeof(BdfSample) * B));
     HIP_OK(ctx, b_roots.alloc(sizeof(BdfRoots) * B));
     HIP_OK(ctx, hipMemcpyAsync(b_ctl.p, hctl.data(), sizeof(BdfCtl) * B, hipMemcpyHostToDevice, ctx->stream));
     HIP_OK(ctx, hipMemcpyAsync(b_smp.p, hsmp.data(), sizeof(BdfSample) * B, hipMemcpyHostToDevice, ctx->stream));
     HIP_OK(ctx, hipMemcpyAsync(b_roots.p, hroots.data(), sizeof(BdfRoots) * B, hipMemcpyHostToDevice, ctx->stream));
+    if (op == MARL_BDF_STOP) {
+        HIP_OK(ctx, b_term.alloc(sizeof(BdfTerm) * B));
+        HIP_OK(ctx, hipMemcpyAsync(b_term.p, hterm.data(), sizeof(BdfTerm) * B, hipMemcpyHostToDevice, ctx->stream));
+    }
     if (list) {
         HIP_OK(ctx, b_list.alloc(sizeof(int32_t) * (size_t)n_list));
         HIP_OK(ctx, hipMemcpyAsync(b_list.p, list, sizeof(int32_t) * (size_t)n_list, hipMemcpyHostToDevice, ctx->stream));
@@ -3668,7 +3722,8 @@ extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, 
     else if (op == MARL_BDF_CHANGE_D) rc = bdf_launch_change_D(ctx, w, n, cnt, zb);
     else if (op == MARL_BDF_ACCEPT_NORMS) rc = bdf_launch_accept_norms(ctx, w, n, cnt, zb);
     else if (op == MARL_BDF_SAMPLE) rc = bdf_launch_sample(ctx, w, n, b_teval.as<double>(), n_eval, b_smp.as<BdfSample>(), b_fr.as<double>(), cnt, zb);
-    else rc = bdf_launch_roots(ctx, w, N, b_roots.as<BdfRoots>(), b_tev.as<double>(), cnt, zb);
+    else if (op == MARL_BDF_ROOTS) rc = bdf_launch_roots(ctx, w, N, b_roots.as<BdfRoots>(), b_tev.as<double>(), cnt, zb);
+    else rc = bdf_launch_stop_state(ctx, w, N, b_term.as<BdfTerm>(), cnt, zb);
     if (rc) return rc;
     for (int64_t b = 0; b < B; b++) {
         HIP_OK(ctx, hipMemcpyAsync(D_out + b * 8 * n, at(a.D, b), 8 * nb, hipMemcpyDeviceToHost, ctx->stream));
@@ -3679,6 +3734,11 @@ extern "C" int marl_debug_bdf_batch(marl_ctx* ctx, int op, const int32_t* list, 
     if (max_events > 0) HIP_OK(ctx, hipMemcpyAsync(t_events, b_tev.p, tev_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < B; b++) { ss[2 * b] = hctl[(size_t)b].ss_m; ss[2 * b + 1] = hctl[(size_t)b].ss_p; }
+    if (op == MARL_BDF_STOP)   // the monitors of the listed instances' stop states (ctl.g; the kernel has no root slot to write)
+        for (int64_t k = 0; k < (list ? n_list : B); k++) {
+            const int64_t b = list ? list[k] : k;
+            for (int e = 0; e < 7; e++) t_events[(b * 7 + e) * max_events] = hctl[(size_t)b].g[e];
+        }
     return 0;
 }
 

@@ -21,9 +21,11 @@ namespace bdf {
 using bdfctl::BdfCtl;
 using bdfctl::BdfRoots;
 using bdfctl::BdfSample;
+using bdfctl::BdfTerm;
 
 // work lists of a cycle; the count words are published by radau::publish_counts_kernel (L_COUNT words, then the sequence word)
-enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_SAMPLE, BL_ROOTS, BL_RUNNING, BL_PROGRESS, BL_COUNT };
+// (BL_ROOTS holds the instances of A_ROOTS and of A_TERM_ROOTS - a step is one or the other - so that the words still fit L_COUNT)
+enum : int { BL_ACCEPT = 0, BL_CHANGE_D, BL_JAC, BL_LU, BL_SOLVE, BL_SAMPLE, BL_ROOTS, BL_RUNNING, BL_PROGRESS, BL_STOP, BL_COUNT };
 static_assert(BL_COUNT <= radau::L_COUNT, "publish_counts_kernel copies L_COUNT words");
 
 // blockIdx.z -> instance (list == NULL: every instance, in order), its arena and its controller
@@ -40,11 +42,15 @@ __device__ __forceinline__ ZBatch z_of(const BdfBatch& B) { return ZBatch{B.zstr
 // the step logic is compiled as the three-argument call: a sweep without samples runs the code it ran before there were any.
 // ROOTS: the sweep locates the monitors' root times - roots: the instances' root-location states (A_ROOTS -> BL_ROOTS); without
 // them the step logic is compiled as the call without a BdfRoots.
-template <bool SAMPLES, bool ROOTS>
+// TERM: the context has terminal monitors - terms: the instances' terminal-monitor states, t_events: the [B][7][max_events] root
+// times the controller stores a terminal step's kept roots into (ROOTS only).  A_TERM_ROOTS -> BL_ROOTS, A_STOP -> BL_STOP.  A sweep
+// without limits launches the instantiations without TERM: the code it ran before there were any.
+template <bool SAMPLES, bool ROOTS, bool TERM = false>
 __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ctls, const double* __restrict__ rec, int64_t B, int64_t n,
                                                          int32_t* __restrict__ counts, int32_t* __restrict__ lists,
                                                          BdfSample* __restrict__ samples, const double* __restrict__ t_eval,
-                                                         BdfRoots* __restrict__ roots)
+                                                         BdfRoots* __restrict__ roots, BdfTerm* __restrict__ terms = nullptr,
+                                                         double* __restrict__ t_events = nullptr)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
@@ -54,7 +60,10 @@ __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ct
     const double g0[7] = {r[1], r[2], r[3], r[5] - 1.0, r[6] - 1.0, r[4], r[7]};   // record_to_events (marl_api.hip)
     const int32_t pc0 = c.pc, status0 = c.status;
     const int64_t attempts0 = c.attempts;
-    if constexpr (ROOTS) bdfctl::bdf_control_step(c, n, g0, SAMPLES ? samples + b : nullptr, SAMPLES ? t_eval : nullptr, roots + b);
+    if constexpr (TERM)
+        bdfctl::bdf_control_step(c, n, g0, SAMPLES ? samples + b : nullptr, SAMPLES ? t_eval : nullptr, ROOTS ? roots + b : nullptr, terms + b,
+                                 ROOTS ? t_events + b * 7 * roots[ROOTS ? b : 0].max_events : nullptr);
+    else if constexpr (ROOTS) bdfctl::bdf_control_step(c, n, g0, SAMPLES ? samples + b : nullptr, SAMPLES ? t_eval : nullptr, roots + b);
     else if constexpr (SAMPLES) bdfctl::bdf_control_step(c, n, g0, samples + b, t_eval);
     else bdfctl::bdf_control_step(c, n, g0);
     ctls[b] = c;
@@ -70,6 +79,10 @@ __global__ void __launch_bounds__(64) bdf_control_kernel(BdfCtl* __restrict__ ct
         if (c.action & bdfctl::A_SAMPLE) push(BL_SAMPLE);
     if constexpr (ROOTS)
         if (c.action & bdfctl::A_ROOTS) push(BL_ROOTS);
+    if constexpr (TERM) {
+        if (c.action & bdfctl::A_TERM_ROOTS) push(BL_ROOTS);
+        if (c.action & bdfctl::A_STOP) push(BL_STOP);
+    }
 }
 
 // D[0] = y0, D[1] = f h  (init_D_kernel; h = the controller's first step)
@@ -147,20 +160,16 @@ __global__ void __launch_bounds__(256) sample_batch_kernel(const double* __restr
 //     (wg_monitors / monitors_kernel)  ->  block_reduce in LDS  ->  the seven monitors, read back from LDS by every thread
 // with no global memory touched.  Control flow is uniform: every thread runs the scalar search (bdfctl::bdf_find_roots) redundantly
 // on the reduced monitors all threads read after the barrier, so every thread reaches every barrier; the loops are bounded
-// (<= 7 monitors x (2 + <= 100) evaluations).  Thread 0 stores the roots: t_events [instances][7][max_events] (device).
-__global__ void __launch_bounds__(radau::WG_THREADS) roots_batch_kernel(const double* __restrict__ D, int64_t N, const BdfRoots* __restrict__ roots,
-                                                                         double* __restrict__ t_events, const DevConsts* __restrict__ consts, BdfBatch B)
+// (<= 7 monitors x (2 + <= 100) evaluations).
+// The body, shared by the two searches: src = the instance's BdfRoots (A_ROOTS) or BdfTerm (A_TERM_ROOTS) - the step (order, t, h,
+// t_old) and the monitors to search - read where it is (a private copy would sit in scratch memory); put(e, root): once per monitor
+// searched, in every thread.  red / tabs / g_sh: the kernel's LDS.
+template <class Src, class Put>
+__device__ __forceinline__ void roots_wg_body(const double* __restrict__ D, int64_t N, const Src& r, const DevConsts& C, double* red, double* tabs, double* g_sh,
+                                              Put&& put)
 {
     using namespace radau;
-    __shared__ double red[NQ * WG_THREADS];
-    __shared__ double tabs[TABLE_DOUBLES];
-    __shared__ double g_sh[7];
     const Tables T = load_tables(tabs, WG_THREADS);
-    const ZBatch zb = z_of(B);
-    const int64_t inst = z_inst(zb);
-    const BdfRoots& r = roots[inst];   // (read where it is: a private copy would sit in scratch memory for slot[e])
-    const DevConsts& C = consts[inst];
-    D = z_shift(D, zb);
     const int64_t n = NF * N, l = threadIdx.x;
     const bool mine = l < N;
     const int order = r.order;
@@ -201,10 +210,91 @@ __global__ void __launch_bounds__(radau::WG_THREADS) roots_batch_kernel(const do
         __syncthreads();   // (g_sh is free for the next evaluation)
         return ge;
     };
+    bdfctl::bdf_find_roots(r, eval, put);
+}
+
+// Thread 0 stores the roots: t_events [instances][7][max_events] (device).
+// TERM (a sweep with terminal monitors): a listed instance whose action word has A_TERM_ROOTS is searched on its BdfTerm (t_old, t, h,
+// order, active) and leaves the roots in BdfTerm::root[] - the same body; its BdfRoots is not read (there is none in a sweep without
+// root slots).  Which of the two an instance is is uniform over its workgroup.  Without TERM the kernel is the body on BdfRoots alone.
+template <bool TERM>
+__global__ void __launch_bounds__(radau::WG_THREADS) roots_batch_kernel(const double* __restrict__ D, int64_t N, const BdfRoots* __restrict__ roots,
+                                                                         double* __restrict__ t_events, const DevConsts* __restrict__ consts, BdfBatch B,
+                                                                         BdfTerm* __restrict__ terms)
+{
+    using namespace radau;
+    __shared__ double red[NQ * WG_THREADS];
+    __shared__ double tabs[TABLE_DOUBLES];
+    __shared__ double g_sh[7];
+    const ZBatch zb = z_of(B);
+    const int64_t inst = z_inst(zb);
+    D = z_shift(D, zb);
+    if constexpr (TERM)
+        if (B.ctls[inst].action & bdfctl::A_TERM_ROOTS) {   // (uniform)
+            BdfTerm& m = terms[inst];
+            roots_wg_body(D, N, m, consts[inst], red, tabs, g_sh, [&](int e, double root) {
+                if (threadIdx.x == 0) m.root[e] = root;
+            });
+            return;
+        }
+    const BdfRoots& r = roots[inst];
     double* out = t_events + inst * 7 * r.max_events;
-    bdfctl::bdf_find_roots(r, eval, [&](int e, double root) {
+    roots_wg_body(D, N, r, consts[inst], red, tabs, g_sh, [&](int e, double root) {
         if (threadIdx.x == 0) out[e * r.max_events + r.slot[e]] = root;
     });
+}
+
+// A_STOP, one workgroup per listed instance: the run ended at t_stop inside the step just accepted (a terminal monitor's root) - the
+// state there, y = the step's dense output at t_stop (field-major in the instance's arena), and that state's monitors -> ctl.g.
+// Thread l < N forms the five fields of cell l with the sum sample_batch_kernel writes a frame with - the same source expression,
+// so that the state returned IS the frame at t_eval = t_stop, bit for bit (that kernel's comment says why each keeps its own copy) -
+// then the cell's monitor terms as roots_batch_kernel's evaluation forms them, block_reduce, and thread 0 stores the seven
+// monitors.  Every thread reaches every barrier; nothing waits for another workgroup; only D is read, only y and ctl.g written.
+__global__ void __launch_bounds__(radau::WG_THREADS) stop_state_batch_kernel(const double* __restrict__ D, int64_t N, const BdfTerm* __restrict__ terms,
+                                                                              double* __restrict__ y, const DevConsts* __restrict__ consts, BdfBatch B)
+{
+    using namespace radau;
+    __shared__ double red[NQ * WG_THREADS];
+    __shared__ double tabs[TABLE_DOUBLES];
+    const Tables T = load_tables(tabs, WG_THREADS);
+    const ZBatch zb = z_of(B);
+    const int64_t inst = z_inst(zb);
+    const BdfTerm& m = terms[inst];
+    const DevConsts& C = consts[inst];
+    D = z_shift(D, zb); y = z_shift(y, zb);
+    const int64_t n = NF * N, l = threadIdx.x;
+    const bool mine = l < N;
+    const int order = m.order;
+    double p[MAX_ORDER + 1];
+    bdfctl::bdf_dense_weights(m.t, m.h, order, m.t_stop, p);
+    const double rhorat = C.hot.rhorat, presum = C.hot.presum;
+    double q[NQ];
+    monitors_init(q);
+    if (mine) {
+        double u[NF];
+#pragma unroll
+        for (int f = 0; f < NF; f++) {
+            double d[MAX_ORDER + 1];
+#pragma unroll
+            for (int j = 0; j <= MAX_ORDER; j++) d[j] = j <= order ? D[(int64_t)j * n + f * N + l] : 0.0;
+            double a = 0;
+#pragma unroll
+            for (int j = 0; j < MAX_ORDER; j++)
+                if (j < order) a += d[j + 1] * p[j];
+            u[f] = a + d[0];
+            y[f * N + l] = u[f];
+        }
+        const double Phi = u[4];
+        const double F = 1.0 - fast_exp(10.0 - 10.0 * rcp_nr(Phi), T);
+        const double rF = rhorat * F;
+        monitors_accumulate(q, u, presum + rF * (Phi * Phi * Phi) * rcp_nr(1.0 - Phi), presum - rF * Phi * Phi);
+    }
+    block_reduce<WG_THREADS, NQ, NQMIN>(q, red);   // (begins and ends with a barrier; the result is thread 0's)
+    if (threadIdx.x == 0) {
+        const double gq[7] = {q[1], q[2], q[3], q[5] - 1.0, q[6] - 1.0, q[4], q[7]};   // record_to_events (marl_api.hip)
+        BdfCtl* c = B.ctls + inst;
+        for (int e = 0; e < 7; e++) c->g[e] = gq[e];
+    }
 }
 
 // A_ACCEPT, one workgroup per instance: the accepted step's update of the differences and y = y_new (accept_kernel), then the norms

@@ -28,14 +28,30 @@
 // (events before t_eval, as in scipy; both only read D).  The last step's roots go out in the cycle that reaches PC_DONE, a run that
 // ends with status -1 or 2 keeps the roots it has, t1 == t0 has none.  Without a BdfRoots, or with max_events <= 0, the action words,
 // the cycles and the controller's bytes are those of the calls without it; n_events counts every sign change either way.
+//
+// Terminal monitors (BdfTerm, a fourth per-instance struct; A_TERM_ROOTS, A_STOP; the rule: marl_terminal.h, ivp.py:79-130, 681-723).
+// At acceptance (PC_SOLVED) a step over which a monitor changed sign that thereby meets its limit is a TERMINAL STEP: all monitors that
+// changed sign are recorded in BdfTerm::active, the step's start is kept, and none of the step's sign changes is counted or marked for
+// A_ROOTS yet - which of them happened is known only once their roots are.  At PC_STEP_END such a step snapshots its dense output
+// where A_ROOTS and A_SAMPLE do, sets A_TERM_ROOTS - the roots of every monitor of `active` -> BdfTerm::root[], with or without root
+// slots - and yields:
+//     A_ACCEPT  ->  A_CHANGE_D  ->  A_TERM_ROOTS
+// The next cycle (PC_TERM) runs terminal_select on those roots: the monitors it keeps are counted and, where a BdfRoots has a free
+// slot, their roots stored into t_events by the controller itself; the ones after the terminal monitor never happened.  Then
+// c.t = t_stop, A_SAMPLE for the samples t_eval[k] <= t_stop (BdfSample::t stays the STEP's end: it is the dense output's t), A_STOP -
+// y = the dense output at t_stop, sample_batch_kernel's sum, and c.g = that state's monitors - status 1 and PC_DONE, all in that cycle:
+//     A_SAMPLE  ->  A_STOP
+// (both only read D; nothing rescales it any more).  One extra cycle per stopped instance.  Every other step, a run that ends with
+// status -1 or 2, and t1 == t0 are untouched; without a BdfTerm the action words, cycles and bytes are those of the calls without it.
 // f(t0, y0), the first Jacobian, D[0] = y0, D[1] = f h and the monitors of y0 (BDF.__init__) are done before the first cycle.
-// Like marl_brent.h: nothing but <math.h> / <stdint.h> (and marl_brent.h), so that a host C++ compiler builds this header alone
+// Like marl_brent.h: nothing but <math.h> / <stdint.h> (and marl_brent.h, marl_terminal.h), so that a host C++ compiler builds this header alone
 // (tests/test_bdf_control_cpu.py holds it to scipy's solve_ivp(method="BDF") that way).
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "marl_brent.h"
+#include "marl_terminal.h"
 
 #ifdef __HIPCC__
 #define MARL_BDF_FN __host__ __device__ __forceinline__
@@ -49,8 +65,8 @@ namespace bdfctl {
 constexpr int MAX_ORDER = 5, NEWTON_MAXITER = 4;
 constexpr double MIN_FACTOR = 0.2, MAX_FACTOR = 10;
 
-enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16, A_SAMPLE = 32, A_ROOTS = 64 };
-enum : int32_t { PC_INIT = 0, PC_STEP, PC_ATTEMPT, PC_SOLVED, PC_SELECT, PC_STEP_END, PC_DONE };
+enum : int32_t { A_ACCEPT = 1, A_CHANGE_D = 2, A_JAC = 4, A_LU = 8, A_SOLVE = 16, A_SAMPLE = 32, A_ROOTS = 64, A_TERM_ROOTS = 128, A_STOP = 256 };
+enum : int32_t { PC_INIT = 0, PC_STEP, PC_ATTEMPT, PC_SOLVED, PC_SELECT, PC_STEP_END, PC_DONE, PC_TERM };
 
 struct BdfCtl {
     // set once
@@ -98,6 +114,18 @@ struct BdfRoots {
     int32_t pending;                   // bit e: monitor e changed sign over the accepted step (set at acceptance, taken at PC_STEP_END)
     int32_t mask, pad;                 // bit e: monitor e is searched in this cycle
     int64_t slot[7];                   // monitor e's root goes to t_events[e * max_events + slot[e]]: its count before this sign change
+};
+
+// The terminal-monitor state of one instance: a fourth parallel array (BdfCtl, BdfSample and BdfRoots keep their layouts).
+struct BdfTerm {
+    int64_t terminal[7];               // monitor e ends the run at its terminal[e]-th occurrence (0: never)
+    double root[7];                    // A_TERM_ROOTS: the root of every monitor of `active` over the terminal step
+    // the dense output of the terminal step (BdfDenseOutput's t_old, t, h, order)
+    double t_old, t, h;                // the step's start (kept at acceptance), its end and S_h_abs after the selection
+    double t_stop;                     // the terminal monitor's root: where the run ended
+    int32_t order;
+    int32_t active;                    // bit e: monitor e changed sign over the terminal step (0: no terminal step so far)
+    int32_t stopped, pad;              // 1: the run was stopped at t_stop
 };
 
 MARL_BDF_FN double kappa_of(int k) { return k == 1 ? -0.1850 : k == 2 ? -1.0 / 9 : k == 3 ? -0.0823 : k == 4 ? -0.0415 : 0.0; }
@@ -180,25 +208,34 @@ MARL_BDF_FN void bdf_roots_init(BdfRoots& r, int64_t max_events)
     r.max_events = max_events;
 }
 
+MARL_BDF_FN void bdf_term_init(BdfTerm& m, const int64_t terminal[7])
+{
+    m = BdfTerm{};
+    for (int e = 0; e < 7; e++) m.terminal[e] = terminal[e];
+}
+
 // A_ROOTS, the search itself (solve_event_equation, ivp.py:51-76, as accepted_step_epilogue in marl_api.hip runs it for a single run):
-// for every monitor of r.mask in ascending e, a search of its own - both end values from the dense output (not the stored g), then the
+// for every monitor of the search's mask in ascending e over its [t_old, t] - `src` says where the three come from: a BdfRoots (A_ROOTS:
+// mask) or a BdfTerm (A_TERM_ROOTS: active), read where it lies each time (on the device that is global memory, not registers) - a search of its own - both end values from the dense output (not the stored g), then the
 // exact sequence of brent_root: an end point whose value is zero as it is, otherwise brent_advance / evaluate for at most 100 passes and
 // the last iterate.  Equal signs at both ends are no special case (the loop is bounded).  eval(tq, e): monitor e of the step's
 // dense output at tq.  put(e, root): called once for every monitor searched.
 // On the device every thread of a workgroup runs this redundantly on the same values (eval holds the barriers): the control flow
-// depends on nothing but r and what eval returns.
-template <class Eval, class Put>
-MARL_BDF_FN void bdf_find_roots(const BdfRoots& r, Eval&& eval, Put&& put)
+// depends on nothing but src and what eval returns.
+MARL_BDF_FN int32_t search_mask(const BdfRoots& r) { return r.mask; }
+MARL_BDF_FN int32_t search_mask(const BdfTerm& m) { return m.active; }
+template <class Src, class Eval, class Put>
+MARL_BDF_FN void bdf_find_roots(const Src& src, Eval&& eval, Put&& put)
 {
 #if defined(__clang__)
 #pragma clang loop unroll(disable)
 #endif
     for (int e = 0; e < 7; e++) {
-        if (!((r.mask >> e) & 1)) continue;
-        const double fa = eval(r.t_old, e), fb = eval(r.t, e);
-        if (fa == 0) { put(e, r.t_old); continue; }
-        if (fb == 0) { put(e, r.t); continue; }
-        BrentState s = {r.t_old, r.t, 0, fa, fb, 0, 0, 0};
+        if (!((search_mask(src) >> e) & 1)) continue;
+        const double fa = eval(src.t_old, e), fb = eval(src.t, e);
+        if (fa == 0) { put(e, src.t_old); continue; }
+        if (fb == 0) { put(e, src.t); continue; }
+        BrentState s = {src.t_old, src.t, 0, fa, fb, 0, 0, 0};
         for (int it = 0; it < 100; it++) {
             if (brent_advance(s)) break;
             s.fcur = eval(s.xcur, e);
@@ -214,10 +251,20 @@ MARL_BDF_FN void bdf_locate_roots(const BdfRoots& r, Eval&& eval, double* t_even
     bdf_find_roots(r, eval, [&](int e, double root) { t_events[e * r.max_events + r.slot[e]] = root; });
 }
 
+// A_TERM_ROOTS: the roots of every monitor that changed sign over the terminal step -> m.root[]
+template <class Eval>
+MARL_BDF_FN void bdf_locate_term_roots(BdfTerm& m, Eval&& eval)
+{
+    bdf_find_roots(m, eval, [&](int e, double root) { m.root[e] = root; });
+}
+
 // One instance from where it stopped to its next action word.  n: unknowns (5 N).  g0: the seven monitors of y0 (read at PC_INIT only).
 // s, t_eval: the instance's sampling state and the n_eval sorted sample times (NULL: no samples).
 // r: the instance's root-location state (NULL, or max_events <= 0: sign changes are counted only).
-MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSample* s = nullptr, const double* t_eval = nullptr, BdfRoots* r = nullptr)
+// m: the instance's terminal-monitor state (NULL: no monitor ends the run); t_events: the instance's [7][max_events] root times, where
+// the controller stores the kept roots of the terminal step (NULL, or no r: they are counted only).
+MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSample* s = nullptr, const double* t_eval = nullptr, BdfRoots* r = nullptr,
+                                  BdfTerm* m = nullptr, double* t_events = nullptr)
 {
     c.action = 0;
     int pc = c.pc;
@@ -306,9 +353,21 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSam
             c.t = c.t_new;
             c.S_h_abs = c.h_abs;
             c.n_acc++;
+            bool term = false;                    // a terminal step (ivp.py:681-704): its sign changes are counted at PC_TERM, once their roots say which happened
+            if (m) {
+                int32_t active = 0;
+                for (int e = 0; e < 7; e++) {
+                    const bool up = c.g[e] <= 0 && c.g_new[e] >= 0, down = c.g[e] >= 0 && c.g_new[e] <= 0;
+                    if (up || down) {
+                        active |= 1 << e;
+                        if (terminal_met(c.n_events[e] + 1, m->terminal[e])) term = true;
+                    }
+                }
+                if (term) { m->active = active; m->t_old = t_old; }
+            }
             for (int e = 0; e < 7; e++) {         // non-terminal events, both directions (ivp.py:131-156): counted; located at PC_STEP_END (r)
                 const bool up = c.g[e] <= 0 && c.g_new[e] >= 0, down = c.g[e] >= 0 && c.g_new[e] <= 0;
-                if (up || down) {
+                if ((up || down) && !term) {
                     if (r && c.n_events[e] < r->max_events) {   // (max_events <= 0: never)
                         r->pending |= 1 << e;
                         r->slot[e] = c.n_events[e];
@@ -350,6 +409,12 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSam
             continue;
         }
         if (pc == PC_STEP_END) {                  // the solve_ivp loop (ivp.py:667-668)
+            if (m && m->active) {                 // a terminal step: its dense output, as A_ROOTS and A_SAMPLE below snapshot it
+                m->t = c.t; m->h = c.S_h_abs; m->order = c.order;
+                c.action |= A_TERM_ROOTS;
+                pc = PC_TERM;
+                break;
+            }
             bool sampled = false;                 // (or searched for roots: the cycle ends here either way)
             if (r && r->pending) {                // ivp.py:673-694: the roots of this step, on the dense output the samples below read
                 r->mask = r->pending;
@@ -371,6 +436,32 @@ MARL_BDF_FN void bdf_control_step(BdfCtl& c, int64_t n, const double* g0, BdfSam
             pc = PC_STEP;
             if (sampled) break;                   // the next step may rescale D: not in the cycle that reads it
             continue;
+        }
+        if (pc == PC_TERM) {                      // the roots of the terminal step are in m->root: handle_events (ivp.py:79-130, 696-704)
+            int64_t counts[7];
+            for (int e = 0; e < 7; e++) counts[e] = c.n_events[e] + 1;
+            uint32_t keep = 0;
+            double t_stop = m->t;
+            terminal_select((uint32_t)m->active, m->root, counts, m->terminal, &keep, &t_stop);
+            for (int e = 0; e < 7; e++) {
+                if (!((keep >> e) & 1)) continue;
+                if (r && t_events && c.n_events[e] < r->max_events) t_events[e * r->max_events + c.n_events[e]] = m->root[e];
+                c.n_events[e]++;
+            }
+            m->t_stop = t_stop;
+            m->stopped = 1;
+            c.t = t_stop;
+            if (s && s->next < s->n_eval && t_eval[s->next] <= t_stop) {   // the samples up to t_stop, from the terminal step's dense output
+                s->t = m->t; s->h = m->h; s->order = m->order;
+                s->first = s->next;
+                int64_t e = s->next + 1;
+                while (e < s->n_eval && t_eval[e] <= t_stop) e++;
+                s->end = s->next = e;
+                c.action |= A_SAMPLE;
+            }
+            c.action |= A_STOP;
+            c.status = 1; pc = PC_DONE;
+            break;
         }
         break;
     }

@@ -1,8 +1,8 @@
 // Terminal monitors, the only statement of the rule in the project: scipy's handle_events (scipy/integrate/_ivp/ivp.py:79-130) for the
 // seven monitors of one accepted step of a forward integration.  A monitor e with terminal[e] = k > 0 stops the run at its k-th
 // occurrence (scipy >= 1.13: event.terminal may be an int; True is 1); terminal[e] = 0: it never does.  Called by the Radau sweeps'
-// device-side controller (radau_control_step, marl_radau_batch.h) and by the host's accepted_step_epilogue of the implicit single runs
-// (marl_api.hip).  Nothing but <stdint.h> and <math.h>: a host C++ compiler builds this header alone (tests/test_terminal_select_cpu.py
+// device-side controller (radau_control_step, marl_radau_batch.h), by the BDF sweep's (bdf_control_step, marl_bdf_ctl.h) and by the
+// host's accepted_step_epilogue of the implicit single runs (marl_api.hip).  Nothing but <stdint.h> and <math.h>: a host C++ compiler builds this header alone (tests/test_terminal_select_cpu.py
 // holds it to scipy's own handle_events that way); under hipcc it follows <hip/hip_runtime.h>, which defines __forceinline__.
 #pragma once
 #include <math.h>

@@ -132,7 +132,7 @@ class HipSweepEngine:
         return yd.cpu().numpy(), res
 
     def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False, t_eval=None, events=False,
-                      max_events=64):
+                      max_events=64, terminal=None):
         """scipy BDF semantics (the other implicit method of the reference's Solver, marlpde/parameters.py:205-219) for every instance of
         the shard.  By default the instances run as concurrent SINGLE runs (marl_integrate_bdf, one context and one HIP stream per worker
         thread - ctypes releases the GIL, and a single BDF run of a small grid leaves the GPU mostly idle between its small launches),
@@ -143,8 +143,11 @@ class HipSweepEngine:
         reached, ``t`` (n_t,) and ``y`` (5N, n_t), either way: the single runs take them from their own dense output, the batched
         sweep writes them inside the sweep (marl_sweep_bdf_eval_dev), as :meth:`integrate_radau` does.  With ``events`` every result
         carries ``t_events``, the root times of the seven monitors (at most ``max_events`` each), either way too: the batched sweep
-        locates them inside the sweep (marl_sweep_bdf_events_dev), the single runs' are cut to ``max_events``."""
+        locates them inside the sweep (marl_sweep_bdf_events_dev), the single runs' are cut to ``max_events``.
+        ``terminal`` as for :meth:`integrate_radau`, either way: the batched sweep stops an instance on the device
+        (marl_sweep_bdf_terminal_dev), the single runs stop themselves (marl_integrate_bdf); None: none, whatever an earlier call set."""
         if batched:
+            self.model.set_terminal(terminal)
             yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
             more = {"events": True, "max_events": max_events} if events else {}
             if t_eval is None:
@@ -178,6 +181,7 @@ class HipSweepEngine:
                         one.use_stream(stream.cuda_stream)
                     else:
                         one.set_scenario(p)
+                    one.set_terminal(terminal)
                     r = one.integrate_bdf(y0[b], t_span, first_step, rtol, atol, t_eval=t_eval, max_attempts=max_attempts)
                     if events:
                         r.t_events = [t[:max(int(max_events), 0)] for t in r.t_events]
@@ -231,14 +235,15 @@ def run_sweep_radau(base_parms, instances, t_span, first_step, rtol, atol, max_a
 
 def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
                   device=None, engine_factory=None, gather=True, balance="cost", cost=None, batched=False, t_eval=None, events=False,
-                  max_events=64):
+                  max_events=64, terminal=None):
     """As :func:`run_sweep_radau` with scipy's BDF semantics; on a GPU the rank's instances run as concurrent single runs, or with
     ``batched=True`` (N <= 409) through the batched BDF kernels, all instances advanced together
     (:meth:`HipSweepEngine.integrate_bdf`).  ``batched``, ``t_eval``, ``events`` and ``max_events`` reach the engine only when asked
     for; with ``t_eval`` two more elements follow, ``n_frames`` and ``y_eval``, and with ``events`` one last element, ``t_events``, as
-    documented for :func:`run_sweep_rk45` (either way of running the shard)."""
+    documented for :func:`run_sweep_rk45` (either way of running the shard).  ``terminal``: as for :func:`run_sweep_radau`, either way
+    of running the shard too; it reaches the engine only when given."""
     return _run_sweep("integrate_bdf", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, t_eval, events, max_events, batched=batched)
+                      balance, cost, t_eval, events, max_events, batched=batched, terminal=terminal)
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
@@ -293,7 +298,7 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
             more |= {"events": True, "max_events": max_events}
         if batched:   # (the BDF driver; passed only when asked for, like `events`)
             more |= {"batched": True}
-        if terminal is not None:   # (the Radau driver; passed only when asked for)
+        if terminal is not None:   # (the Radau and BDF drivers; passed only when asked for)
             more |= {"terminal": terminal}
         y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()

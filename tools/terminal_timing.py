@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
-"""What a terminal monitor saves in a Radau sweep (marl_set_terminal): the 512-instance Phi0 x PhiIni sweep of tools/rk23_timing.py and
+"""What a terminal monitor saves in a Radau sweep, or with --method bdf in a batched BDF sweep (marl_set_terminal): the 512-instance Phi0 x PhiIni sweep of tools/rk23_timing.py and
 DESIGN.md section 8 (16 x 32 values in 0.5 .. 0.8, PhiNR = PhiIni) at N = 200, uniform initial state, rtol = atol = 1e-3, first_step
-1e-6, to t1 = 1 through marl_sweep_radau_dev - once without limits and once with `ones_Phi: 1`, the reference's own example of "stop
+1e-6, to t1 = 1 through marl_sweep_radau_dev (bdf: marl_sweep_bdf_dev / marl_sweep_bdf_terminal_dev) - once without limits and once with `ones_Phi: 1`, the reference's own example of "stop
 here" (marlpde/LHeureux_model.py:113-122), same build, same process, the two alternating in every round; medians over the rounds.
 A measurement, not a test: there is no threshold.
 
-    python tools/terminal_timing.py [--rounds 7] [--t1 1.0]
+    python tools/terminal_timing.py [--method radau|bdf] [--rounds 7] [--t1 1.0]
 
 Per setting: wall time (a host clock around the synchronising entry, the state copy excluded), RHS evaluations summed over the
-instances, instances per status.  One JSON line.  Where a run on an MI355X is recorded: profiles/terminal_timing.log, with the figures
-in DESIGN.md section 8."""
+instances, instances per status.  One JSON line.  Where a run on an MI355X is recorded: profiles/terminal_timing.log (Radau) and
+profiles/bdf_terminal_timing.log (BDF), with the figures in DESIGN.md section 8."""
 import argparse
 import json
 import os
@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--method", choices=("radau", "bdf"), default="radau")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--t1", type=float, default=1.0)
     args = ap.parse_args()
@@ -47,11 +48,11 @@ def main():
         buf = y0.clone()
         torch.cuda.synchronize()
         t = time.perf_counter()
-        res = eq.sweep_radau_device(buf.data_ptr(), (0.0, args.t1), 1e-6, 1e-3, 1e-3)
+        res = getattr(eq, f"sweep_{args.method}_device")(buf.data_ptr(), (0.0, args.t1), 1e-6, 1e-3, 1e-3)
         torch.cuda.synchronize()
         return time.perf_counter() - t, res
 
-    out = {"instances": len(inst), "N": N, "t1": args.t1, "rtol": 1e-3, "atol": 1e-3, "first_step": 1e-6, "rounds": args.rounds}
+    out = {"method": args.method, "instances": len(inst), "N": N, "t1": args.t1, "rtol": 1e-3, "atol": 1e-3, "first_step": 1e-6, "rounds": args.rounds}
     times = {name: [] for name in settings}
     for name in settings:                                      # warm-up, and the counts (the runs are deterministic)
         _, res = call(name)
