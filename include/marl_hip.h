@@ -70,9 +70,9 @@ int marl_synchronize(marl_ctx* ctx);
  * In such a step the roots of ALL active monitors are located (the order needs them), with or without a free slot and also when the
  * caller passed no t_events; they are stored only where a slot is free.  A step that meets no limit runs exactly as without limits.
  * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev,
- * marl_sweep_bdf_terminal_dev.  Every other
- * integrator entry (marl_integrate_rk45 / rk23 [_dev], marl_sweep_rk45* / rk23*, marl_sweep_bdf_dev / _eval_dev / _events_dev, marl_slab_init_control,
- * marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
+ * marl_sweep_bdf_terminal_dev, marl_sweep_rk45_terminal_dev / rk23_terminal_dev, marl_integrate_rk45_terminal / rk23_terminal.  Every other
+ * integrator entry (marl_integrate_rk45 / rk23, marl_integrate_rk45_dev / rk23_dev, marl_sweep_rk45_dev / _eval_dev / _events_dev and their rk23
+ * counterparts, marl_sweep_bdf_dev / _eval_dev / _events_dev, marl_slab_init_control, marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
  * before it touches the state, and is unchanged when none is. */
 int marl_set_terminal(marl_ctx* ctx, const int64_t terminal[7]);
 /* Tuning knobs; unknown names are an error.  See DESIGN.md.
@@ -239,6 +239,31 @@ int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t
                                int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                                int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
+/* The RK45 sweep HONOURING TERMINAL MONITORS (marl_set_terminal; the semantics of the block there; the rule: csrc/marl_terminal.h, its
+ * bookkeeping for one accepted step: csrc/marl_rk_terminal.h): the reference's `terminal` switch (marlpde/LHeureux_model.py:113-122) for
+ * the explicit sweeps.  The three entries above refuse a context with limits; this one ends every instance at its terminal monitor's
+ * root inside the sweep kernel (rk45_sweep_term_kernel): in an accepted step in which a monitor that changed sign meets its limit, the
+ * roots of ALL monitors that changed sign are located (Brent on replays of the step, with or without a free slot, also without
+ * t_events), the rule says which of them happened - counted and, where a slot is free, stored - then the samples with
+ * t_eval[k] <= t_stop are written, and one more replay writes the step's dense output at t_stop into the state: stats[b].status = 1,
+ * stats[b].t = t_stop, stats[b].event_value = that state's monitors, counters those after the accepted step.  A stop in the step that
+ * reaches t1 is a stop.  Instances that meet no limit, and every step before the terminal one, run exactly as under
+ * marl_sweep_rk45_events_dev.  With no limit set this entry dispatches to the kernels of the three entries above (t_eval / n_eval = 0
+ * and t_events == NULL / max_events <= 0 allowed) and is those entries bit for bit.  Arguments as for marl_sweep_rk45_events_dev.
+ * Synchronises. */
+int marl_sweep_rk45_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                 int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                 int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* marl_integrate_rk45 HONOURING TERMINAL MONITORS: the same arguments (host pointers), the same loops - one workgroup for N <= 1024, the
+ * streamed loop, one launch per attempt - which pause on every monitor sign change, also without t_events, while a limit is set.  At
+ * such a pause the roots are located on the step's dense output as without limits; when a monitor meets its limit, those of all
+ * monitors that changed sign, and the rule is applied: stats->status = 1, stats->t = t_stop, y = the dense output at t_stop (the launch
+ * that writes a t_eval sample: bit-equal to a sample at t_stop), y_eval holds the samples with t_eval[k] <= t_stop, a dropped sign
+ * change is neither stored nor counted.  With no limit set this is marl_integrate_rk45. */
+int marl_integrate_rk45_terminal(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                                 const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                                 int64_t max_attempts, marl_stats* stats);
+
 /* ---- adaptive Bogacki-Shampine RK23 -------------------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="RK23", ...): the reference's Solver forwards any solve_ivp method
  * (marlpde/parameters.py:212-213), and on these stability-limited equations RK23 reaches the same time with 1.6 - 3.1 times fewer
@@ -265,6 +290,14 @@ int marl_sweep_rk23_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1,
 int marl_sweep_rk23_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                                int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* marl_sweep_rk45_terminal_dev with RK23 (rk23_sweep_term_kernel) */
+int marl_sweep_rk23_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                 int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                 int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* marl_integrate_rk45_terminal with RK23 */
+int marl_integrate_rk23_terminal(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                                 const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                                 int64_t max_attempts, marl_stats* stats);
 
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,

@@ -58,7 +58,9 @@ def _scipy_events(eq, limits):
 
 def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="../Results/", verbose=True, device=0, terminal=None):
     """``terminal``: the reference's switch (LHeureux_model.py:113-122) - which monitors end the run at their root, as
-    :func:`marlpde_amd.LHeureux_model.terminal_counts` reads it.  Native for Radau and BDF; RK45 / RK23 need ``scipy_driver``."""
+    :func:`marlpde_amd.LHeureux_model.terminal_counts` reads it.  Native for Radau and BDF; for RK45 / RK23 the solver parameters
+    choose: ``native_terminal=True`` - the native loop stops itself (marl_integrate_rk45_terminal / rk23_terminal) - or
+    ``scipy_driver=True`` - solve_ivp drives the HIP RHS."""
     limits = terminal_counts(terminal)
     solver_parms = dict(solver_parms)
     Xstar, Tstar = pde_parms["Xstar"], pde_parms["Tstar"]
@@ -79,17 +81,23 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     no_progress_updates = tracker_parms.get("no_progress_updates", 100_000)
     start = time.time()
     scipy_driver = bool(solver_parms.pop("scipy_driver", False))
+    native_terminal = bool(solver_parms.pop("native_terminal", False))
     if method in ("RK45", "RK23") and not scipy_driver:
-        if any(limits):
+        if any(limits) and not native_terminal:
             eq.close()
-            raise ValueError(f"terminal monitors are not built into the native {method} loop: pass scipy_driver=True in the solver "
-                             "parameters, or use method 'Radau' or 'BDF'")
-        integrate = eq.integrate_rk45 if method == "RK45" else eq.integrate_rk23
+            raise ValueError(f"terminal monitors in the {method} loop are opt-in: pass native_terminal=True in the solver parameters for "
+                             "the native loop (marl_integrate_rk45_terminal / rk23_terminal) or scipy_driver=True for solve_ivp on the "
+                             "HIP RHS, or use method 'Radau' or 'BDF'")
+        if any(limits):
+            eq.set_terminal(limits)
+            integrate = eq.integrate_rk45_terminal if method == "RK45" else eq.integrate_rk23_terminal
+        else:
+            integrate = eq.integrate_rk45 if method == "RK45" else eq.integrate_rk23
         res = integrate(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"],
                         t_eval=t_eval)
         t_out, y_out, t_events = res.t, res.y, res.t_events
         nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
-        if status not in (0, -1):
+        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the implicit branch)
             status = -1
         covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
     elif method in ("Radau", "BDF") and not scipy_driver:

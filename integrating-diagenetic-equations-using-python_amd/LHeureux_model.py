@@ -267,8 +267,10 @@ class LMAHeureuxPorosityDiff:
 
     def set_terminal(self, spec):
         """Make monitors terminal - the reference's ``terminal`` switch (LHeureux_model.py:113-122), for every run of this model from
-        now on (marl_set_terminal).  ``spec`` as for :func:`terminal_counts`; None switches it off again.  Radau and BDF single runs and
-        Radau and BDF sweeps end at the root with ``status`` 1; the other integrators raise while a monitor is terminal."""
+        now on (marl_set_terminal).  ``spec`` as for :func:`terminal_counts`; None switches it off again.  Radau and BDF single runs,
+        Radau, BDF, RK45 and RK23 sweeps and :meth:`integrate_rk45_terminal` / :meth:`integrate_rk23_terminal` end at the root with
+        ``status`` 1; the other integrators (:meth:`integrate_rk45` / :meth:`integrate_rk23` and the ``*_device`` single runs among
+        them) raise while a monitor is terminal."""
         counts = terminal_counts(spec)
         self._check(self._lib.marl_set_terminal(self._ctx, (C.c_int64 * NEVENTS)(*counts)), "marl_set_terminal")
         self._terminal = counts
@@ -383,6 +385,19 @@ class LMAHeureuxPorosityDiff:
         """scipy ``solve_ivp(method="RK23")`` semantics for ONE instance, entirely on the device (marl_integrate_rk23):
         :meth:`integrate_rk45` with Bogacki-Shampine 3(2) - 3 RHS evaluations per attempt, cubic dense output.  Same result."""
         return self._integrate_rk("rk23", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
+    def integrate_rk45_terminal(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
+                                max_attempts=0):
+        """:meth:`integrate_rk45` honouring terminal monitors (:meth:`set_terminal`; marl_integrate_rk45_terminal): the run ends at
+        the terminal monitor's root with ``status`` 1, ``t_reached`` = the root, ``y_final`` the step's dense output there (bit for
+        bit a ``t_eval`` sample at that time), ``t`` / ``y`` the samples up to it and ``t_events`` the roots up to and including
+        it.  The same signature and result; without a terminal monitor the same run."""
+        return self._integrate_rk("rk45_terminal", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
+    def integrate_rk23_terminal(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
+                                max_attempts=0):
+        """:meth:`integrate_rk45_terminal` with RK23 (marl_integrate_rk23_terminal)."""
+        return self._integrate_rk("rk23_terminal", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
     def _integrate_rk(self, method, y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts):
         entry = getattr(self._lib, f"marl_integrate_{method}")
@@ -682,7 +697,11 @@ class LMAHeureuxPorosityDiff:
 
         ``events=True``: the monitors' root times are located inside the sweep (marl_sweep_rk45_events_dev) and returned as
         ``t_events`` - a list of 7 arrays per instance, ``min(n_events[e], max_events)`` long, what the reference prints and stores
-        for every run (Evolve_scenario.py:118-145, 175-177); otherwise sign changes are only counted.  Combinable with ``t_eval``."""
+        for every run (Evolve_scenario.py:118-145, 175-177); otherwise sign changes are only counted.  Combinable with ``t_eval``.
+
+        While a monitor is terminal (:meth:`set_terminal`) the sweep runs through marl_sweep_rk45_terminal_dev: an instance whose
+        terminal monitor occurs ends at that root inside the sweep kernel with ``status`` 1, ``t_reached`` = the root and the state
+        there; the results are built as above, with or without ``t_eval`` and ``events``."""
         return self._sweep_rk_device("rk45", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events)
 
     def sweep_rk23_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
@@ -694,6 +713,21 @@ class LMAHeureuxPorosityDiff:
         plain, with_eval, with_events = (f"marl_sweep_{method}_dev", f"marl_sweep_{method}_eval_dev", f"marl_sweep_{method}_events_dev")
         stats = (MarlStats * self.n_instances)()
         locate = bool(events) and int(max_events) > 0
+        if any(self.terminal):
+            entry = f"marl_sweep_{method}_terminal_dev"
+            te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
+            if te.size and not y_eval_dev_ptr:
+                raise ValueError(f"sweep_{method}_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
+            n_done = np.zeros(self.n_instances, dtype=np.int64)
+            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan) if locate else None
+            rc = getattr(self._lib, entry)(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol),
+                                           float(atol), int(max_attempts), _as_ptr(te) if te.size else None, te.size,
+                                           C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
+                                           _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
+            self._check(rc, entry)
+            return [RK45Result(s, t=te[:int(k)].copy() if t_eval is not None else None,
+                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
+                    for b, (s, k) in enumerate(zip(stats, n_done))]
         if t_eval is None and not locate:
             rc = getattr(self._lib, plain)(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]),
                                                float(first_step), float(rtol), float(atol), int(max_attempts), stats)

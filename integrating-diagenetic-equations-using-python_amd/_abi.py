@@ -93,6 +93,10 @@ PROTOTYPES = {
     "marl_sweep_rk45_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
     "marl_sweep_rk45_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, C.POINTER(MarlStats)]),
     "marl_sweep_rk45_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
+    "marl_sweep_rk45_terminal_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
+    "marl_sweep_rk23_terminal_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
+    "marl_integrate_rk45_terminal": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
+    "marl_integrate_rk23_terminal": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_integrate_rk23": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_integrate_rk23_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
     "marl_sweep_rk23_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),

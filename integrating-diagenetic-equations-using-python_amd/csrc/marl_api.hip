@@ -853,11 +853,12 @@ static int64_t rk45_blocks(const marl_ctx* ctx) { return rk_blocks(ctx, 256 - 12
 // ---- the explicit adaptive methods behind one set of host drivers (rk_run, sweep_rk) --------------------------------------------
 // RK45: the kernels of marl_kernels.h, launched here.  RK23: those of marl_rk23.h, a translation unit of its own (marl_rk23.hip),
 // reached through its launchers.  What differs between the two on the host is in this table and nowhere else.
-enum : int { SWEEP_PLAIN = 0, SWEEP_EVENTS = 1, SWEEP_EVAL = 2, SWEEP_ROOTS = 3 };   // the four one-workgroup kernels of a method
+enum : int { SWEEP_PLAIN = 0, SWEEP_EVENTS = 1, SWEEP_EVAL = 2, SWEEP_ROOTS = 3, SWEEP_TERM = 4 };   // the five one-workgroup kernels of a method
 struct SweepLaunch {
     double *Y, *Yold, *Fold;
     const double* t_eval; int64_t n_eval; double* Yeval; int64_t* n_done;
     double* t_events; int64_t max_events;
+    const int64_t* terminal;   // SWEEP_TERM: the seven limits (host); else NULL
 };
 struct RkMethod {
     const char* name;        // in front of error messages: "rk45", "rk23"
@@ -1028,8 +1029,14 @@ static int rk45_m_sweep(marl_ctx* ctx, int kind, int blk, unsigned batch, const 
         case SWEEP_PLAIN: SWEEP_DISPATCH(rk45_sweep_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.Yold, a.Fold) break;
         case SWEEP_EVENTS: SWEEP_DISPATCH(rk45_sweep_events_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.Yold, a.Fold) break;
         case SWEEP_EVAL: SWEEP_DISPATCH(rk45_sweep_eval_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.t_eval, a.n_eval, a.Yeval, a.n_done) break;
-        default: SWEEP_DISPATCH(rk45_sweep_roots_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events,
-                                a.max_events) break;
+        case SWEEP_ROOTS: SWEEP_DISPATCH(rk45_sweep_roots_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events,
+                                         a.max_events) break;
+        default: {
+            TermLimits lim = {};
+            for (int e = 0; e < 7; e++) lim.k[e] = a.terminal[e];
+            SWEEP_DISPATCH(rk45_sweep_term_kernel, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events,
+                           a.max_events, lim) break;
+        }
     }
     LAUNCH_OK(ctx);
     return 0;
@@ -1067,7 +1074,7 @@ static const RkMethod kRk45 = {"rk45", "marl_sweep_rk45_dev", 256 - 2 * 6, true,
 extern "C" {
 int marl_rk23_launch_sweep(int kind, int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls, int64_t N,
                            double* Yold, double* Fold, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events,
-                           int64_t max_events);
+                           int64_t max_events, const int64_t* terminal);
 int marl_rk23_launch_attempt(int tiled, int vd, unsigned nb, hipStream_t stream, double* Y0, double* Y1, double* F0, double* F1, const void* consts,
                              const int64_t slab5[5], const void* ctrl, double* part);
 int marl_rk23_launch_control(hipStream_t stream, const double* recs, int64_t nrec, void* ctrl);
@@ -1082,7 +1089,8 @@ static int rk23_launched(marl_ctx* ctx, int err)
 static int rk23_m_sweep(marl_ctx* ctx, int kind, int blk, unsigned batch, const SweepLaunch& a)
 {
     return rk23_launched(ctx, marl_rk23_launch_sweep(kind, blk, ctx->var_dphi ? 1 : 0, batch, ctx->stream, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, a.Yold,
-                                                     a.Fold, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events));
+                                                     a.Fold, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events,
+                                                     kind == SWEEP_TERM ? a.terminal : nullptr));
 }
 static int rk23_m_attempt(marl_ctx* ctx, int64_t nb, int layout)
 {
@@ -1137,7 +1145,7 @@ static void ctrl_to_stats(const Rk45Ctrl& c, marl_stats* st)
     st->nfev = c.nfev;
     st->n_accepted = c.n_acc;
     st->n_rejected = c.n_rej;
-    st->status = c.status;
+    st->status = c.status == ST_TERMINAL ? 1 : c.status;   // scipy's "A termination event occurred."
     st->t = c.t;
     st->h_next = c.h_abs;
     for (int e = 0; e < 7; e++) { st->event_value[e] = c.g[e]; st->n_events[e] = c.n_events[e]; }
@@ -1171,6 +1179,10 @@ static int check_ivp_args(marl_ctx* ctx, const char* name, double t0, double t1,
 // The adaptive loop on device buffers buf[0..3] (`layout`), state already in buf[0].
 // small = true: the grid fits one workgroup -> the persistent sweep kernel runs all attempts on-chip
 // (state in buf[0], FIELD-MAJOR; (y_old, f_old) of a paused step in buf[1], buf[3]).
+// Terminal monitors (ctx->terminal; only marl_integrate_rk45_terminal / rk23_terminal arrive here with limits): the loop pauses on every
+// sign change also without t_events; at such a pause rk_terminal_step (marl_rk_terminal.h, the rule the sweep kernels apply) says which
+// of the step's sign changes happened - when a limit is met, after the roots of ALL of them are located - and where the run ends: the
+// samples up to t_stop, then the step's dense output at t_stop as the state (the launch that writes a sample), status 1.
 static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, double t0, double t1, double first_step, double rtol, double atol,
                     const double* t_eval, int64_t n_eval, double* y_eval_dev, double* t_events, int64_t max_events,
                     int64_t max_attempts, marl_stats* stats)
@@ -1190,11 +1202,11 @@ static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, doub
     LAUNCH_OK(ctx);
     int64_t eval_i = 0;
     // t_eval == t0 is emitted on the first step by scipy (dense output at x = 0 == y_old)
-    const bool events_on = t_events != nullptr && max_events > 0;
+    const bool events_on = t_events != nullptr && max_events > 0, term = has_terminal(ctx);
     auto next_pause = [&]() { return eval_i < n_eval ? t_eval[eval_i] : (double)INFINITY; };
     hipLaunchKernelGGL(rk45_resume_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->dctrl, next_pause(), max_attempts);
     LAUNCH_OK(ctx);
-    if (events_on) {
+    if (events_on || term) {
         // pause_on_event is a plain field: set it through a tiny host round trip once
         HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1209,7 +1221,7 @@ static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, doub
         if (small) {
             // events: pauses on monitor sign changes (root finding) - the loop shape that decides with this step's events
             const SweepLaunch a = {ctx->buf[0], ctx->buf[1], ctx->buf[3], nullptr, 0, nullptr, nullptr, nullptr, 0};
-            if (int rc = m.sweep(ctx, events_on ? SWEEP_EVENTS : SWEEP_PLAIN, blk, 1, a)) return rc;
+            if (int rc = m.sweep(ctx, (events_on || term) ? SWEEP_EVENTS : SWEEP_PLAIN, blk, 1, a)) return rc;
         } else if (streamed) {
             if (int rc = launch_rk45_stream(ctx, layout, ctx->rk45_stream_attempts)) return rc;
         } else {
@@ -1226,9 +1238,16 @@ static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, doub
         if (hc.status == ST_RUNNING) continue;
         const bool stepped = hc.n_acc > 0;
         // event roots inside the last accepted step (ivp.py:673-694)
-        if (events_on && stepped) {
+        double t_stop = INFINITY;   // < +inf: a terminal monitor ends the run inside this step (ivp.py:696-704)
+        if ((events_on || term) && stepped) {
+            uint32_t active = 0;
+            double roots[7] = {0, 0, 0, 0, 0, 0, 0};
+            for (int e = 0; e < 7; e++)
+                if (hc.n_events[e] > seen_events[e]) active |= 1u << e;
+            // with a limit met, every sign change of the step is located: the order of the roots decides which of them happened
+            const bool met = term && rk_terminal_any_met(active, seen_events, ctx->terminal);
             for (int e = 0; e < 7; e++) {
-                if (hc.n_events[e] > seen_events[e]) {
+                if (((active >> e) & 1) && (events_on || met)) {
                     // only the newest sign change can be refined (earlier ones were refined at their own pause)
                     double ga[7];
                     if (int rc = dense_eval(ctx, m, layout, small, hc, hc.t_old, nullptr, ga)) return rc;
@@ -1240,15 +1259,29 @@ static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, doub
                         return 0;
                     };
                     if (int rc = brent_root(monitor_at, hc.t_old, ga[e], hc.t, hc.g[e], &root)) return rc;
+                    roots[e] = root;
+                    if (met) continue;   // stored and counted below, once the rule has spoken
                     for (int64_t k = seen_events[e]; k < hc.n_events[e]; k++)
                         if (k < max_events) t_events[e * max_events + k] = root;
                     seen_events[e] = hc.n_events[e];
                 }
             }
+            if (met) {
+                uint32_t keep = 0;
+                int64_t slot[7];
+                rk_terminal_step(active, roots, seen_events, ctx->terminal, events_on ? max_events : 0, &keep, &t_stop, seen_events, slot);
+                for (int e = 0; e < 7; e++) {
+                    if (slot[e] >= 0) t_events[e * max_events + slot[e]] = roots[e];
+                    hc.n_events[e] = seen_events[e];   // a dropped sign change is un-counted: it never happened
+                }
+            } else if (!events_on) {
+                for (int e = 0; e < 7; e++) seen_events[e] = hc.n_events[e];
+            }
         }
+        const double t_lim = t_stop < hc.t ? t_stop : hc.t;   // the samples of this step: up to where it ends
         // t_eval samples inside (t_old, t]  (ivp.py:706-723)
         if (stepped) {
-            while (eval_i < n_eval && t_eval[eval_i] <= hc.t) {
+            while (eval_i < n_eval && t_eval[eval_i] <= t_lim) {
                 double* dst = y_eval_dev + eval_i * sd;
                 if (t_eval[eval_i] <= hc.t_old && hc.n_acc == 1 && t_eval[eval_i] == t0) {
                     HIP_OK(ctx, hipMemcpyAsync(dst, small ? ctx->buf[1] : ctx->buf[hc.cur ^ 1], sizeof(double) * sd, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1260,6 +1293,14 @@ static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, doub
                 HIP_OK(ctx, hipMemcpyAsync(y_eval_dev + eval_i * sd, ctx->buf[small ? 0 : hc.cur], sizeof(double) * sd, hipMemcpyDeviceToDevice, ctx->stream));
                 eval_i++;
             }
+        }
+        if (t_stop <= hc.t) {   // the state there (the expression that writes a sample), its monitors, scipy's status 1
+            double g[7];
+            if (int rc = dense_eval(ctx, m, layout, small, hc, t_stop, ctx->buf[small ? 0 : hc.cur], g)) return rc;
+            for (int e = 0; e < 7; e++) hc.g[e] = g[e];
+            hc.t = t_stop;
+            hc.status = ST_TERMINAL;
+            break;
         }
         if (hc.status != ST_PAUSED) break;
         hipLaunchKernelGGL(rk45_resume_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->dctrl, next_pause(), max_attempts);
@@ -1289,15 +1330,17 @@ static int grow_dev(marl_ctx* ctx, double** buf, size_t* cap, size_t n)
 
 // The RK45 sweep behind marl_sweep_rk45_dev / _eval_dev / _events_dev (`entry`: the one the caller used).  Neither samples (n_eval == 0)
 // nor roots (no t_events or max_events <= 0): rk45_sweep_kernel; samples only: rk45_sweep_eval_kernel; roots, with samples or
-// without: rk45_sweep_roots_kernel.
+// without: rk45_sweep_roots_kernel.  terminal_ok: the entry honours ctx->terminal (marl_sweep_rk45_terminal_dev / rk23; the others refuse a
+// context with limits): with a limit set the sweep is one launch of rk45_sweep_term_kernel, whatever else was asked for; with none it is
+// the dispatch above.
 static int sweep_rk(const RkMethod& m, const char* entry, marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                       int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done, double* t_events,
-                      int64_t max_events, marl_stats* stats)
+                      int64_t max_events, marl_stats* stats, bool terminal_ok = false)
 {
     if (!ctx || !y_dev || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval_dev || !n_done)))
         return ctx ? fail(ctx, -1, "%s: invalid argument", entry) : -1;
-    NO_TERMINAL(ctx, entry)
-    const bool frames = n_eval > 0, roots = t_events && max_events > 0;
+    if (!terminal_ok) { NO_TERMINAL(ctx, entry) }
+    const bool frames = n_eval > 0, roots = t_events && max_events > 0, term = has_terminal(ctx);
     if (!frames && !roots && n_done) memset(n_done, 0, sizeof(int64_t) * ctx->batch);   // nothing to sample: the plain sweep itself
     if (!(first_step > 0) || !(t1 >= t0)) return fail(ctx, -1, "%s: need first_step > 0 and t1 >= t0 (forward integration)", m.name);
     if (t1 > t0 && first_step > t1 - t0) return fail(ctx, -1, "%s: `first_step` exceeds bounds", m.name);
@@ -1310,20 +1353,21 @@ static int sweep_rk(const RkMethod& m, const char* entry, marl_ctx* ctx, double*
     const size_t n_tev = roots ? (size_t)ctx->batch * 7 * (size_t)max_events : 0;
     if (frames)
         if (int rc = grow_dev(ctx, &ctx->sw_teval, &ctx->sw_teval_cap, (size_t)n_eval)) return rc;
-    if ((frames || roots) && !ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
+    if ((frames || roots || term) && !ctx->sw_ndone) HIP_OK(ctx, hipMalloc((void**)&ctx->sw_ndone, sizeof(int64_t) * ctx->batch));
     if (roots) {
         if (int rc = grow_dev(ctx, &ctx->sw_tev, &ctx->sw_tev_cap, n_tev)) return rc;
         HIP_OK(ctx, hipMemsetAsync(ctx->sw_tev, 0xff, sizeof(double) * n_tev, ctx->stream));   // NaN beyond the roots found (all bits set is a quiet NaN)
     }
     // (pageable host memory: the copy has left the caller's array when the call returns)
     if (frames) HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, t_eval, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
-    if (frames || roots) HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
+    if (frames || roots || term) HIP_OK(ctx, hipMemsetAsync(ctx->sw_ndone, 0, sizeof(int64_t) * ctx->batch, ctx->stream));   // an instance that never runs writes none
     if (int rc = launch_monitors(ctx, y_dev, LAYOUT_FIELD_MAJOR)) return rc;
     hipLaunchKernelGGL(rk45_init_kernel, dim3((unsigned)ctx->batch), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, clamp_rtol(rtol),
                        atol, (int64_t)NF * ctx->N, max_attempts, 0);
     LAUNCH_OK(ctx);
-    const SweepLaunch a = {y_dev, nullptr, nullptr, ctx->sw_teval, n_eval, y_eval_dev, ctx->sw_ndone, ctx->sw_tev, max_events};
-    if (int rc = m.sweep(ctx, roots ? SWEEP_ROOTS : (frames ? SWEEP_EVAL : SWEEP_PLAIN), blk, (unsigned)ctx->batch, a)) return rc;
+    const SweepLaunch a = {y_dev, nullptr, nullptr, frames ? ctx->sw_teval : nullptr, n_eval, y_eval_dev, ctx->sw_ndone, roots ? ctx->sw_tev : nullptr,
+                           roots ? max_events : 0, term ? ctx->terminal : nullptr};
+    if (int rc = m.sweep(ctx, term ? SWEEP_TERM : (roots ? SWEEP_ROOTS : (frames ? SWEEP_EVAL : SWEEP_PLAIN)), blk, (unsigned)ctx->batch, a)) return rc;
     HIP_OK(ctx, hipMemcpyAsync(ctx->hctrl, ctx->dctrl, sizeof(Rk45Ctrl) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
     if ((frames || roots) && n_done) HIP_OK(ctx, hipMemcpyAsync(n_done, ctx->sw_ndone, sizeof(int64_t) * ctx->batch, hipMemcpyDeviceToHost, ctx->stream));
     if (roots) HIP_OK(ctx, hipMemcpyAsync(t_events, ctx->sw_tev, sizeof(double) * n_tev, hipMemcpyDeviceToHost, ctx->stream));
@@ -1474,6 +1518,14 @@ int marl_sweep_rk45_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t
                       t_events, max_events, stats);
 }
 
+int marl_sweep_rk45_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                 int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                                 double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_rk(kRk45, "marl_sweep_rk45_terminal_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    t_events, max_events, stats, true);
+}
+
 // marl_integrate_<method>_dev
 static int integrate_rk_dev(const RkMethod& m, marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
                             double atol, int64_t max_attempts, marl_stats* stats)
@@ -1496,10 +1548,11 @@ static int integrate_rk_dev(const RkMethod& m, marl_ctx* ctx, double* y_dev, int
 // marl_integrate_<method>
 static int integrate_rk(const RkMethod& m, marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
                         const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
-                        int64_t max_attempts, marl_stats* stats)
+                        int64_t max_attempts, marl_stats* stats, bool terminal_ok = false)
 {
-    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_%s: invalid argument", m.name) : -1;
-    NO_TERMINAL(ctx, (std::string("marl_integrate_") + m.name).c_str())
+    if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval)))
+        return ctx ? fail(ctx, -1, "marl_integrate_%s%s: invalid argument", m.name, terminal_ok ? "_terminal" : "") : -1;
+    if (!terminal_ok) { NO_TERMINAL(ctx, (std::string("marl_integrate_") + m.name).c_str()) }
     if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s: single-instance context required (use %s)", m.name, m.sweep_entry);
     if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -1579,6 +1632,29 @@ int marl_sweep_rk23_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t
 {
     return sweep_rk(kRk23, "marl_sweep_rk23_events_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
                     t_events, max_events, stats);
+}
+
+int marl_sweep_rk23_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                 int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                                 double* t_events, int64_t max_events, marl_stats* stats)
+{
+    return sweep_rk(kRk23, "marl_sweep_rk23_terminal_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    t_events, max_events, stats, true);
+}
+
+// the single runs that stop at a terminal monitor's root (rk_run)
+int marl_integrate_rk45_terminal(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                                 const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                                 int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk(kRk45, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats, true);
+}
+
+int marl_integrate_rk23_terminal(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                                 const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                                 int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk(kRk23, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats, true);
 }
 
 

@@ -30,6 +30,7 @@
 #include "marl_math.h"
 #include "marl_brent.h"
 #include "marl_rk_ctrl.h"
+#include "marl_rk_terminal.h"
 
 namespace marl {
 
@@ -2095,14 +2096,18 @@ struct Dp45Method { static constexpr int N_WEIGHTS = 7; };
 // that step inside the loop (see there); without it the four trailing arguments are unused and the code is what it was without them.
 // ROOTS (FAST and EVAL only; rk45_sweep_roots_kernel): the root times of the monitors that change sign in an accepted step are located
 // by Brent's method on dense-output replays of that step, before its samples and its commit (see there); two more arguments.
-template <int BLK, bool VD, bool FAST, bool EVAL = false, bool ROOTS = false, class M = Dp45Method>
+// TERM (ROOTS only; rk45_sweep_term_kernel): terminal monitors (marl_set_terminal) - a step in which an active monitor meets its limit
+// `lim` ends the instance at that monitor's root (see there; the rule: marl_rk_terminal.h); every other step is a ROOTS step.
+struct TermLimits { int64_t k[7]; };   // marl_set_terminal's limits, a kernel argument by value
+template <int BLK, bool VD, bool FAST, bool EVAL = false, bool ROOTS = false, class M = Dp45Method, bool TERM = false>
 __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls, int64_t N,
                                                 double* __restrict__ Yold, double* __restrict__ Fold,
                                                 const double* __restrict__ t_eval = nullptr, int64_t n_eval = 0,
                                                 double* __restrict__ Yeval = nullptr, int64_t* __restrict__ n_done = nullptr,
-                                                double* __restrict__ t_events = nullptr, int64_t max_events = 0)
+                                                double* __restrict__ t_events = nullptr, int64_t max_events = 0, TermLimits lim = {})
 {
     constexpr bool DP = std::is_same_v<M, Dp45Method>;
+    static_assert(ROOTS || !TERM, "the stop is found by the root search");
     static_assert(FAST || !EVAL, "the sampling loop is built on the replicated controller");
     static_assert((FAST && EVAL) || !ROOTS, "a Brent function evaluation is a dense-output replay");
     using SB = StencilBlock<BLK, false, VD>;
@@ -2202,6 +2207,18 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         //     step are read after one more workgroup barrier and before the next DECISION replaces them.  Replays sit between that decision
         //     and the next attempt, add barriers and decide nothing; events_pending stays set through them, so the bookkeeping still
         //     follows the evaluations of the next attempt - or the loop, when the step was the last.
+        //   TERM: in an accepted step in which a monitor that changed sign meets its limit (rk_terminal_any_met: replicated scalars,
+        //   from rec, sc.g, sc.n_events and the kernel argument) ALL monitors that changed sign are located, with or without a slot, the
+        //   roots stay in replicated scalars (term_root) and nothing is written to sc until the last of them is known; then every wave
+        //   applies rk_terminal_step to the same numbers, one barrier lets every wave finish reading sc.n_events, and thread 0 does the
+        //   bookkeeping of the kept monitors and stores their roots where a slot is free.  The samples up to t_stop follow (next_sample),
+        //   then ONE more replay with the weights of t_stop: the frame expression becomes the state (parked fields through pk[]), its
+        //   monitors go through the monitor columns into rec and sc.g, c.t = t_stop, ST_TERMINAL, and the loop ends.  term_step,
+        //   stopping, t_stop and the kept mask are replicated scalars like br_phase, so every barrier of these trips is reached by every
+        //   wave or by none; a step that meets no limit takes none of these branches and is a ROOTS step instruction for instruction.
+        bool term_step = false, stopping = false;    // TERM: the step just accepted ends the run; this trip replays it at t_stop
+        int term_act = 0;                            // the monitors that changed sign in that step (bit e)
+        double t_stop = 0.0, term_root[7] = {};      // where the run ends; the roots of that step's monitors
         int64_t ie = 0;                              // the next sample, t_eval[ie]; the same in every lane (SGPRs)
         bool sampling = false;                       // this trip of the loop replays the step just accepted for sample ie
         double te = 0.0;                             // t_eval[ie] of that replay
@@ -2212,7 +2229,11 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         auto next_sample = [&]() -> bool {           // is sample ie inside the step just accepted?  then dw = its weights
             if (!(ie < n_eval)) return false;
             te = to_sgpr(t_eval[ie]);
-            if (!(te <= c.t)) return false;
+            if constexpr (TERM) {
+                if (!(te <= (term_step ? t_stop : c.t))) return false;   // a step that ends the run: the samples up to t_stop
+            } else {
+                if (!(te <= c.t)) return false;
+            }
             const DenseWeights w = weights_of((te - c.t_old) / c.h_prev);
 #pragma unroll
             for (int j = 0; j < M::N_WEIGHTS; j++) dw.w[j] = to_sgpr(w.w[j]);
@@ -2252,6 +2273,7 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
         while (true) {
             bool replay = sampling;                  // workgroup-uniform: this trip is no attempt
             if constexpr (ROOTS) replay = sampling || br_phase != 0;
+            if constexpr (TERM) replay = replay || stopping;
             const double h = (EVAL && replay) ? c.h_prev : c.h_try;
             // (the first evaluation's exchange barrier also orders the monitor reduction of the previous attempt before the
             // event bookkeeping below; dp45_attempt is opaque, so the bookkeeping follows the whole attempt's evaluations -
@@ -2262,6 +2284,46 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
             } else {
                 if constexpr (EVAL) M::template attempt<BLK, SB, PARK, true>(sb, h, y, k1, yn, k7, esum, aux, dw, pk, replay);
                 else M::template attempt<BLK, SB, PARK, false>(sb, h, y, k1, yn, k7, esum, aux, DenseWeights{}, pk, false);
+            }
+            if constexpr (TERM) {
+                if (stopping) {                      // workgroup-uniform: the state at t_stop, its monitors, and the way out
+                    double q[NQ];
+                    monitors_init(q);
+                    MARL_ONCE if (l0 < N) {
+                        double d[NF];
+#pragma unroll
+                        for (int f = 0; f < NF; f++) d[f] = (t_stop == c.t_old) ? MARL_Y(f) : h * esum[f] + MARL_Y(f);   // (as the frames)
+                        double U, W;
+                        uw_point(d[4], C, sb.T, U, W);
+                        monitors_accumulate<true>(q, d, U, W);
+#pragma unroll
+                        for (int f = 0; f < NF; f++) {
+                            if (f < PARK) pk[f * BLK] = d[f]; else y[f] = d[f];
+                        }
+                    }
+#pragma unroll
+                    for (int j = 1; j < NQ; j++) mon[(j - 1) * BLK + threadIdx.x] = q[j];
+                    __syncthreads();
+#pragma unroll
+                    for (int jj = 0; jj < (NMON + NW - 1) / NW; jj++) {   // the reduction of an accepted step's monitors, below
+                        const int j = wave + jj * NW + 1;
+                        if (j < NQ) {
+                            const double sgn = (j <= NQMIN) ? 1.0 : -1.0;
+                            double a = sgn * mon[(j - 1) * BLK + lane];
+#pragma unroll
+                            for (int i = 1; i < NW; i++) a = __builtin_fmin(a, sgn * mon[(j - 1) * BLK + lane + 64 * i]);
+#pragma unroll
+                            for (int off = 32; off > 0; off >>= 1) a = __builtin_fmin(a, __shfl_xor(a, off, 64));
+                            if (lane == 0) rec[j] = sgn * a;
+                        }
+                    }
+                    __syncthreads();
+                    if (threadIdx.x < 7) sc.g[threadIdx.x] = rk45_monitor_of_record(rec, threadIdx.x);
+                    if (c.status == ST_RUNNING) c.attempts--;   // (the attempt prepared after the accepted step is never made)
+                    c.t = t_stop;
+                    c.status = ST_TERMINAL;
+                    break;
+                }
             }
             if constexpr (ROOTS) {
                 if (br_phase != 0) {                 // workgroup-uniform
@@ -2319,13 +2381,49 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                         continue;
                     }
                     // (wave 0 did this step's bookkeeping before its first probe: n_events[br_e] - 1 is the count before the step, < max_events)
-                    if (threadIdx.x == 0) t_events[((int64_t)blockIdx.x * 7 + br_e) * max_events + (sc.n_events[br_e] - 1)] = root;
+                    if constexpr (TERM) {
+                        if (term_step) {             // kept until the rule has said which of them happened
+#pragma unroll
+                            for (int e = 0; e < 7; e++)
+                                if (e == br_e) term_root[e] = to_sgpr(root);
+                        } else if (threadIdx.x == 0) t_events[((int64_t)blockIdx.x * 7 + br_e) * max_events + (sc.n_events[br_e] - 1)] = root;
+                    } else {
+                        if (threadIdx.x == 0) t_events[((int64_t)blockIdx.x * 7 + br_e) * max_events + (sc.n_events[br_e] - 1)] = root;
+                    }
                     ev_mask = to_sgpr((int32_t)(ev_mask & ~(1 << br_e)));
                     if (ev_mask != 0) {
                         first_probe();
                         continue;
                     }
                     br_phase = 0;
+                    if constexpr (TERM) {
+                        if (term_step) {             // every root of the step is known: the rule, the same in every lane
+                            int64_t nev[7], slot[7];
+#pragma unroll
+                            for (int e = 0; e < 7; e++) nev[e] = sc.n_events[e];
+                            uint32_t keep = 0;
+                            double ts = c.t;
+                            rk_terminal_step((uint32_t)term_act, term_root, nev, lim.k, max_events, &keep, &ts, nev, slot);
+                            t_stop = to_sgpr(ts);
+                            const int kept = to_sgpr((int32_t)keep);
+                            __syncthreads();         // every wave has read sc.n_events
+                            if (threadIdx.x == 0) {
+#pragma unroll
+                                for (int e = 0; e < 7; e++) {
+                                    if (!((kept >> e) & 1)) continue;
+                                    rk45_event_one(sc, e, rk45_monitor_of_record(rec, e));
+                                    if (slot[e] >= 0) t_events[((int64_t)blockIdx.x * 7 + e) * max_events + slot[e]] = term_root[e];
+                                }
+                            }
+                            if (next_sample()) {     // the samples up to t_stop
+                                sampling = true;
+                                continue;
+                            }
+                            stopping = true;
+                            probe_at(t_stop);
+                            continue;
+                        }
+                    }
                     if (next_sample()) {             // then the step's samples
                         sampling = true;
                         continue;
@@ -2350,6 +2448,13 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                     ie = to_sgpr(ie + 1);
                     if (next_sample()) continue;     // another sample in the same step
                     sampling = false;
+                    if constexpr (TERM) {
+                        if (term_step) {             // then the stop
+                            stopping = true;
+                            probe_at(t_stop);
+                            continue;
+                        }
+                    }
 #pragma unroll
                     for (int f = 0; f < NF; f++) {   // the commit the accepted attempt postponed: y_new, k7 as the replay left them
                         if (f < PARK) pk[f * BLK] = yn[f]; else y[f] = yn[f];
@@ -2421,8 +2526,26 @@ __device__ __forceinline__ void rk45_sweep_body(double* __restrict__ Y, const De
                         const double go = sc.g[e], gn = rk45_monitor_of_record(rec, e);
                         const bool up = go <= 0.0 && gn >= 0.0, down = go >= 0.0 && gn <= 0.0;
                         if ((up || down) && sc.n_events[e] < max_events) m |= 1 << e;
+                        if constexpr (TERM) {
+                            if (up || down) term_act |= 1 << e;
+                        }
                     }
                     ev_mask = to_sgpr((int32_t)m);
+                    if constexpr (TERM) {
+                        term_act = to_sgpr((int32_t)term_act);
+                        int64_t nev[7];
+#pragma unroll
+                        for (int e = 0; e < 7; e++) nev[e] = sc.n_events[e];
+                        if (to_sgpr((int32_t)rk_terminal_any_met((uint32_t)term_act, nev, lim.k)) != 0) {
+                            // a limit is met: all of the step's roots first, kept in registers; sc stays as it is until the rule has spoken
+                            term_step = true;
+                            ev_mask = term_act;
+                            events_pending = false;
+                            first_probe();
+                            continue;
+                        }
+                        term_act = 0;
+                    }
                     if (ev_mask != 0) {              // roots inside this step: locate them first
                         __syncthreads();             // every wave has read sc.g / sc.n_events
                         event_bookkeeping();
@@ -2511,6 +2634,20 @@ __global__ void __launch_bounds__(BLK) rk45_sweep_roots_kernel(double* __restric
                                                                double* __restrict__ t_events, int64_t max_events)
 {
     rk45_sweep_body<BLK, VD, true, true, true>(Y, consts, ctrls, N, nullptr, nullptr, t_eval, n_eval, Yeval, n_done, t_events, max_events);
+}
+
+// rk45_sweep_roots_kernel honouring terminal monitors (marl_sweep_rk45_terminal_dev; `lim`: marl_set_terminal's limits): an instance
+// whose monitor meets its limit ends at that root with ST_TERMINAL, the state the step's dense output there.  t_events may be NULL with
+// max_events = 0 (the roots of a terminal step are located all the same), n_eval may be 0.
+template <int BLK, bool VD = false>
+__global__ void __launch_bounds__(BLK) rk45_sweep_term_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
+                                                              Rk45Ctrl* __restrict__ ctrls, int64_t N,
+                                                              const double* __restrict__ t_eval, int64_t n_eval,
+                                                              double* __restrict__ Yeval, int64_t* __restrict__ n_done,
+                                                              double* __restrict__ t_events, int64_t max_events, TermLimits lim)
+{
+    rk45_sweep_body<BLK, VD, true, true, true, Dp45Method, true>(Y, consts, ctrls, N, nullptr, nullptr, t_eval, n_eval, Yeval, n_done, t_events,
+                                                                 max_events, lim);
 }
 
 template <int BLK, bool VD = false>

@@ -153,6 +153,18 @@ __global__ void __launch_bounds__(BLK) rk23_sweep_roots_kernel(double* __restric
                                                            max_events);
 }
 
+// rk23_sweep_roots_kernel honouring terminal monitors (arguments: rk45_sweep_term_kernel)
+template <int BLK, bool VD = false>
+__global__ void __launch_bounds__(BLK) rk23_sweep_term_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
+                                                              Rk45Ctrl* __restrict__ ctrls, int64_t N,
+                                                              const double* __restrict__ t_eval, int64_t n_eval,
+                                                              double* __restrict__ Yeval, int64_t* __restrict__ n_done,
+                                                              double* __restrict__ t_events, int64_t max_events, TermLimits lim)
+{
+    rk45_sweep_body<BLK, VD, true, true, true, Bs23Method, true>(Y, consts, ctrls, N, nullptr, nullptr, t_eval, n_eval, Yeval, n_done, t_events,
+                                                                 max_events, lim);
+}
+
 // ---- one large grid, one launch per attempt ---------------------------------------------------------------------------------------
 // The counterpart of rk45_attempt_kernel: reads (y, f) from buffer `cur`, writes (y_new, f_new) into the other buffer and one
 // reduction record per block; rk23_control_kernel then accepts (flips `cur`) or rejects.  Three evaluations after K1: a halo of

@@ -14,32 +14,38 @@ using namespace marl_rk23;
 #define RK23_VIS extern "C" __attribute__((visibility("hidden")))
 
 namespace {
-// the kernel of the rk45_sweep_* family's `kind`: 0 plain, 1 events (pausing loop), 2 eval, 3 roots
+// the kernel of the rk45_sweep_* family's `kind`: 0 plain, 1 events (pausing loop), 2 eval, 3 roots, 4 roots with terminal monitors (`lim`)
 template <int BLK, bool VD>
 void launch_sweep_t(int kind, unsigned grid, hipStream_t stream, double* Y, const DevConsts* consts, Rk45Ctrl* ctrls, int64_t N, double* Yold,
-                    double* Fold, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events, int64_t max_events)
+                    double* Fold, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events, int64_t max_events,
+                    const TermLimits& lim)
 {
     const dim3 g(grid), b(BLK);
     switch (kind) {
         case 0: hipLaunchKernelGGL((rk23_sweep_kernel<BLK, VD>), g, b, 0, stream, Y, consts, ctrls, N, Yold, Fold); break;
         case 1: hipLaunchKernelGGL((rk23_sweep_events_kernel<BLK, VD>), g, b, 0, stream, Y, consts, ctrls, N, Yold, Fold); break;
         case 2: hipLaunchKernelGGL((rk23_sweep_eval_kernel<BLK, VD>), g, b, 0, stream, Y, consts, ctrls, N, t_eval, n_eval, Yeval, n_done); break;
-        default: hipLaunchKernelGGL((rk23_sweep_roots_kernel<BLK, VD>), g, b, 0, stream, Y, consts, ctrls, N, t_eval, n_eval, Yeval, n_done,
-                                    t_events, max_events); break;
+        case 3: hipLaunchKernelGGL((rk23_sweep_roots_kernel<BLK, VD>), g, b, 0, stream, Y, consts, ctrls, N, t_eval, n_eval, Yeval, n_done,
+                                   t_events, max_events); break;
+        default: hipLaunchKernelGGL((rk23_sweep_term_kernel<BLK, VD>), g, b, 0, stream, Y, consts, ctrls, N, t_eval, n_eval, Yeval, n_done,
+                                    t_events, max_events, lim); break;
     }
 }
 }  // namespace
 
-// blk: 256, 512 or 1024 (anything else: hipErrorInvalidValue, nothing launched)
+// blk: 256, 512 or 1024 (anything else: hipErrorInvalidValue, nothing launched); terminal: the seven limits of kind 4 (host; else NULL)
 RK23_VIS int marl_rk23_launch_sweep(int kind, int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls,
                                     int64_t N, double* Yold, double* Fold, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done,
-                                    double* t_events, int64_t max_events)
+                                    double* t_events, int64_t max_events, const int64_t* terminal)
 {
+    if ((kind == 4) != (terminal != nullptr) || kind < 0 || kind > 4) return (int)hipErrorInvalidValue;
+    TermLimits lim = {};
+    for (int e = 0; terminal && e < 7; e++) lim.k[e] = terminal[e];
     const DevConsts* c = static_cast<const DevConsts*>(consts);
     Rk45Ctrl* k = static_cast<Rk45Ctrl*>(ctrls);
 #define RK23_SWEEP(B)                                                                                                                   \
-    if (vd) launch_sweep_t<B, true>(kind, grid, stream, Y, c, k, N, Yold, Fold, t_eval, n_eval, Yeval, n_done, t_events, max_events);  \
-    else launch_sweep_t<B, false>(kind, grid, stream, Y, c, k, N, Yold, Fold, t_eval, n_eval, Yeval, n_done, t_events, max_events)
+    if (vd) launch_sweep_t<B, true>(kind, grid, stream, Y, c, k, N, Yold, Fold, t_eval, n_eval, Yeval, n_done, t_events, max_events, lim);  \
+    else launch_sweep_t<B, false>(kind, grid, stream, Y, c, k, N, Yold, Fold, t_eval, n_eval, Yeval, n_done, t_events, max_events, lim)
     switch (blk) {
         case 256: RK23_SWEEP(256); break;
         case 512: RK23_SWEEP(512); break;

@@ -5,7 +5,8 @@
 
 namespace marl {
 
-enum : int { ST_DONE = 0, ST_RUNNING = 1, ST_BUDGET = 2, ST_PAUSED = 3, ST_TOO_SMALL = -1 };
+// (ST_TERMINAL: a terminal monitor ended the run, marl_set_terminal - marl_stats.status = 1, scipy's code, which ST_RUNNING occupies here)
+enum : int { ST_DONE = 0, ST_RUNNING = 1, ST_BUDGET = 2, ST_PAUSED = 3, ST_TERMINAL = 4, ST_TOO_SMALL = -1 };
 
 // Device-resident step controller: the scalar state of scipy's RungeKutta._step_impl
 // (rk.py:111-176) plus the driver's event bookkeeping (ivp.py:673-694).  One per instance.

@@ -85,17 +85,20 @@ class HipSweepEngine:
             self._model.use_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
         return self._model
 
-    def integrate_rk45(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64):
+    def integrate_rk45(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
         """y0: (n_local, 5N) host array.  Returns (y_final (n_local, 5N), list of RK45Result).  With ``t_eval`` every result carries
         the samples that instance reached, as a single run's does: ``t`` (n_t,) and ``y`` (5N, n_t).  With ``events`` every result
-        carries ``t_events``, the root times of the seven monitors located inside the sweep (at most ``max_events`` each)."""
-        return self._integrate_rk("sweep_rk45_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events)
+        carries ``t_events``, the root times of the seven monitors located inside the sweep (at most ``max_events`` each).
+        ``terminal`` as for :meth:`integrate_radau`: an instance whose terminal monitor occurs ends at that root inside the sweep
+        kernel (marl_sweep_rk45_terminal_dev) - status 1, ``t_reached`` the root; None: none, whatever an earlier call set."""
+        return self._integrate_rk("sweep_rk45_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
 
-    def integrate_rk23(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64):
-        """:meth:`integrate_rk45` with RK23 (marl_sweep_rk23_dev / _eval_dev / _events_dev): the same arguments and results."""
-        return self._integrate_rk("sweep_rk23_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events)
+    def integrate_rk23(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
+        """:meth:`integrate_rk45` with RK23 (marl_sweep_rk23_dev / _eval_dev / _events_dev / _terminal_dev): the same arguments and results."""
+        return self._integrate_rk("sweep_rk23_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
 
-    def _integrate_rk(self, sweep, y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events):
+    def _integrate_rk(self, sweep, y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal=None):
+        self.model.set_terminal(terminal)
         sweep = getattr(self.model, sweep)
         yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
         more = {"events": True, "max_events": max_events} if events else {}
@@ -247,7 +250,8 @@ def run_sweep_bdf(base_parms, instances, t_span, first_step, rtol, atol, max_att
 
 
 def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64):
+                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64,
+                   terminal=None):
     """Integrate every instance with adaptive RK45; ranks of ``group`` each take a contiguous shard (``balance``: see :func:`assign`).
 
     Returns ``(y_final, status, n_accepted, n_rejected, t_reached)`` - for ALL instances, in their order, when ``gather``,
@@ -259,17 +263,20 @@ def run_sweep_rk45(base_parms, instances, t_span, first_step, rtol, atol, max_at
     ``solve_ivp(..., t_eval=)`` returns (Evolve_scenario.py:104-109) - NaN beyond an instance's ``n_frames``; ordered like the states.
 
     With ``events`` one last element follows: ``t_events``, per instance a list of 7 arrays - the root times of the reference's monitors
-    (Evolve_scenario.py:118-145, 175-177), at most ``max_events`` each, located inside the sweep; ordered like the states."""
+    (Evolve_scenario.py:118-145, 175-177), at most ``max_events`` each, located inside the sweep; ordered like the states.
+
+    ``terminal``: as for :func:`run_sweep_radau` - set for this call only, and handed to the engine only when given."""
     return _run_sweep("integrate_rk45", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, t_eval, events, max_events)
+                      balance, cost, t_eval, events, max_events, terminal=terminal)
 
 
 def run_sweep_rk23(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
-                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64):
+                   device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64,
+                   terminal=None):
     """As :func:`run_sweep_rk45` with adaptive RK23 (scipy's Bogacki-Shampine 3(2) pair; every instance costs about the same, so
-    contiguous shards): the same arguments and the same returned tuple, ``t_eval`` and ``events`` included."""
+    contiguous shards): the same arguments and the same returned tuple, ``t_eval``, ``events`` and ``terminal`` included."""
     return _run_sweep("integrate_rk23", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-                      balance, cost, t_eval, events, max_events)
+                      balance, cost, t_eval, events, max_events, terminal=terminal)
 
 
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
@@ -298,7 +305,7 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
             more |= {"events": True, "max_events": max_events}
         if batched:   # (the BDF driver; passed only when asked for, like `events`)
             more |= {"batched": True}
-        if terminal is not None:   # (the Radau and BDF drivers; passed only when asked for)
+        if terminal is not None:   # (passed only when asked for)
             more |= {"terminal": terminal}
         y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()
