@@ -72,7 +72,8 @@ int marl_synchronize(marl_ctx* ctx);
  * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev,
  * marl_sweep_bdf_terminal_dev, marl_sweep_rk45_terminal_dev / rk23_terminal_dev, marl_integrate_rk45_terminal / rk23_terminal.  Every other
  * integrator entry (marl_integrate_rk45 / rk23, marl_integrate_rk45_dev / rk23_dev, marl_sweep_rk45_dev / _eval_dev / _events_dev and their rk23
- * counterparts, marl_sweep_bdf_dev / _eval_dev / _events_dev, marl_slab_init_control, marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
+ * counterparts, marl_integrate_dop853, marl_sweep_dop853_dev / _eval_dev / _events_dev, marl_sweep_bdf_dev / _eval_dev / _events_dev,
+ * marl_slab_init_control, marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
  * before it touches the state, and is unchanged when none is. */
 int marl_set_terminal(marl_ctx* ctx, const int64_t terminal[7]);
 /* Tuning knobs; unknown names are an error.  See DESIGN.md.
@@ -298,6 +299,36 @@ int marl_sweep_rk23_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double
 int marl_integrate_rk23_terminal(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
                                  const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
                                  int64_t max_attempts, marl_stats* stats);
+
+/* ---- adaptive Dormand-Prince DOP853, grids of one workgroup ------------------------------------------
+ * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="DOP853", first_step=, rtol=, atol=, t_eval=, events=[7 monitors]):
+ * the reference's Solver forwards any solve_ivp method (marlpde/parameters.py:212-213), and DOP853 was the last explicit one that
+ * scipy drove on marl_rhs.  The method is scipy/integrate/_ivp/rk.py, class DOP853 (order 8, error_estimator_order 7, n_stages 12;
+ * coefficients: dop853_coefficients.py) under RungeKutta._step_impl (rk.py:111-176): 12 evaluations per attempt, step factor
+ * 0.9 err^(-1/8), the error norm of DOP853._estimate_error_norm (rk.py:506-518), the dense output of Dop853DenseOutput
+ * (rk.py:520-547, :577-601), whose three extra evaluations scipy counts once per accepted step that has a monitor sign change or a
+ * t_eval sample in it:  nfev = 1 + 12 attempts + 3 (such steps) - also where the roots are not asked for: the monitors are always
+ * watched and counted.  Arguments, results, argument checks, status codes and the t0 == t1 behaviour are those of the RK45 entry of
+ * the same name; messages start with "dop853:".  On these stability-limited equations DOP853 needs about as many evaluations as
+ * RK45: it is here for coverage of the reference's solver switch, not as the cheaper method.
+ * Only grids that fit one workgroup: N > 1024 returns -1, "dop853: ... N <= 1024 ...".  No terminal monitors: -1 with the standard
+ * message while a limit is set (marl_set_terminal), before the state is touched.  No _dev single-run entry, no slab contexts. */
+/* marl_integrate_rk45 with DOP853: one instance, host pointers; t_eval frames and root times come from the sweep kernel that
+ * locates roots (dop853_sweep_roots_kernel) run for one instance - no host in the loop. */
+int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                          const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                          int64_t max_attempts, marl_stats* stats);
+/* marl_sweep_rk45_dev with DOP853 (rk.py, class DOP853; marlpde/parameters.py:212-213) */
+int marl_sweep_dop853_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol,
+                          double atol, int64_t max_attempts, marl_stats* stats);
+/* marl_sweep_rk45_eval_dev with DOP853 (rk.py, class DOP853 and Dop853DenseOutput :577-601; ivp.py:706-723) */
+int marl_sweep_dop853_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                               int64_t* n_done, marl_stats* stats);
+/* marl_sweep_rk45_events_dev with DOP853 (rk.py, class DOP853; roots as ivp.py:673-694, :51-76) */
+int marl_sweep_dop853_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                 int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                                 int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
 
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,

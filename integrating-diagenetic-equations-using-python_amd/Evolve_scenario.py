@@ -9,13 +9,16 @@ reference (Evolve_scenario.py:19) and returns the same tuple
   output) runs on the GPU via ``marl_integrate_rk45``.
 * ``backend == "hip"`` and ``method == "RK23"``: the same loop with scipy's Bogacki-Shampine 3(2) pair (3 RHS evaluations per
   attempt, step factor ``0.9 err^(-1/3)``, cubic dense output) via ``marl_integrate_rk23`` - no scipy in the loop.
+* ``backend == "hip"`` and ``method == "DOP853"`` on a grid of up to 1024 cells, without terminal monitors: scipy's Dormand-Prince
+  8(5,3) (12 evaluations per attempt, step factor ``0.9 err^(-1/8)``, the degree-7 dense output whose 3 extra evaluations scipy
+  counts) via ``marl_integrate_dop853`` - no scipy in the loop.  Larger grids and terminal monitors take the scipy route below.
 * ``backend == "hip"`` and ``method == "Radau"`` (the reference's default, parameters.py:213): scipy's Radau IIA step
   logic restated natively, with the RHS, the finite-difference Jacobian (the reference's 27-diagonal pattern), the
   block-tridiagonal LU factorisations and every vector operation on the GPU via ``marl_integrate_radau`` - no scipy in the loop.
 * ``backend == "hip"`` and ``method == "BDF"``: scipy's BDF step logic restated natively on the same Jacobian /
   factorisation kernels via ``marl_integrate_bdf`` - no scipy in the loop either.
-* ``backend == "hip"`` and any other scipy method (DOP853, LSODA with the reference's ``lband = uband = 1``; or any
-  method with ``solver_parms["scipy_driver"] = True``): scipy's ``solve_ivp`` drives, exactly as in the reference
+* ``backend == "hip"`` and any other scipy method (LSODA with the reference's ``lband = uband = 1``; or any
+  method with ``solver_parms["scipy_driver"] = True``; DOP853 where the native loop does not reach): scipy's ``solve_ivp`` drives, exactly as in the reference
   (:104-109), with the HIP RHS and HIP monitors as callables
   (``test_every_other_method_of_the_reference_solver_runs_through_scipy_on_the_hip_rhs``).
 * other backends: rejected - this package has no CPU implementation.
@@ -98,6 +101,14 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
         t_out, y_out, t_events = res.t, res.y, res.t_events
         nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
         if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the implicit branch)
+            status = -1
+        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+    elif method == "DOP853" and not scipy_driver and N <= 1024 and not any(limits):
+        # the native loop covers grids of one workgroup and no terminal monitors; everything else keeps the scipy route below
+        res = eq.integrate_dop853(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
+        t_out, y_out, t_events = res.t, res.y, res.t_events
+        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
+        if status not in (0, -1):
             status = -1
         covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
     elif method in ("Radau", "BDF") and not scipy_driver:

@@ -386,6 +386,14 @@ class LMAHeureuxPorosityDiff:
         :meth:`integrate_rk45` with Bogacki-Shampine 3(2) - 3 RHS evaluations per attempt, cubic dense output.  Same result."""
         return self._integrate_rk("rk23", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
+    def integrate_dop853(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
+                         max_attempts=0):
+        """scipy ``solve_ivp(method="DOP853")`` semantics for ONE instance, entirely on the device (marl_integrate_dop853):
+        :meth:`integrate_rk45` with Dormand-Prince 8(5,3) - 12 RHS evaluations per attempt, and 3 more for every accepted step with
+        a monitor sign change or a ``t_eval`` sample in it (the dense output's extra stages, which scipy counts).  Same result.
+        Grids of up to 1024 cells only, and no terminal monitors: both are refused with a :class:`MarlError`."""
+        return self._integrate_rk("dop853", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
     def integrate_rk45_terminal(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
                                 max_attempts=0):
         """:meth:`integrate_rk45` honouring terminal monitors (:meth:`set_terminal`; marl_integrate_rk45_terminal): the run ends at
@@ -709,11 +717,20 @@ class LMAHeureuxPorosityDiff:
         """:meth:`sweep_rk45_device` with RK23 (marl_sweep_rk23_dev / _eval_dev / _events_dev): the same arguments and results."""
         return self._sweep_rk_device("rk23", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events)
 
-    def _sweep_rk_device(self, method, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events):
+    def sweep_dop853_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
+                            events=False, max_events=64):
+        """:meth:`sweep_rk45_device` with DOP853 (marl_sweep_dop853_dev / _eval_dev / _events_dev): the same arguments and results;
+        ``nfev`` counts 12 per attempt and 3 per accepted step with a monitor sign change or a sample in it.  There is no terminal
+        entry: while a monitor is terminal (:meth:`set_terminal`) the entries refuse the call, and so does this method."""
+        return self._sweep_rk_device("dop853", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events,
+                                     terminal_entry=False)
+
+    def _sweep_rk_device(self, method, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events,
+                         terminal_entry=True):
         plain, with_eval, with_events = (f"marl_sweep_{method}_dev", f"marl_sweep_{method}_eval_dev", f"marl_sweep_{method}_events_dev")
         stats = (MarlStats * self.n_instances)()
         locate = bool(events) and int(max_events) > 0
-        if any(self.terminal):
+        if terminal_entry and any(self.terminal):
             entry = f"marl_sweep_{method}_terminal_dev"
             te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
             if te.size and not y_eval_dev_ptr:

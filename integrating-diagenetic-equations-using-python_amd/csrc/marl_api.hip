@@ -80,6 +80,9 @@ struct marl_ctx {
     // sweeps that locate the monitors' roots (rk45_sweep_roots_kernel): the root times [batch][7][max_events], allocated on first use or growth
     double* sw_tev = nullptr;
     size_t sw_tev_cap = 0;
+    // DOP853 sweeps (marl_dop853.h): the stage derivatives of every instance, [batch][16][5][window]; allocated on first use or growth
+    double* dop_k = nullptr;
+    size_t dop_k_cap = 0;
     // domain decomposition: this rank's message / the gathered messages (device), and the RCCL communicator (dlopen'ed API)
     double* dd_send = nullptr;
     double* dd_gathered = nullptr;
@@ -368,6 +371,7 @@ void marl_ctx_destroy(marl_ctx* ctx)
     if (ctx->sw_teval) (void)hipFree(ctx->sw_teval);
     if (ctx->sw_ndone) (void)hipFree(ctx->sw_ndone);
     if (ctx->sw_tev) (void)hipFree(ctx->sw_tev);
+    if (ctx->dop_k) (void)hipFree(ctx->dop_k);
     if (ctx->rccl_comm && ctx->rccl_destroy) (void)ctx->rccl_destroy(ctx->rccl_comm);
     if (ctx->dd_send) (void)hipFree(ctx->dd_send);
     if (ctx->dd_gathered) (void)hipFree(ctx->dd_gathered);
@@ -1657,6 +1661,94 @@ int marl_integrate_rk23_terminal(marl_ctx* ctx, double* y, double t0, double t1,
     return integrate_rk(kRk23, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats, true);
 }
 
+
+// ---- DOP853: grids of one workgroup only (include/marl_hip.h; kernels: marl_dop853.h, a translation unit of its own) ----
+}  // extern "C"
+extern "C" {
+int64_t marl_dop853_arena_doubles(int64_t grid, int blk);
+int marl_dop853_launch_sweep(int kind, int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls, int64_t N,
+                             double* karena, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events,
+                             int64_t max_events);
+}
+static int dop853_m_sweep(marl_ctx* ctx, int kind, int blk, unsigned batch, const SweepLaunch& a)
+{
+    if (kind != SWEEP_PLAIN && kind != SWEEP_EVAL && kind != SWEEP_ROOTS) return fail(ctx, -1, "dop853: no kernel of kind %d", kind);
+    if (int rc = grow_dev(ctx, &ctx->dop_k, &ctx->dop_k_cap, (size_t)marl_dop853_arena_doubles((int64_t)batch, blk))) return rc;
+    const int err = marl_dop853_launch_sweep(kind, blk, ctx->var_dphi ? 1 : 0, batch, ctx->stream, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, ctx->dop_k,
+                                             a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events);
+    if (err != (int)hipSuccess) return fail(ctx, -3, "dop853: kernel launch failed: %s", hipGetErrorString((hipError_t)err));
+    return 0;
+}
+// (only the one-workgroup kernels exist: sweep_rk is the one driver, single runs included)
+static const RkMethod kDop853 = {"dop853", "marl_sweep_dop853_dev", 0, false, dop853_m_sweep, nullptr, nullptr, nullptr, nullptr};
+
+// what every DOP853 entry refuses before it touches anything: terminal monitors, grids above one workgroup, slabs
+static int dop853_refuse(marl_ctx* ctx, const char* entry)
+{
+    NO_TERMINAL(ctx, entry)
+    if (ctx->N > 1024)
+        return fail(ctx, -1, "dop853: N = %lld: the native DOP853 loop runs grids of one workgroup only, N <= 1024 cells (%s)", (long long)ctx->N, entry);
+    if (ctx->halo > 0) return fail(ctx, -1, "dop853: slab contexts (domain decomposition) are not supported");
+    return 0;
+}
+
+extern "C" {
+int marl_sweep_dop853_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                          int64_t max_attempts, marl_stats* stats)
+{
+    if (ctx)
+        if (int rc = dop853_refuse(ctx, "marl_sweep_dop853_dev")) return rc;
+    return sweep_rk(kDop853, "marl_sweep_dop853_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, nullptr, 0, nullptr, nullptr, nullptr, 0, stats);
+}
+
+int marl_sweep_dop853_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                               marl_stats* stats)
+{
+    if (ctx)
+        if (int rc = dop853_refuse(ctx, "marl_sweep_dop853_eval_dev")) return rc;
+    return sweep_rk(kDop853, "marl_sweep_dop853_eval_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    nullptr, 0, stats);
+}
+
+int marl_sweep_dop853_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                                 int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                                 double* t_events, int64_t max_events, marl_stats* stats)
+{
+    if (ctx)
+        if (int rc = dop853_refuse(ctx, "marl_sweep_dop853_events_dev")) return rc;
+    return sweep_rk(kDop853, "marl_sweep_dop853_events_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    t_events, max_events, stats);
+}
+
+// One instance, host pointers: the sweep that locates roots, for an instance count of one - frames and root times are written by the
+// kernel, the host only moves them.
+int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                          const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                          int64_t max_attempts, marl_stats* stats)
+{
+    if (!ctx || !y || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_dop853: invalid argument") : -1;
+    if (int rc = dop853_refuse(ctx, "marl_integrate_dop853")) return rc;
+    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_dop853: single-instance context required (use marl_sweep_dop853_dev)");
+    if (int rc = check_ivp_args(ctx, "dop853", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)NF * ctx->N;
+    if (int rc = ensure(ctx, 0, n)) return rc;
+    HIP_OK(ctx, hipMemcpyAsync(ctx->buf[0], y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    double* yev = nullptr;
+    if (n_eval > 0) HIP_OK(ctx, hipMalloc((void**)&yev, sizeof(double) * n * (size_t)n_eval));
+    const bool roots = t_events != nullptr && max_events > 0;
+    int64_t n_done = 0;
+    int rc = sweep_rk(kDop853, "marl_integrate_dop853", ctx, ctx->buf[0], t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, yev, &n_done,
+                      roots ? t_events : nullptr, roots ? max_events : 0, stats);
+    if (rc == 0 && n_done > 0 && hipMemcpyAsync(y_eval, yev, sizeof(double) * n * (size_t)n_done, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = fail(ctx, -3, "copy of t_eval samples failed");
+    if (rc == 0 && hipMemcpyAsync(y, ctx->buf[0], n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = fail(ctx, -3, "copy of final state failed");
+    if (rc == 0 && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, -3, "sync failed");
+    if (yev) (void)hipFree(yev);
+    return rc;
+}
 
 // ---- domain decomposition building blocks --------------------------------------------------------
 int marl_ctx_create_slab(const marl_params* params, int64_t N_global, int64_t g_begin, int64_t g_end, int64_t halo, int device,

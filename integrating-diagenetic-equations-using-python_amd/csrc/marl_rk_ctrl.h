@@ -1,5 +1,5 @@
-// marl_rk_ctrl.h - the step controller record of the explicit adaptive Runge-Kutta loops (RK45, RK23) and their status codes.
-// Plain data and nothing but <stdint.h>: marl_kernels.h (device) and marl_rk23_ctl.h (host-compilable) share it.
+// marl_rk_ctrl.h - the step controller record of the explicit adaptive Runge-Kutta loops (RK45, RK23, DOP853) and their status codes.
+// Plain data and nothing but <stdint.h>: marl_kernels.h (device) and marl_rk23_ctl.h / marl_dop853_ctl.h (host-compilable) share it.
 #pragma once
 #include <stdint.h>
 

@@ -97,6 +97,11 @@ class HipSweepEngine:
         """:meth:`integrate_rk45` with RK23 (marl_sweep_rk23_dev / _eval_dev / _events_dev / _terminal_dev): the same arguments and results."""
         return self._integrate_rk("sweep_rk23_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
 
+    def integrate_dop853(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
+        """:meth:`integrate_rk45` with DOP853 (marl_sweep_dop853_dev / _eval_dev / _events_dev; N <= 1024): the same arguments and
+        results.  There is no terminal entry: with ``terminal`` set the sweep is refused (:class:`marlpde_amd._abi.MarlError`)."""
+        return self._integrate_rk("sweep_dop853_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
+
     def _integrate_rk(self, sweep, y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal=None):
         self.model.set_terminal(terminal)
         sweep = getattr(self.model, sweep)
@@ -276,6 +281,16 @@ def run_sweep_rk23(base_parms, instances, t_span, first_step, rtol, atol, max_at
     """As :func:`run_sweep_rk45` with adaptive RK23 (scipy's Bogacki-Shampine 3(2) pair; every instance costs about the same, so
     contiguous shards): the same arguments and the same returned tuple, ``t_eval``, ``events`` and ``terminal`` included."""
     return _run_sweep("integrate_rk23", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
+                      balance, cost, t_eval, events, max_events, terminal=terminal)
+
+
+def run_sweep_dop853(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
+                     device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False, max_events=64,
+                     terminal=None):
+    """As :func:`run_sweep_rk45` with adaptive DOP853 (scipy's Dormand-Prince 8(5,3); grids of up to 1024 cells): the same arguments
+    and the same returned tuple, ``t_eval`` and ``events`` included.  ``terminal`` is handed on and refused by the entries, which
+    cannot stop at a monitor's root."""
+    return _run_sweep("integrate_dop853", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
                       balance, cost, t_eval, events, max_events, terminal=terminal)
 
 
