@@ -70,7 +70,8 @@ int marl_synchronize(marl_ctx* ctx);
  * In such a step the roots of ALL active monitors are located (the order needs them), with or without a free slot and also when the
  * caller passed no t_events; they are stored only where a slot is free.  A step that meets no limit runs exactly as without limits.
  * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev,
- * marl_sweep_bdf_terminal_dev, marl_sweep_rk45_terminal_dev / rk23_terminal_dev, marl_integrate_rk45_terminal / rk23_terminal.  Every other
+ * marl_sweep_bdf_terminal_dev, marl_sweep_rk45_terminal_dev / rk23_terminal_dev, marl_integrate_rk45_terminal / rk23_terminal,
+ * marl_sweep_dop853_stop_dev, marl_integrate_dop853_stop.  Every other
  * integrator entry (marl_integrate_rk45 / rk23, marl_integrate_rk45_dev / rk23_dev, marl_sweep_rk45_dev / _eval_dev / _events_dev and their rk23
  * counterparts, marl_integrate_dop853, marl_sweep_dop853_dev / _eval_dev / _events_dev, marl_sweep_bdf_dev / _eval_dev / _events_dev,
  * marl_slab_init_control, marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
@@ -311,8 +312,9 @@ int marl_integrate_rk23_terminal(marl_ctx* ctx, double* y, double t0, double t1,
  * watched and counted.  Arguments, results, argument checks, status codes and the t0 == t1 behaviour are those of the RK45 entry of
  * the same name; messages start with "dop853:".  On these stability-limited equations DOP853 needs about as many evaluations as
  * RK45: it is here for coverage of the reference's solver switch, not as the cheaper method.
- * Only grids that fit one workgroup: N > 1024 returns -1, "dop853: ... N <= 1024 ...".  No terminal monitors: -1 with the standard
- * message while a limit is set (marl_set_terminal), before the state is touched.  No _dev single-run entry, no slab contexts. */
+ * Only grids that fit one workgroup: N > 1024 returns -1, "dop853: ... N <= 1024 ...".  Terminal monitors: the four entries below
+ * return -1 with the standard message while a limit is set (marl_set_terminal), before the state is touched; the two _stop entries
+ * after them honour the limits.  No _dev single-run entry, no slab contexts. */
 /* marl_integrate_rk45 with DOP853: one instance, host pointers; t_eval frames and root times come from the sweep kernel that
  * locates roots (dop853_sweep_roots_kernel) run for one instance - no host in the loop. */
 int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
@@ -329,6 +331,23 @@ int marl_sweep_dop853_eval_dev(marl_ctx* ctx, double* y_dev, double t0, double t
 int marl_sweep_dop853_events_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
                                  int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
                                  int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* marl_sweep_dop853_events_dev honouring terminal monitors (marl_set_terminal; the arguments of marl_sweep_rk45_terminal_dev).  With a
+ * limit set the sweep is one launch of dop853_sweep_stop_kernel, whatever else was asked for: t_eval may be NULL with n_eval = 0 and
+ * t_events NULL with max_events = 0.  An instance whose monitor meets its limit ends at that root inside the kernel: all roots of that
+ * step are located by probe replays of the step, the rule is applied once, the samples up to t_stop are written, and one more replay
+ * of the step with the weights of t_stop becomes the state (the STOP trip, csrc/marl_dop853.h).  nfev counts nothing for the stop: the
+ * sign change has counted the step's dense output.  Every step that meets no limit is a step of marl_sweep_dop853_events_dev.  With
+ * no limit set the call is marl_sweep_dop853_dev / _eval_dev / _events_dev, whichever the arguments ask for, bit for bit.
+ * N > 1024 and slab contexts are refused as above. */
+int marl_sweep_dop853_stop_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev,
+                               int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats);
+/* marl_integrate_dop853 honouring terminal monitors (the arguments of marl_integrate_rk45_terminal): the sweep above run for one
+ * instance.  A run that a monitor ends: stats->status = 1, stats->t = t_stop, y the state at t_stop, y_eval the samples up to t_stop.
+ * With no limit set it is marl_integrate_dop853. */
+int marl_integrate_dop853_stop(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                               const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                               int64_t max_attempts, marl_stats* stats);
 
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,

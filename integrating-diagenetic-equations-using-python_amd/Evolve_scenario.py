@@ -63,7 +63,8 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     """``terminal``: the reference's switch (LHeureux_model.py:113-122) - which monitors end the run at their root, as
     :func:`marlpde_amd.LHeureux_model.terminal_counts` reads it.  Native for Radau and BDF; for RK45 / RK23 the solver parameters
     choose: ``native_terminal=True`` - the native loop stops itself (marl_integrate_rk45_terminal / rk23_terminal) - or
-    ``scipy_driver=True`` - solve_ivp drives the HIP RHS."""
+    ``scipy_driver=True`` - solve_ivp drives the HIP RHS.  DOP853 with a terminal monitor: ``native_terminal=True`` and N <= 1024 - the
+    native loop stops itself (marl_integrate_dop853_stop); otherwise solve_ivp drives the HIP RHS, as it does without the switch."""
     limits = terminal_counts(terminal)
     solver_parms = dict(solver_parms)
     Xstar, Tstar = pde_parms["Xstar"], pde_parms["Tstar"]
@@ -104,11 +105,21 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
             status = -1
         covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
     elif method == "DOP853" and not scipy_driver and N <= 1024 and not any(limits):
-        # the native loop covers grids of one workgroup and no terminal monitors; everything else keeps the scipy route below
+        # the native loop covers grids of one workgroup; with a terminal monitor it is opt-in (the next branch), and everything else
+        # keeps the scipy route below
         res = eq.integrate_dop853(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
         t_out, y_out, t_events = res.t, res.y, res.t_events
         nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
         if status not in (0, -1):
+            status = -1
+        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+    elif method == "DOP853" and not scipy_driver and N <= 1024 and native_terminal:
+        # a terminal monitor and native_terminal=True: the native loop stops itself (marl_integrate_dop853_stop)
+        eq.set_terminal(limits)
+        res = eq.integrate_dop853_stop(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
+        t_out, y_out, t_events = res.t, res.y, res.t_events
+        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
+        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the RK45 branch)
             status = -1
         covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
     elif method in ("Radau", "BDF") and not scipy_driver:

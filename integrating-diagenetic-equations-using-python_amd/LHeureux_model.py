@@ -391,7 +391,8 @@ class LMAHeureuxPorosityDiff:
         """scipy ``solve_ivp(method="DOP853")`` semantics for ONE instance, entirely on the device (marl_integrate_dop853):
         :meth:`integrate_rk45` with Dormand-Prince 8(5,3) - 12 RHS evaluations per attempt, and 3 more for every accepted step with
         a monitor sign change or a ``t_eval`` sample in it (the dense output's extra stages, which scipy counts).  Same result.
-        Grids of up to 1024 cells only, and no terminal monitors: both are refused with a :class:`MarlError`."""
+        Grids of up to 1024 cells only, and no terminal monitors: both are refused with a :class:`MarlError`
+        (:meth:`integrate_dop853_stop` is the run that stops at a terminal monitor's root)."""
         return self._integrate_rk("dop853", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
     def integrate_rk45_terminal(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
@@ -406,6 +407,14 @@ class LMAHeureuxPorosityDiff:
                                 max_attempts=0):
         """:meth:`integrate_rk45_terminal` with RK23 (marl_integrate_rk23_terminal)."""
         return self._integrate_rk("rk23_terminal", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
+    def integrate_dop853_stop(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
+                              max_attempts=0):
+        """:meth:`integrate_dop853` honouring terminal monitors (:meth:`set_terminal`; marl_integrate_dop853_stop): the signature and
+        the result of :meth:`integrate_rk45_terminal` - the run ends at the terminal monitor's root with ``status`` 1, ``t_reached``
+        = the root, ``y_final`` the step's dense output there, ``t`` / ``y`` the samples up to it and ``t_events`` the roots up to
+        and including it; ``events=False`` stops all the same.  Without a terminal monitor the same run as :meth:`integrate_dop853`."""
+        return self._integrate_rk("dop853_stop", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
     def _integrate_rk(self, method, y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts):
         entry = getattr(self._lib, f"marl_integrate_{method}")
@@ -720,18 +729,32 @@ class LMAHeureuxPorosityDiff:
     def sweep_dop853_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
                             events=False, max_events=64):
         """:meth:`sweep_rk45_device` with DOP853 (marl_sweep_dop853_dev / _eval_dev / _events_dev): the same arguments and results;
-        ``nfev`` counts 12 per attempt and 3 per accepted step with a monitor sign change or a sample in it.  There is no terminal
-        entry: while a monitor is terminal (:meth:`set_terminal`) the entries refuse the call, and so does this method."""
+        ``nfev`` counts 12 per attempt and 3 per accepted step with a monitor sign change or a sample in it.  These entries do not
+        stop: while a monitor is terminal (:meth:`set_terminal`) they refuse the call, and so does this method
+        (:meth:`sweep_dop853_stop_device` is the sweep that stops)."""
         return self._sweep_rk_device("dop853", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events,
                                      terminal_entry=False)
 
+    def sweep_dop853_stop_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
+                                 events=False, max_events=64):
+        """:meth:`sweep_dop853_device` honouring terminal monitors: while a monitor is terminal (:meth:`set_terminal`) the sweep runs
+        through marl_sweep_dop853_stop_dev - an instance whose terminal monitor occurs ends at that root inside the sweep kernel with
+        ``status`` 1, ``t_reached`` = the root and the state there, as :meth:`sweep_rk45_device` describes it; the results are built
+        the same way, with or without ``t_eval`` and ``events``.  While none is, it is :meth:`sweep_dop853_device`."""
+        if not any(self.terminal):
+            return self.sweep_dop853_device(y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events)
+        return self._sweep_rk_device("dop853", y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events,
+                                     terminal_entry="marl_sweep_dop853_stop_dev")
+
     def _sweep_rk_device(self, method, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts, t_eval, y_eval_dev_ptr, events, max_events,
                          terminal_entry=True):
+        """``terminal_entry``: the entry that honours terminal monitors, taken while one is set - True: marl_sweep_<method>_terminal_dev;
+        a name: that entry; False: the method has none here, and its other entries refuse the call."""
         plain, with_eval, with_events = (f"marl_sweep_{method}_dev", f"marl_sweep_{method}_eval_dev", f"marl_sweep_{method}_events_dev")
         stats = (MarlStats * self.n_instances)()
         locate = bool(events) and int(max_events) > 0
         if terminal_entry and any(self.terminal):
-            entry = f"marl_sweep_{method}_terminal_dev"
+            entry = terminal_entry if isinstance(terminal_entry, str) else f"marl_sweep_{method}_terminal_dev"
             te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
             if te.size and not y_eval_dev_ptr:
                 raise ValueError(f"sweep_{method}_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")

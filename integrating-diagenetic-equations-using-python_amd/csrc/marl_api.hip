@@ -1669,23 +1669,31 @@ int64_t marl_dop853_arena_doubles(int64_t grid, int blk);
 int marl_dop853_launch_sweep(int kind, int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls, int64_t N,
                              double* karena, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events,
                              int64_t max_events);
+// marl_dop853_stop.hip: the kernel that stops at a terminal monitor's root (SWEEP_TERM), a unit of its own
+int marl_dop853_stop_launch(int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls, int64_t N, double* karena,
+                            const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done, double* t_events, int64_t max_events,
+                            const int64_t* terminal);
 }
 static int dop853_m_sweep(marl_ctx* ctx, int kind, int blk, unsigned batch, const SweepLaunch& a)
 {
-    if (kind != SWEEP_PLAIN && kind != SWEEP_EVAL && kind != SWEEP_ROOTS) return fail(ctx, -1, "dop853: no kernel of kind %d", kind);
+    if (kind != SWEEP_PLAIN && kind != SWEEP_EVAL && kind != SWEEP_ROOTS && kind != SWEEP_TERM) return fail(ctx, -1, "dop853: no kernel of kind %d", kind);
     if (int rc = grow_dev(ctx, &ctx->dop_k, &ctx->dop_k_cap, (size_t)marl_dop853_arena_doubles((int64_t)batch, blk))) return rc;
-    const int err = marl_dop853_launch_sweep(kind, blk, ctx->var_dphi ? 1 : 0, batch, ctx->stream, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, ctx->dop_k,
-                                             a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events);
+    const int err = kind == SWEEP_TERM
+                        ? marl_dop853_stop_launch(blk, ctx->var_dphi ? 1 : 0, batch, ctx->stream, a.Y, ctx->dconsts, ctx->dctrl, ctx->N, ctx->dop_k,
+                                                  a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events, a.terminal)
+                        : marl_dop853_launch_sweep(kind, blk, ctx->var_dphi ? 1 : 0, batch, ctx->stream, a.Y, ctx->dconsts, ctx->dctrl, ctx->N,
+                                                   ctx->dop_k, a.t_eval, a.n_eval, a.Yeval, a.n_done, a.t_events, a.max_events);
     if (err != (int)hipSuccess) return fail(ctx, -3, "dop853: kernel launch failed: %s", hipGetErrorString((hipError_t)err));
     return 0;
 }
 // (only the one-workgroup kernels exist: sweep_rk is the one driver, single runs included)
 static const RkMethod kDop853 = {"dop853", "marl_sweep_dop853_dev", 0, false, dop853_m_sweep, nullptr, nullptr, nullptr, nullptr};
 
-// what every DOP853 entry refuses before it touches anything: terminal monitors, grids above one workgroup, slabs
-static int dop853_refuse(marl_ctx* ctx, const char* entry)
+// what every DOP853 entry refuses before it touches anything: terminal monitors (but for the entries that stop: terminal_ok), grids
+// above one workgroup, slabs
+static int dop853_refuse(marl_ctx* ctx, const char* entry, bool terminal_ok = false)
 {
-    NO_TERMINAL(ctx, entry)
+    if (!terminal_ok) { NO_TERMINAL(ctx, entry) }
     if (ctx->N > 1024)
         return fail(ctx, -1, "dop853: N = %lld: the native DOP853 loop runs grids of one workgroup only, N <= 1024 cells (%s)", (long long)ctx->N, entry);
     if (ctx->halo > 0) return fail(ctx, -1, "dop853: slab contexts (domain decomposition) are not supported");
@@ -1721,15 +1729,28 @@ int marl_sweep_dop853_events_dev(marl_ctx* ctx, double* y_dev, double t0, double
                     t_events, max_events, stats);
 }
 
-// One instance, host pointers: the sweep that locates roots, for an instance count of one - frames and root times are written by the
-// kernel, the host only moves them.
-int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
-                          const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
-                          int64_t max_attempts, marl_stats* stats)
+// marl_sweep_dop853_events_dev honouring terminal monitors: with a limit set one launch of dop853_sweep_stop_kernel, whatever else was
+// asked for; with none the dispatch of the three entries above
+int marl_sweep_dop853_stop_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,
+                               int64_t max_attempts, const double* t_eval, int64_t n_eval, double* y_eval_dev, int64_t* n_done,
+                               double* t_events, int64_t max_events, marl_stats* stats)
 {
-    if (!ctx || !y || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "marl_integrate_dop853: invalid argument") : -1;
-    if (int rc = dop853_refuse(ctx, "marl_integrate_dop853")) return rc;
-    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_dop853: single-instance context required (use marl_sweep_dop853_dev)");
+    if (ctx)
+        if (int rc = dop853_refuse(ctx, "marl_sweep_dop853_stop_dev", true)) return rc;
+    return sweep_rk(kDop853, "marl_sweep_dop853_stop_dev", ctx, y_dev, t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, y_eval_dev, n_done,
+                    t_events, max_events, stats, true);
+}
+}  // extern "C"
+
+// One instance, host pointers: the sweep that locates roots, for an instance count of one - frames and root times are written by the
+// kernel, the host only moves them.  terminal_ok: marl_integrate_dop853_stop, the sweep that stops.
+static int integrate_dop853(const char* entry, bool terminal_ok, marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol,
+                            double atol, const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                            int64_t max_attempts, marl_stats* stats)
+{
+    if (!ctx || !y || !stats || n_eval < 0 || (n_eval > 0 && (!t_eval || !y_eval))) return ctx ? fail(ctx, -1, "%s: invalid argument", entry) : -1;
+    if (int rc = dop853_refuse(ctx, entry, terminal_ok)) return rc;
+    if (ctx->batch != 1) return fail(ctx, -1, "%s: single-instance context required (use marl_sweep_dop853_dev)", entry);
     if (int rc = check_ivp_args(ctx, "dop853", t0, t1, first_step, rtol, atol, t_eval, n_eval)) return rc;
     HIP_OK(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)NF * ctx->N;
@@ -1739,8 +1760,8 @@ int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double
     if (n_eval > 0) HIP_OK(ctx, hipMalloc((void**)&yev, sizeof(double) * n * (size_t)n_eval));
     const bool roots = t_events != nullptr && max_events > 0;
     int64_t n_done = 0;
-    int rc = sweep_rk(kDop853, "marl_integrate_dop853", ctx, ctx->buf[0], t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, yev, &n_done,
-                      roots ? t_events : nullptr, roots ? max_events : 0, stats);
+    int rc = sweep_rk(kDop853, entry, ctx, ctx->buf[0], t0, t1, first_step, rtol, atol, max_attempts, t_eval, n_eval, yev, &n_done,
+                      roots ? t_events : nullptr, roots ? max_events : 0, stats, terminal_ok);
     if (rc == 0 && n_done > 0 && hipMemcpyAsync(y_eval, yev, sizeof(double) * n * (size_t)n_done, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         rc = fail(ctx, -3, "copy of t_eval samples failed");
     if (rc == 0 && hipMemcpyAsync(y, ctx->buf[0], n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
@@ -1748,6 +1769,25 @@ int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double
     if (rc == 0 && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, -3, "sync failed");
     if (yev) (void)hipFree(yev);
     return rc;
+}
+
+extern "C" {
+int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                          const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                          int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_dop853("marl_integrate_dop853", false, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events,
+                            max_attempts, stats);
+}
+
+// marl_integrate_dop853 honouring terminal monitors: the run ends at the terminal monitor's root (stats->status 1, stats->t the root,
+// y the state there, y_eval the samples up to it); without a limit it is marl_integrate_dop853
+int marl_integrate_dop853_stop(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                               const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                               int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_dop853("marl_integrate_dop853_stop", true, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events,
+                            max_attempts, stats);
 }
 
 // ---- domain decomposition building blocks --------------------------------------------------------

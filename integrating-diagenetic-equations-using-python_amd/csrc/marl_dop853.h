@@ -27,13 +27,20 @@
 //   * nfev: 12 per attempt, and 3 more for every accepted step with a monitor sign change or a sample in it
 //     (dop853_count_dense_output) - what solve_ivp(method="DOP853", events=<the seven monitors>, t_eval=...) reports.
 //
-// Every loop ends on its own: a NaN error norm is a rejection with MIN_FACTOR until the step falls below 10 ulp(t) (ST_TOO_SMALL),
-// max_attempts gives ST_BUDGET, Brent's iteration is capped at 100 as everywhere, and the samples of a step are finitely many.
+//   * Terminal monitors (TERM; dop853_sweep_stop_kernel): a fourth trip kind, the STOP - one more replay of the step that ends the run,
+//     at the terminal monitor's root, whose result becomes the state - and a stop record in LDS that only that kernel has
+//     (marl_dop853_stop.h; see dop853_control).  Without TERM the body is what it was, instruction for instruction.
 //
-// Compiled as its own translation unit (marl_dop853.hip), which leaves the code generation of the other units alone.
+// Every loop ends on its own: a NaN error norm is a rejection with MIN_FACTOR until the step falls below 10 ulp(t) (ST_TOO_SMALL),
+// max_attempts gives ST_BUDGET, Brent's iteration is capped at 100 as everywhere (for each of at most seven monitors), the samples of
+// a step are finitely many, and the STOP trip leaves the loop.
+//
+// Compiled as two translation units: marl_dop853.hip (the plain, eval and roots kernels) and marl_dop853_stop.hip (the stop kernel),
+// which leaves the code generation of the other units, and of each other, alone.
 #pragma once
 #include "marl_kernels.h"
 #include "marl_dop853_ctl.h"
+#include "marl_dop853_stop.h"
 
 namespace marl {
 
@@ -44,14 +51,16 @@ static_assert(dop853::N_STAGES % DOP853_BATCH == 0, "the error sums walk K_1..K_
 // doubles of the arena of `batch` instances at a BLK-thread window
 __host__ __device__ constexpr int64_t dop853_arena_doubles(int64_t batch, int blk) { return batch * DOP853_SLOTS * NF * blk; }
 
-enum : int { DOP853_ATTEMPT = 0, DOP853_SAMPLE = 1, DOP853_PROBE = 2 };
+enum : int { DOP853_ATTEMPT = 0, DOP853_SAMPLE = 1, DOP853_PROBE = 2, DOP853_STOP = 3 };
+static_assert(DOP853_NEXT_SAMPLE == DOP853_SAMPLE && DOP853_NEXT_PROBE == DOP853_PROBE && DOP853_NEXT_STOP == DOP853_STOP,
+              "dop853_stop_next (marl_dop853_stop.h) answers in trip kinds");
 
 // What thread 0 asks of the next trip of the loop (LDS; read by every thread behind a barrier).
 struct Dop853Trip {
     double h;          // the step: h_try of an attempt, h_prev of a replay
     double w[16];      // replay: the dense-output weights at its abscissa
     int64_t ie;        // SAMPLE: the frame to write
-    int32_t kind;      // DOP853_*
+    int32_t kind;      // DOP853_* (DOP853_STOP: the stop kernel only)
     int32_t at_start;  // replay at t_old itself: the result is y_old, whatever 0 * K_j gives
     int32_t commit;    // first: y <- y_new, K_1 <- K_13 (the step accepted before is complete)
     int32_t leave;     // then: leave the loop
@@ -67,6 +76,10 @@ struct Dop853Walk {
     BrentState bs;
 };
 struct Dop853Record { double q[NQ]; double s3; };   // the reduced record of a trip: {sum (err5 / scale)^2, monitors}, sum (err3 / scale)^2
+// TERM: what thread 0's functions get beside the walk - the stop record (Dop853Stop, marl_dop853_stop.h; LDS of the stop kernel).
+// Without TERM there is nothing to hand over: an empty argument, which costs the three older kernels no register and no instruction.
+template <bool TERM> struct Dop853StopRef {};
+template <> struct Dop853StopRef<true> { Dop853Stop* rec; };
 
 // the next trip replays the step just accepted at time tp
 __device__ __forceinline__ void dop853_replay_at(Rk45Ctrl& sc, Dop853Trip& trip, Dop853Walk& st, int kind, double tp)
@@ -86,9 +99,11 @@ __device__ __forceinline__ void dop853_replay_at(Rk45Ctrl& sc, Dop853Trip& trip,
 }
 
 // what follows in the step just accepted: roots (Brent on the lowest monitor of ev_mask over [t_old, t]: f(a) first), then samples,
-// then the commit and the next attempt - or the way out
-template <bool EVAL, bool ROOTS>
-__device__ __forceinline__ void dop853_schedule(Rk45Ctrl& sc, Dop853Trip& trip, Dop853Walk& st, const double* __restrict__ t_eval, int64_t n_eval)
+// then the commit and the next attempt - or the way out.  TERM, in a step that ends the run (its roots located and the rule applied:
+// DOP853_STOP_SAMPLES): the samples up to t_stop, then the STOP trip - no commit, no further attempt.
+template <bool EVAL, bool ROOTS, bool TERM = false>
+__device__ __forceinline__ void dop853_schedule(Rk45Ctrl& sc, Dop853Trip& trip, Dop853Walk& st, const double* __restrict__ t_eval, int64_t n_eval,
+                                                Dop853StopRef<TERM> stop = {})
 {
     if constexpr (ROOTS) {
         if (st.ev_mask != 0) {
@@ -96,6 +111,17 @@ __device__ __forceinline__ void dop853_schedule(Rk45Ctrl& sc, Dop853Trip& trip, 
             st.br_phase = 1;
             st.br_iter = 0;
             dop853_replay_at(sc, trip, st, DOP853_PROBE, sc.t_old);
+            return;
+        }
+    }
+    if constexpr (TERM) {
+        if (stop.rec->stage == DOP853_STOP_SAMPLES) {
+            if (dop853_stop_next(*stop.rec, st.ie, n_eval, t_eval) == DOP853_NEXT_SAMPLE) {
+                dop853_replay_at(sc, trip, st, DOP853_SAMPLE, t_eval[st.ie]);
+                trip.ie = st.ie;
+            } else {
+                dop853_replay_at(sc, trip, st, DOP853_STOP, stop.rec->t_stop);
+            }
             return;
         }
     }
@@ -118,10 +144,31 @@ __device__ __forceinline__ void dop853_schedule(Rk45Ctrl& sc, Dop853Trip& trip, 
 // Thread 0 between the barriers of two trips: the trip of kind `kind` has left the record r; decide (an attempt), advance Brent's method
 // (a probe) or the sample counter, and write the next trip.  A function of its own, not inlined: its registers (pow, the 16 x 7 weights)
 // are thread 0's business and stay out of the stage loop's allocation.  tev: this instance's root times [7][max_events].
-template <bool EVAL, bool ROOTS>
+//   TERM (the marl_set_terminal block of include/marl_hip.h, as rk45_sweep_body<TERM> carries it out; the walk: marl_dop853_stop.h):
+//   an accepted attempt in which a monitor that changed sign meets its limit books nothing of its monitors - sc.g and the counts stay -
+//   and sends ALL monitors that changed sign through the probes, slot or no slot, tev or none; their roots stay in the stop record.
+//   Behind the last of them rk_terminal_step speaks once: the kept monitors are booked as rk45_events books them and their roots stored
+//   where a slot is free, the dropped ones never happened.  The samples up to t_stop follow, then the STOP trip, whose record holds the
+//   monitors of the state at t_stop: sc.g, sc.t = t_stop, ST_TERMINAL, and the loop is left without a commit.  The attempt that was
+//   prepared after the accepted step is never made (attempts--).  nfev: the sign change counted the step's dense output already.
+template <bool EVAL, bool ROOTS, bool TERM = false>
 __device__ __noinline__ void dop853_control(Rk45Ctrl& sc, Dop853Trip& trip, Dop853Walk& st, int kind, const Dop853Record& r,
-                                            const double* __restrict__ t_eval, int64_t n_eval, double* __restrict__ tev, int64_t max_events)
+                                            const double* __restrict__ t_eval, int64_t n_eval, double* __restrict__ tev, int64_t max_events,
+                                            Dop853StopRef<TERM> stop = {})
 {
+    if constexpr (TERM) {
+        if (kind == DOP853_STOP) {
+            for (int e = 0; e < 7; e++) sc.g[e] = rk45_monitor_of_record(r.q, e);
+            if (sc.status == ST_RUNNING) sc.attempts--;
+            sc.t = stop.rec->t_stop;
+            sc.status = ST_TERMINAL;
+            trip.kind = DOP853_ATTEMPT;
+            trip.h = sc.h_try;
+            trip.commit = 0;
+            trip.leave = 1;
+            return;
+        }
+    }
     if (kind == DOP853_ATTEMPT) {
         if (dop853_decide(sc, r.q[0], r.s3)) {
             int changed = 0, locate = 0;
@@ -130,6 +177,18 @@ __device__ __noinline__ void dop853_control(Rk45Ctrl& sc, Dop853Trip& trip, Dop8
                 if ((go <= 0.0 && gn >= 0.0) || (go >= 0.0 && gn <= 0.0)) {
                     changed |= 1 << e;
                     if (ROOTS && sc.n_events[e] < max_events) locate |= 1 << e;
+                }
+            }
+            if constexpr (TERM) {
+                if (dop853_stop_begin(*stop.rec, (uint32_t)changed, sc.n_events)) {
+                    for (int e = 0; e < 7; e++) stop.rec->g_new[e] = rk45_monitor_of_record(r.q, e);
+                    dop853_status_after_accept(sc);
+                    if (sc.status == ST_RUNNING) dop853_prepare_attempt(sc);
+                    dop853_count_dense_output(sc);
+                    st.counted = 1;
+                    st.ev_mask = (int32_t)stop.rec->locate;
+                    dop853_schedule<EVAL, ROOTS, TERM>(sc, trip, st, t_eval, n_eval, stop);
+                    return;
                 }
             }
             rk45_events(sc, r.q);                // g <- g_new, the counts, ev_first / ev_last
@@ -141,7 +200,7 @@ __device__ __noinline__ void dop853_control(Rk45Ctrl& sc, Dop853Trip& trip, Dop8
                 st.counted = 1;
             }
             st.ev_mask = locate;
-            dop853_schedule<EVAL, ROOTS>(sc, trip, st, t_eval, n_eval);
+            dop853_schedule<EVAL, ROOTS, TERM>(sc, trip, st, t_eval, n_eval, stop);
         } else {
             dop853_prepare_attempt(sc);
             trip.kind = DOP853_ATTEMPT;
@@ -153,7 +212,7 @@ __device__ __noinline__ void dop853_control(Rk45Ctrl& sc, Dop853Trip& trip, Dop8
     }
     if (kind == DOP853_SAMPLE) {
         st.ie++;
-        dop853_schedule<EVAL, ROOTS>(sc, trip, st, t_eval, n_eval);
+        dop853_schedule<EVAL, ROOTS, TERM>(sc, trip, st, t_eval, n_eval, stop);
         return;
     }
     if constexpr (ROOTS) {
@@ -185,11 +244,28 @@ __device__ __noinline__ void dop853_control(Rk45Ctrl& sc, Dop853Trip& trip, Dop8
             dop853_replay_at(sc, trip, st, DOP853_PROBE, st.bs.xcur);
             return;
         }
+        if constexpr (TERM) {
+            if (stop.rec->stage == DOP853_STOP_ROOTS) {   // a step that ends the run: kept until the rule has said which of them happened
+                st.ev_mask = (int32_t)dop853_stop_root(*stop.rec, st.br_e, root);
+                st.br_phase = 0;
+                if (st.ev_mask == 0) {
+                    int64_t counts[7], slot[7];
+                    dop853_stop_rule(*stop.rec, sc.n_events, max_events, counts, slot);
+                    for (int e = 0; e < 7; e++) {
+                        if (!((stop.rec->kept >> e) & 1)) continue;
+                        rk45_event_one(sc, e, stop.rec->g_new[e]);   // the count, ev_first / ev_last, as rk45_events
+                        if (slot[e] >= 0) tev[e * max_events + slot[e]] = stop.rec->root[e];
+                    }
+                }
+                dop853_schedule<EVAL, ROOTS, TERM>(sc, trip, st, t_eval, n_eval, stop);
+                return;
+            }
+        }
         // (the step's bookkeeping is done: n_events[br_e] - 1 is the count before the step, < max_events)
         tev[st.br_e * max_events + (sc.n_events[st.br_e] - 1)] = root;
         st.ev_mask &= ~(1 << st.br_e);
         st.br_phase = 0;
-        dop853_schedule<EVAL, ROOTS>(sc, trip, st, t_eval, n_eval);
+        dop853_schedule<EVAL, ROOTS, TERM>(sc, trip, st, t_eval, n_eval, stop);
     }
 }
 
@@ -197,14 +273,19 @@ __device__ __noinline__ void dop853_control(Rk45Ctrl& sc, Dop853Trip& trip, Dop8
 // method on replays (dop853_sweep_roots_kernel); order within a step: roots (monitors ascending), samples, commit.
 //   Y [batch][5][N] field-major, in place;  karena: dop853_arena_doubles(batch, BLK);  t_eval [n_eval] (device), Yeval
 //   [batch][n_eval][5 N], n_done [batch];  t_events [batch][7][max_events] (device).
-template <int BLK, bool VD, bool EVAL, bool ROOTS>
+// TERM (with ROOTS; dop853_sweep_stop_kernel): terminal monitors with the limits `lim` - see dop853_control.  The stop record is LDS of
+// its own, declared under TERM only: the LDS of the other kernels is what it was.  One more trip kind, DOP853_STOP: the replay at t_stop
+// whose  y + h sum_j w_j K_j  - the expression that writes a frame - becomes the thread's y, and whose monitors are reduced like a
+// probe's; the loop is left behind it.  t_events may be NULL with max_events = 0, n_eval may be 0.
+template <int BLK, bool VD, bool EVAL, bool ROOTS, bool TERM = false>
 __device__ __forceinline__ void dop853_sweep_body(double* __restrict__ Y, const DevConsts* __restrict__ consts, Rk45Ctrl* __restrict__ ctrls,
                                                   int64_t N, double* __restrict__ karena, const double* __restrict__ t_eval = nullptr,
                                                   int64_t n_eval = 0, double* __restrict__ Yeval = nullptr,
                                                   int64_t* __restrict__ n_done = nullptr, double* __restrict__ t_events = nullptr,
-                                                  int64_t max_events = 0)
+                                                  int64_t max_events = 0, TermLimits lim = {})
 {
     static_assert(EVAL || !ROOTS, "a Brent function evaluation is a dense-output replay");
+    static_assert(ROOTS || !TERM, "the stop is found by the root search");
     using SB = StencilBlock<BLK, false, VD>;
     static_assert(SB::EDGE_DOUBLES >= NQ * BLK, "block_reduce transposes the record through the edge buffers");
     __shared__ double lds[SB::LDS_DOUBLES];
@@ -212,6 +293,11 @@ __device__ __forceinline__ void dop853_sweep_body(double* __restrict__ Y, const 
     __shared__ Dop853Trip trip;
     __shared__ Dop853Walk st;
     __shared__ double wsum3[BLK / 64];             // per-wave sums of (err3 / scale)^2
+    Dop853StopRef<TERM> stop;
+    if constexpr (TERM) {
+        __shared__ Dop853Stop stop_rec;
+        stop.rec = &stop_rec;
+    }
     const DevConsts& C = consts[blockIdx.x];
     double* yg = Y + (int64_t)blockIdx.x * NF * N;
     const Slab S = {N, 0, N, 0, N};
@@ -233,6 +319,7 @@ __device__ __forceinline__ void dop853_sweep_body(double* __restrict__ Y, const 
 
     if (threadIdx.x == 0) {
         st = Dop853Walk{};
+        if constexpr (TERM) dop853_stop_init(*stop.rec, lim.k);
         trip.kind = DOP853_ATTEMPT;
         trip.h = sc.h_try;
         trip.commit = 0;
@@ -337,6 +424,11 @@ __device__ __forceinline__ void dop853_sweep_body(double* __restrict__ Y, const 
                     double U, W;
                     uw_point(d[4], C, sb.T, U, W);
                     monitors_accumulate(r.q, d, U, W);
+                    if constexpr (TERM) {
+                        if (kind == DOP853_STOP) {   // the state at t_stop: what the kernel leaves in Y
+                            MARL_FIELDS y[f] = d[f];
+                        }
+                    }
                 }
             }
         }
@@ -356,8 +448,8 @@ __device__ __forceinline__ void dop853_sweep_body(double* __restrict__ Y, const 
 #pragma unroll
             for (int w = 0; w < BLK / 64; w++) s3 += wsum3[w];
             r.s3 = s3;
-            dop853_control<EVAL, ROOTS>(sc, trip, st, kind, r, t_eval, n_eval, ROOTS ? t_events + (int64_t)blockIdx.x * 7 * max_events : nullptr,
-                                        max_events);
+            dop853_control<EVAL, ROOTS, TERM>(sc, trip, st, kind, r, t_eval, n_eval,
+                                              ROOTS ? t_events + (int64_t)blockIdx.x * 7 * max_events : nullptr, max_events, stop);
         }
         __syncthreads();
     }
@@ -398,6 +490,19 @@ __global__ void __launch_bounds__(BLK) dop853_sweep_roots_kernel(double* __restr
                                                                  double* __restrict__ t_events, int64_t max_events)
 {
     dop853_sweep_body<BLK, VD, true, true>(Y, consts, ctrls, N, karena, t_eval, n_eval, Yeval, n_done, t_events, max_events);
+}
+
+// dop853_sweep_roots_kernel honouring terminal monitors (marl_sweep_dop853_stop_dev; `lim`: marl_set_terminal's limits): an instance
+// whose monitor meets its limit ends at that root with ST_TERMINAL, the state the step's dense output there.  A unit of its own
+// (marl_dop853_stop.hip).
+template <int BLK, bool VD = false>
+__global__ void __launch_bounds__(BLK) dop853_sweep_stop_kernel(double* __restrict__ Y, const DevConsts* __restrict__ consts,
+                                                                Rk45Ctrl* __restrict__ ctrls, int64_t N, double* __restrict__ karena,
+                                                                const double* __restrict__ t_eval, int64_t n_eval,
+                                                                double* __restrict__ Yeval, int64_t* __restrict__ n_done,
+                                                                double* __restrict__ t_events, int64_t max_events, TermLimits lim)
+{
+    dop853_sweep_body<BLK, VD, true, true, /*TERM=*/true>(Y, consts, ctrls, N, karena, t_eval, n_eval, Yeval, n_done, t_events, max_events, lim);
 }
 
 }  // namespace marl

@@ -33,7 +33,8 @@ void launch_sweep_t(int kind, unsigned grid, hipStream_t stream, double* Y, cons
 DOP853_VIS int64_t marl_dop853_arena_doubles(int64_t grid, int blk) { return dop853_arena_doubles(grid, blk); }
 
 // blk: 256, 512 or 1024; kind: 0, 2 or 3 (anything else: hipErrorInvalidValue, nothing launched).  There is no pausing kernel (kind 1)
-// and no terminal kernel (kind 4): single runs go through kind 3 with one instance, terminal monitors are refused by the entries.
+// and kind 4 is refused here: single runs go through kind 3 with one instance, and the kernel that stops at a terminal monitor's root
+// lives in marl_dop853_stop.hip behind a launcher of its own.
 DOP853_VIS int marl_dop853_launch_sweep(int kind, int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* ctrls,
                                         int64_t N, double* karena, const double* t_eval, int64_t n_eval, double* Yeval, int64_t* n_done,
                                         double* t_events, int64_t max_events)

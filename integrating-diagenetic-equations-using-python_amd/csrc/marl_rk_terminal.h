@@ -1,7 +1,8 @@
 // Terminal monitors in the explicit adaptive loops (RK45, RK23): what ONE accepted step does with the rule of marl_terminal.h
 // (terminal_select, scipy's handle_events) - which sign changes happened, how the counts move and where the kept roots are stored.
-// Called by the sweep kernels (rk45_sweep_body<..., TERM>, marl_kernels.h) and by the host loop of the single runs (rk_run,
-// marl_api.hip), so the rule and its bookkeeping stay stated once.  Nothing but <stdint.h>, <math.h> and marl_terminal.h: a host C++
+// Called by the sweep kernels (rk45_sweep_body<..., TERM>, marl_kernels.h), by the host loop of the single runs (rk_run,
+// marl_api.hip) and by the DOP853 loop's walk of a step that ends the run (marl_dop853_stop.h), so the rule and its bookkeeping stay
+// stated once.  Nothing but <stdint.h>, <math.h> and marl_terminal.h: a host C++
 // compiler builds this header alone (tests/test_rk_terminal_cpu.py holds it to scipy's handle_events that way); under hipcc it
 // follows <hip/hip_runtime.h>.
 #pragma once

@@ -102,6 +102,11 @@ class HipSweepEngine:
         results.  There is no terminal entry: with ``terminal`` set the sweep is refused (:class:`marlpde_amd._abi.MarlError`)."""
         return self._integrate_rk("sweep_dop853_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
 
+    def integrate_dop853_stop(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
+        """:meth:`integrate_dop853` with ``terminal`` honoured as :meth:`integrate_rk45` honours it: an instance whose terminal monitor
+        occurs ends at that root inside the sweep kernel (marl_sweep_dop853_stop_dev) - status 1, ``t_reached`` the root."""
+        return self._integrate_rk("sweep_dop853_stop_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
+
     def _integrate_rk(self, sweep, y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal=None):
         self.model.set_terminal(terminal)
         sweep = getattr(self.model, sweep)
@@ -292,6 +297,15 @@ def run_sweep_dop853(base_parms, instances, t_span, first_step, rtol, atol, max_
     cannot stop at a monitor's root."""
     return _run_sweep("integrate_dop853", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
                       balance, cost, t_eval, events, max_events, terminal=terminal)
+
+
+def run_sweep_dop853_stop(base_parms, instances, t_span, first_step, rtol, atol, max_attempts=0, y0=None, group=None,
+                          device=None, engine_factory=None, gather=True, balance="contiguous", cost=None, t_eval=None, events=False,
+                          max_events=64, terminal=None):
+    """As :func:`run_sweep_dop853` with ``terminal`` honoured, as :func:`run_sweep_rk45` honours it: an instance whose terminal
+    monitor fires ends there - ``status`` 1, ``t_reached`` the root.  The same arguments and the same returned tuple."""
+    return _run_sweep("integrate_dop853_stop", base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory,
+                      gather, balance, cost, t_eval, events, max_events, terminal=terminal)
 
 
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
