@@ -71,9 +71,10 @@ int marl_synchronize(marl_ctx* ctx);
  * caller passed no t_events; they are stored only where a slot is free.  A step that meets no limit runs exactly as without limits.
  * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev,
  * marl_sweep_bdf_terminal_dev, marl_sweep_rk45_terminal_dev / rk23_terminal_dev, marl_integrate_rk45_terminal / rk23_terminal,
- * marl_sweep_dop853_stop_dev, marl_integrate_dop853_stop.  Every other
+ * marl_sweep_dop853_stop_dev, marl_integrate_dop853_stop, marl_integrate_dop853_grid.  Every other
  * integrator entry (marl_integrate_rk45 / rk23, marl_integrate_rk45_dev / rk23_dev, marl_sweep_rk45_dev / _eval_dev / _events_dev and their rk23
- * counterparts, marl_integrate_dop853, marl_sweep_dop853_dev / _eval_dev / _events_dev, marl_sweep_bdf_dev / _eval_dev / _events_dev,
+ * counterparts, marl_integrate_dop853, marl_sweep_dop853_dev / _eval_dev / _events_dev, marl_integrate_dop853_grid_dev,
+ * marl_sweep_bdf_dev / _eval_dev / _events_dev,
  * marl_slab_init_control, marl_slab_run) returns -1 while a limit is set - "...: terminal monitors are not supported by this entry (marl_set_terminal)" -
  * before it touches the state, and is unchanged when none is. */
 int marl_set_terminal(marl_ctx* ctx, const int64_t terminal[7]);
@@ -312,9 +313,9 @@ int marl_integrate_rk23_terminal(marl_ctx* ctx, double* y, double t0, double t1,
  * watched and counted.  Arguments, results, argument checks, status codes and the t0 == t1 behaviour are those of the RK45 entry of
  * the same name; messages start with "dop853:".  On these stability-limited equations DOP853 needs about as many evaluations as
  * RK45: it is here for coverage of the reference's solver switch, not as the cheaper method.
- * Only grids that fit one workgroup: N > 1024 returns -1, "dop853: ... N <= 1024 ...".  Terminal monitors: the four entries below
- * return -1 with the standard message while a limit is set (marl_set_terminal), before the state is touched; the two _stop entries
- * after them honour the limits.  No _dev single-run entry, no slab contexts. */
+ * Only grids that fit one workgroup: N > 1024 returns -1, "dop853: ... N <= 1024 ..." (larger single grids: the two _grid entries
+ * further down).  Terminal monitors: the four entries below return -1 with the standard message while a limit is set
+ * (marl_set_terminal), before the state is touched; the two _stop entries after them honour the limits.  No slab contexts. */
 /* marl_integrate_rk45 with DOP853: one instance, host pointers; t_eval frames and root times come from the sweep kernel that
  * locates roots (dop853_sweep_roots_kernel) run for one instance - no host in the loop. */
 int marl_integrate_dop853(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
@@ -348,6 +349,26 @@ int marl_sweep_dop853_stop_dev(marl_ctx* ctx, double* y_dev, double t0, double t
 int marl_integrate_dop853_stop(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
                                const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
                                int64_t max_attempts, marl_stats* stats);
+
+/* ---- DOP853 on one grid of any size: one launch per stage (csrc/marl_dop853_grid.h) ----
+ * The large-grid counterpart of marl_integrate_dop853: on a grid of many workgroups a stage state needs its neighbours' stage
+ * derivatives, which other workgroups own, so an attempt is 12 launches of dop853_grid_stage_kernel (256-thread windows that write
+ * 254 cells; K_1..K_16 in an arena of 16 state-shaped buffers owned by the context), a reduction of the per-workgroup records in a
+ * fixed order (two error sums, no float atomics: a run is reproducible bit for bit) and a control kernel.  The host enqueues batches
+ * of `poll_interval` attempts and reads the status once per batch, as marl_integrate_rk45 does on a large grid; at a pause it locates
+ * roots by Brent's method on dense evaluations (dop853_grid_dense_kernel) and writes the samples.
+ * Arguments, checks, messages ("dop853: ..."), status codes and the t0 == t1 behaviour are those of marl_integrate_dop853 /
+ * marl_integrate_rk23_dev; nfev = 1 + 12 attempts + 3 (accepted steps with a monitor sign change or a sample).  Any N is accepted,
+ * N <= 1024 included (the two paths order their sums differently and agree to rounding, not bit for bit).
+ * Terminal monitors (marl_set_terminal): marl_integrate_dop853_grid honours them as marl_integrate_rk45_terminal does - all roots of
+ * the step located, the rule applied, the samples with t_eval[k] <= t_stop written, the state the step's dense output at t_stop,
+ * stats->status = 1; marl_integrate_dop853_grid_dev refuses a limit with the standard message.
+ * Refused with -1 before the state is touched: slab contexts, contexts of more than one instance. */
+int marl_integrate_dop853_grid(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                               const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                               int64_t max_attempts, marl_stats* stats);
+int marl_integrate_dop853_grid_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step,
+                                   double rtol, double atol, int64_t max_attempts, marl_stats* stats);
 
 /* ---- implicit Radau IIA (order 5): the reference's DEFAULT solver ------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="Radau", jac_sparsity=jacobian_sparsity(), first_step=,

@@ -11,7 +11,10 @@ reference (Evolve_scenario.py:19) and returns the same tuple
   attempt, step factor ``0.9 err^(-1/3)``, cubic dense output) via ``marl_integrate_rk23`` - no scipy in the loop.
 * ``backend == "hip"`` and ``method == "DOP853"`` on a grid of up to 1024 cells, without terminal monitors: scipy's Dormand-Prince
   8(5,3) (12 evaluations per attempt, step factor ``0.9 err^(-1/8)``, the degree-7 dense output whose 3 extra evaluations scipy
-  counts) via ``marl_integrate_dop853`` - no scipy in the loop.  Larger grids and terminal monitors take the scipy route below.
+  counts) via ``marl_integrate_dop853`` - no scipy in the loop.  Terminal monitors: ``native_terminal=True`` takes
+  ``marl_integrate_dop853_stop``.  Larger grids: ``solver_parms["native_grid"] = True`` takes the large-grid loop, one launch per
+  stage, via ``marl_integrate_dop853_grid`` (with a terminal monitor only together with ``native_terminal=True``) - no scipy in
+  the loop either.  Without these keys larger grids and terminal monitors take the scipy route below.
 * ``backend == "hip"`` and ``method == "Radau"`` (the reference's default, parameters.py:213): scipy's Radau IIA step
   logic restated natively, with the RHS, the finite-difference Jacobian (the reference's 27-diagonal pattern), the
   block-tridiagonal LU factorisations and every vector operation on the GPU via ``marl_integrate_radau`` - no scipy in the loop.
@@ -64,7 +67,8 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     :func:`marlpde_amd.LHeureux_model.terminal_counts` reads it.  Native for Radau and BDF; for RK45 / RK23 the solver parameters
     choose: ``native_terminal=True`` - the native loop stops itself (marl_integrate_rk45_terminal / rk23_terminal) - or
     ``scipy_driver=True`` - solve_ivp drives the HIP RHS.  DOP853 with a terminal monitor: ``native_terminal=True`` and N <= 1024 - the
-    native loop stops itself (marl_integrate_dop853_stop); otherwise solve_ivp drives the HIP RHS, as it does without the switch."""
+    native loop stops itself (marl_integrate_dop853_stop); ``native_terminal=True`` with ``native_grid=True`` and N > 1024 - the
+    large-grid loop stops itself (marl_integrate_dop853_grid); otherwise solve_ivp drives the HIP RHS, as it does without the switch."""
     limits = terminal_counts(terminal)
     solver_parms = dict(solver_parms)
     Xstar, Tstar = pde_parms["Xstar"], pde_parms["Tstar"]
@@ -86,6 +90,7 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     start = time.time()
     scipy_driver = bool(solver_parms.pop("scipy_driver", False))
     native_terminal = bool(solver_parms.pop("native_terminal", False))
+    native_grid = bool(solver_parms.pop("native_grid", False))
     if method in ("RK45", "RK23") and not scipy_driver:
         if any(limits) and not native_terminal:
             eq.close()
@@ -117,6 +122,16 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
         # a terminal monitor and native_terminal=True: the native loop stops itself (marl_integrate_dop853_stop)
         eq.set_terminal(limits)
         res = eq.integrate_dop853_stop(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
+        t_out, y_out, t_events = res.t, res.y, res.t_events
+        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
+        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the RK45 branch)
+            status = -1
+        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+    elif method == "DOP853" and not scipy_driver and N > 1024 and native_grid and (native_terminal or not any(limits)):
+        # a grid above one workgroup and native_grid=True: the large-grid loop, one launch per stage (marl_integrate_dop853_grid); it
+        # stops itself at a terminal monitor's root, which stays opt-in (native_terminal=True) as everywhere
+        eq.set_terminal(limits)
+        res = eq.integrate_dop853_grid(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
         t_out, y_out, t_events = res.t, res.y, res.t_events
         nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
         if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the RK45 branch)

@@ -416,6 +416,15 @@ class LMAHeureuxPorosityDiff:
         and including it; ``events=False`` stops all the same.  Without a terminal monitor the same run as :meth:`integrate_dop853`."""
         return self._integrate_rk("dop853_stop", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
+    def integrate_dop853_grid(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
+                              max_attempts=0):
+        """:meth:`integrate_dop853` for a grid of ANY size (marl_integrate_dop853_grid): the large-grid loop - one launch per stage,
+        the stage derivatives in an arena owned by the context, one status read per batch of attempts, roots by Brent's method on
+        dense evaluations at a pause.  The same signature, result and ``nfev``; on grids of up to 1024 cells it agrees with
+        :meth:`integrate_dop853` to rounding (the sums are ordered differently), not bit for bit.  Terminal monitors
+        (:meth:`set_terminal`) are honoured as by :meth:`integrate_rk45_terminal`.  One instance, no slab contexts."""
+        return self._integrate_rk("dop853_grid", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
+
     def _integrate_rk(self, method, y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts):
         entry = getattr(self._lib, f"marl_integrate_{method}")
         y_start = self._host_state(y0)
@@ -593,6 +602,10 @@ class LMAHeureuxPorosityDiff:
     def integrate_rk23_device(self, y_dev_ptr, t_span, first_step, rtol, atol, layout=LAYOUT_FIELD_MAJOR, max_attempts=0):
         """:meth:`integrate_rk45_device` with RK23 (marl_integrate_rk23_dev)."""
         return self._integrate_rk_device("rk23", y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts)
+
+    def integrate_dop853_grid_device(self, y_dev_ptr, t_span, first_step, rtol, atol, layout=LAYOUT_FIELD_MAJOR, max_attempts=0):
+        """:meth:`integrate_rk45_device` with DOP853 on a grid of any size (marl_integrate_dop853_grid_dev); refuses terminal monitors."""
+        return self._integrate_rk_device("dop853_grid", y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts)
 
     def _integrate_rk_device(self, method, y_dev_ptr, t_span, first_step, rtol, atol, layout, max_attempts):
         stats = MarlStats()

@@ -108,6 +108,8 @@ PROTOTYPES = {
     "marl_sweep_dop853_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
     "marl_sweep_dop853_stop_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
     "marl_integrate_dop853_stop": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
+    "marl_integrate_dop853_grid": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
+    "marl_integrate_dop853_grid_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
     "marl_integrate_radau": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_integrate_bdf": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_sweep_radau_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, C.POINTER(MarlStats)]),

@@ -80,9 +80,11 @@ struct marl_ctx {
     // sweeps that locate the monitors' roots (rk45_sweep_roots_kernel): the root times [batch][7][max_events], allocated on first use or growth
     double* sw_tev = nullptr;
     size_t sw_tev_cap = 0;
-    // DOP853 sweeps (marl_dop853.h): the stage derivatives of every instance, [batch][16][5][window]; allocated on first use or growth
+    // DOP853 sweeps (marl_dop853.h): the stage derivatives of every instance, [batch][16][5][window]; allocated on first use or growth.
+    // Large-grid DOP853 runs (marl_dop853_grid.h) keep their arena here too: 16 state-shaped buffers in the layout of the state.
     double* dop_k = nullptr;
     size_t dop_k_cap = 0;
+    int64_t dop_grid_extra = -1;   // large-grid DOP853: the accepted step (its n_acc) whose extra stages K14..K16 lie in the arena; -1: none
     // domain decomposition: this rank's message / the gathered messages (device), and the RCCL communicator (dlopen'ed API)
     double* dd_send = nullptr;
     double* dd_gathered = nullptr;
@@ -874,6 +876,15 @@ struct RkMethod {
     int (*control)(marl_ctx*, const double* recs, int64_t nrec);
     int (*dense)(marl_ctx*, int64_t nb, int layout, const double* yold, const double* fold, double h, const DenseWeights& dw, double* yout);
     void (*weights)(double x, DenseWeights* dw);   // w_j(x) of the dense output
+    // A method whose attempt is not "K1 in a buffer, the rest in one launch" (DOP853 on large grids: 16 stage derivatives in an arena,
+    // 16 dense-output weights) replaces three steps of rk_run; NULL in the rows of RK45 and RK23, which run exactly as they did.
+    const char* entry;       // the name behind "marl_integrate_" in messages, where it is not `name`
+    bool grid_only;          // marl_integrate_<entry> takes the large-grid loop at every N (no one-workgroup sweep)
+    int64_t (*part_records)(int64_t nb);   // records of ctx->part for nb windows, laid out by the method: `control` then reduces all of it
+    int (*first_k)(marl_ctx*, int layout);   // K1 = f(t0, y0) of the state in buf[0], behind rk45_init_kernel; in place of launch_rhs into buf[2]
+    // the dense output of the last accepted step at time t: the state into yout (may be NULL), one monitors record per workgroup into
+    // ctx->part when want_part; *nb: how many.  In place of weights + dense.
+    int (*dense_at)(marl_ctx*, int layout, const Rk45Ctrl& c, double t, double* yout, bool want_part, int64_t* nb);
 };
 
 constexpr int64_t kReduceGroups = 64;
@@ -905,6 +916,7 @@ static int launch_attempt(marl_ctx* ctx, int layout, const RkMethod& m)
 {
     const int64_t nb = rk_blocks(ctx, m.written);
     if (int rc = m.attempt(ctx, nb, layout)) return rc;
+    if (m.part_records) return m.control(ctx, ctx->part, nb);   // (a record buffer of the method's own layout: its control reduces it)
     int64_t nrec = nb;
     const double* recs = reduce_first_level(ctx, &nrec);
     LAUNCH_OK(ctx);
@@ -1127,12 +1139,16 @@ static const RkMethod kRk23 = {"rk23", "marl_sweep_rk23_dev", 256 - 2 * 3, false
 // seven monitors into g (may be NULL; synchronises when given).
 static int dense_eval(marl_ctx* ctx, const RkMethod& m, int layout, bool small, const Rk45Ctrl& c, double t, double* yout, double* g)
 {
-    DenseWeights dw;
-    m.weights((t - c.t_old) / c.h_prev, &dw);
-    const double* yold = small ? ctx->buf[1] : ctx->buf[c.cur ^ 1];
-    const double* fold = small ? ctx->buf[3] : ctx->buf[2 + (c.cur ^ 1)];
-    const int64_t nb = rk_blocks(ctx, m.written);
-    if (int rc = m.dense(ctx, nb, layout, yold, fold, c.h_prev, dw, yout)) return rc;
+    int64_t nb = rk_blocks(ctx, m.written);
+    if (m.dense_at) {
+        if (int rc = m.dense_at(ctx, layout, c, t, yout, g != nullptr, &nb)) return rc;
+    } else {
+        DenseWeights dw;
+        m.weights((t - c.t_old) / c.h_prev, &dw);
+        const double* yold = small ? ctx->buf[1] : ctx->buf[c.cur ^ 1];
+        const double* fold = small ? ctx->buf[3] : ctx->buf[2 + (c.cur ^ 1)];
+        if (int rc = m.dense(ctx, nb, layout, yold, fold, c.h_prev, dw, yout)) return rc;
+    }
     if (g) {
         hipLaunchKernelGGL(reduce_records_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->part, nb, ctx->rec);
         LAUNCH_OK(ctx);
@@ -1195,15 +1211,17 @@ static int rk_run(const RkMethod& m, marl_ctx* ctx, int layout, bool small, doub
     rtol = clamp_rtol(rtol);
     const int blk = small ? sweep_block(ctx) : 0;
     const int64_t nb = rk_blocks(ctx, m.written);
-    if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(nb + kReduceGroups, 1024))) return rc;
+    if (int rc = ensure_part(ctx, (size_t)std::max<int64_t>(m.part_records ? m.part_records(nb) : nb + kReduceGroups, 1024))) return rc;
     const int64_t sd = state_doubles(ctx->slab.n_buf, layout);
     // f(t0, y0) and the monitors at t0
-    if (!small)
+    if (!small && !m.first_k)
         if (int rc = launch_rhs(ctx, ctx->buf[0], ctx->buf[2], layout)) return rc;
     if (int rc = launch_monitors(ctx, ctx->buf[0], layout)) return rc;
     hipLaunchKernelGGL(rk45_init_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->dctrl, ctx->rec, t0, t1, first_step, rtol, atol,
                        (int64_t)NF * ctx->N, max_attempts, 0);
     LAUNCH_OK(ctx);
+    if (!small && m.first_k)
+        if (int rc = m.first_k(ctx, layout)) return rc;
     int64_t eval_i = 0;
     // t_eval == t0 is emitted on the first step by scipy (dense output at x = 0 == y_old)
     const bool events_on = t_events != nullptr && max_events > 0, term = has_terminal(ctx);
@@ -1534,9 +1552,10 @@ int marl_sweep_rk45_terminal_dev(marl_ctx* ctx, double* y_dev, double t0, double
 static int integrate_rk_dev(const RkMethod& m, marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
                             double atol, int64_t max_attempts, marl_stats* stats)
 {
-    if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_integrate_%s_dev: invalid argument", m.name) : -1;
-    NO_TERMINAL(ctx, (std::string("marl_integrate_") + m.name + "_dev").c_str())
-    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s_dev: single-instance context required (use %s)", m.name, m.sweep_entry);
+    const char* en = m.entry ? m.entry : m.name;
+    if (!ctx || !y_dev || !stats) return ctx ? fail(ctx, -1, "marl_integrate_%s_dev: invalid argument", en) : -1;
+    NO_TERMINAL(ctx, (std::string("marl_integrate_") + en + "_dev").c_str())
+    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s_dev: single-instance context required (use %s)", en, m.sweep_entry);
     if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
     const size_t sd = (size_t)state_doubles(ctx->slab.n_buf, layout);
@@ -1554,13 +1573,14 @@ static int integrate_rk(const RkMethod& m, marl_ctx* ctx, double* y, double t0, 
                         const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
                         int64_t max_attempts, marl_stats* stats, bool terminal_ok = false)
 {
+    const char* en = m.entry ? m.entry : m.name;
     if (!ctx || !y || !stats || (n_eval > 0 && (!t_eval || !y_eval)))
-        return ctx ? fail(ctx, -1, "marl_integrate_%s%s: invalid argument", m.name, terminal_ok ? "_terminal" : "") : -1;
-    if (!terminal_ok) { NO_TERMINAL(ctx, (std::string("marl_integrate_") + m.name).c_str()) }
-    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s: single-instance context required (use %s)", m.name, m.sweep_entry);
+        return ctx ? fail(ctx, -1, "marl_integrate_%s%s: invalid argument", en, terminal_ok && !m.entry ? "_terminal" : "") : -1;
+    if (!terminal_ok) { NO_TERMINAL(ctx, (std::string("marl_integrate_") + en).c_str()) }
+    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_%s: single-instance context required (use %s)", en, m.sweep_entry);
     if (!m.can_stream && ctx->halo > 0) return fail(ctx, -1, "%s: slab contexts (domain decomposition) are not supported", m.name);
     HIP_OK(ctx, hipSetDevice(ctx->device));
-    const bool small = sweep_block(ctx) > 0;
+    const bool small = !m.grid_only && sweep_block(ctx) > 0;
     const int layout = small ? LAYOUT_FIELD_MAJOR : (int)ctx->host_layout;
     const size_t n = (size_t)NF * ctx->N;
     const size_t sd = (size_t)state_doubles(ctx->N, layout);
@@ -1573,8 +1593,14 @@ static int integrate_rk(const RkMethod& m, marl_ctx* ctx, double* y, double t0, 
     if (n_eval > 0) HIP_OK(ctx, hipMalloc((void**)&yev, sizeof(double) * sd * (size_t)(n_eval + 1)));
     int rc = rk_run(m, ctx, layout, small, t0, t1, first_step, rtol, atol, t_eval, n_eval, yev, t_events, max_events, max_attempts, stats);
     if (rc == 0) {
-        // results back to field-major through a spare slot
-        for (int64_t i = 0; i < n_eval && rc == 0; i++) {
+        // results back to field-major through a spare slot.  The large-grid DOP853 entry returns the frames it wrote - the samples up to
+        // stats->t, where the run ended (t1, a terminal monitor's root, or the attempt budget) - and leaves the caller's later frames untouched.
+        int64_t n_back = n_eval;
+        if (m.grid_only) {
+            n_back = 0;
+            while (n_back < n_eval && t_eval[n_back] <= stats->t) n_back++;
+        }
+        for (int64_t i = 0; i < n_back && rc == 0; i++) {
             rc = launch_convert(ctx, yev + i * sd, yev + n_eval * sd, layout, LAYOUT_FIELD_MAJOR);
             if (rc == 0 && hipMemcpyAsync(y_eval + i * n, yev + n_eval * sd, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
                 rc = fail(ctx, -3, "copy of t_eval sample failed");
@@ -1788,6 +1814,86 @@ int marl_integrate_dop853_stop(marl_ctx* ctx, double* y, double t0, double t1, d
 {
     return integrate_dop853("marl_integrate_dop853_stop", true, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events,
                             max_attempts, stats);
+}
+}  // extern "C"
+
+// ---- DOP853 on one grid of any size: one launch per stage (kernels: marl_dop853_grid.h, a translation unit of its own) ----
+// The loop is rk_run's - batches of ctx->poll attempts, one status read per batch, Brent on dense evaluations at a pause, terminal
+// monitors by rk_terminal_step - with a third row of the method table: an attempt is 12 stage launches, the reduction and the control;
+// K_1..K_16 live in an arena of 16 state-shaped buffers (ctx->dop_k) instead of the FSAL pair buf[2], buf[3]; the dense output has 16
+// weights and, once per step that needs it, three more stage launches (K_14..K_16).  nfev is counted by the control kernel alone.
+extern "C" {
+int64_t marl_dop853_grid_part_doubles(int64_t nb);
+int marl_dop853_grid_launch_stage(int tiled, int vd, unsigned nb, hipStream_t stream, double* Y0, double* Y1, double* karena, int64_t kstride,
+                                  const void* consts, const int64_t slab5[5], const void* ctrl, int s, int replay, double* part);
+int marl_dop853_grid_launch_control(hipStream_t stream, double* part, int64_t nb, void* ctrl);
+int marl_dop853_grid_launch_dense(int tiled, unsigned nb, hipStream_t stream, const double* yold, const double* karena, int64_t kstride, int frame,
+                                  const void* consts, const int64_t slab5[5], double h, double x, int at_start, double* yout, double* part);
+}
+constexpr int kDop853GridWritten = 256 - 2, kDop853GridSlots = 16, kDop853GridStages = 12;
+static int dop853_grid_launched(marl_ctx* ctx, int err)
+{
+    if (err != (int)hipSuccess) return fail(ctx, -3, "dop853: kernel launch failed: %s", hipGetErrorString((hipError_t)err));
+    return 0;
+}
+static int dop853_grid_stage(marl_ctx* ctx, int64_t nb, int layout, int s, int replay)
+{
+    const Slab& S = ctx->slab;
+    const int64_t slab5[5] = {S.n_buf, S.goff, S.ld, S.out_lo, S.out_hi};
+    return dop853_grid_launched(ctx, marl_dop853_grid_launch_stage(layout == LAYOUT_TILED, ctx->var_dphi ? 1 : 0, (unsigned)nb, ctx->stream, ctx->buf[0],
+                                                                   ctx->buf[1], ctx->dop_k, state_doubles(S.n_buf, layout), ctx->dconsts, slab5, ctx->dctrl,
+                                                                   s, replay, ctx->part));
+}
+static int64_t dop853_grid_m_part_records(int64_t nb) { return (marl_dop853_grid_part_doubles(nb) + NQ - 1) / NQ; }
+// the arena (grown here: nothing of a run is in it yet) and K_1 = f(t0, y0) into the slot of frame 0
+static int dop853_grid_m_first_k(marl_ctx* ctx, int layout)
+{
+    if (int rc = grow_dev(ctx, &ctx->dop_k, &ctx->dop_k_cap, (size_t)kDop853GridSlots * (size_t)state_doubles(ctx->slab.n_buf, layout))) return rc;
+    ctx->dop_grid_extra = -1;
+    return dop853_grid_stage(ctx, rk_blocks(ctx, kDop853GridWritten), layout, 0, 0);
+}
+static int dop853_grid_m_attempt(marl_ctx* ctx, int64_t nb, int layout)
+{
+    for (int s = 1; s <= kDop853GridStages; s++)
+        if (int rc = dop853_grid_stage(ctx, nb, layout, s, 0)) return rc;
+    return 0;
+}
+// (launch_attempt's first reduction level is skipped: the control launcher reduces both of the attempt's sums, in one or two levels)
+static int dop853_grid_m_control(marl_ctx* ctx, const double*, int64_t)
+{
+    return dop853_grid_launched(ctx, marl_dop853_grid_launch_control(ctx->stream, ctx->part, rk_blocks(ctx, kDop853GridWritten), ctx->dctrl));
+}
+static int dop853_grid_m_dense_at(marl_ctx* ctx, int layout, const Rk45Ctrl& c, double t, double* yout, bool want_part, int64_t* nb)
+{
+    const Slab& S = ctx->slab;
+    const int64_t slab5[5] = {S.n_buf, S.goff, S.ld, S.out_lo, S.out_hi};
+    if (ctx->dop_grid_extra != c.n_acc) {   // K_14..K_16 of this step, once (rk.py:520-535); the control kernel has counted them
+        for (int s = kDop853GridStages + 1; s < kDop853GridSlots; s++)
+            if (int rc = dop853_grid_stage(ctx, rk_blocks(ctx, kDop853GridWritten), layout, s, 1)) return rc;
+        ctx->dop_grid_extra = c.n_acc;
+    }
+    *nb = (S.out_hi - S.out_lo + 255) / 256;
+    const int frame = c.cur ^ 1;   // the accepted step's first state and slots
+    return dop853_grid_launched(ctx, marl_dop853_grid_launch_dense(layout == LAYOUT_TILED, (unsigned)*nb, ctx->stream, ctx->buf[frame], ctx->dop_k,
+                                                                   state_doubles(S.n_buf, layout), frame, ctx->dconsts, slab5, c.h_prev,
+                                                                   (t - c.t_old) / c.h_prev, t == c.t_old ? 1 : 0, yout, want_part ? ctx->part : nullptr));
+}
+static const RkMethod kDop853Grid = {"dop853", "marl_sweep_dop853_dev", kDop853GridWritten, false, nullptr, dop853_grid_m_attempt, dop853_grid_m_control,
+                                     nullptr, nullptr, "dop853_grid", true, dop853_grid_m_part_records, dop853_grid_m_first_k, dop853_grid_m_dense_at};
+
+extern "C" {
+int marl_integrate_dop853_grid_dev(marl_ctx* ctx, double* y_dev, int layout, double t0, double t1, double first_step, double rtol,
+                                   double atol, int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk_dev(kDop853Grid, ctx, y_dev, layout, t0, t1, first_step, rtol, atol, max_attempts, stats);
+}
+
+// honours terminal monitors (marl_set_terminal), as marl_integrate_rk45_terminal does
+int marl_integrate_dop853_grid(marl_ctx* ctx, double* y, double t0, double t1, double first_step, double rtol, double atol,
+                               const double* t_eval, int64_t n_eval, double* y_eval, double* t_events, int64_t max_events,
+                               int64_t max_attempts, marl_stats* stats)
+{
+    return integrate_rk(kDop853Grid, ctx, y, t0, t1, first_step, rtol, atol, t_eval, n_eval, y_eval, t_events, max_events, max_attempts, stats, true);
 }
 
 // ---- domain decomposition building blocks --------------------------------------------------------
