@@ -71,7 +71,9 @@ int marl_synchronize(marl_ctx* ctx);
  * caller passed no t_events; they are stored only where a slot is free.  A step that meets no limit runs exactly as without limits.
  * Entries that stop: marl_integrate_radau, marl_integrate_bdf, marl_sweep_radau_dev / _events_dev / _eval_dev,
  * marl_sweep_bdf_terminal_dev, marl_sweep_rk45_terminal_dev / rk23_terminal_dev, marl_integrate_rk45_terminal / rk23_terminal,
- * marl_sweep_dop853_stop_dev, marl_integrate_dop853_stop, marl_integrate_dop853_grid.  Every other
+ * marl_sweep_dop853_stop_dev, marl_integrate_dop853_stop, marl_integrate_dop853_grid; and, by a rule of their own (the end of the step,
+ * no interpolation: see there), marl_sweep_rk4_watch_dev and marl_integrate_rk4_watch.  The plain fixed-step entries
+ * (marl_integrate_rk4, marl_integrate_rk4_dev, marl_sweep_rk4_dev) ignore the limits, as they always did.  Every other
  * integrator entry (marl_integrate_rk45 / rk23, marl_integrate_rk45_dev / rk23_dev, marl_sweep_rk45_dev / _eval_dev / _events_dev and their rk23
  * counterparts, marl_integrate_dop853, marl_sweep_dop853_dev / _eval_dev / _events_dev, marl_integrate_dop853_grid_dev,
  * marl_sweep_bdf_dev / _eval_dev / _events_dev,
@@ -200,6 +202,40 @@ int marl_integrate_rk4(marl_ctx* ctx, double* y, double dt, int64_t nsteps);
 int marl_integrate_rk4_dev(marl_ctx* ctx, double* y_dev, int layout, double dt, int64_t nsteps);
 /* batched sweep: one dt per instance (host array, n_instances entries); FIELD-MAJOR device state */
 int marl_sweep_rk4_dev(marl_ctx* ctx, double* y_dev, const double* dt, int64_t nsteps);
+/* The MONITORED fixed-step sweep (rk4_watch_kernel, csrc/marl_rk4_watch.h; the rules: csrc/marl_rk4_watch_ctl.h): the step of
+ * marl_sweep_rk4_dev with the reference's driver inside the kernel - the seven monitors after every step (Evolve_scenario.py:107-109),
+ * frames, the `terminal` switch (LHeureux_model.py:113-122) - and word that the step was too large.  Grids of one workgroup, N <= 1024
+ * (else -1); no slab contexts.  The three entries above are unchanged and go on ignoring marl_set_terminal.
+ *   steps   step s (0-based) goes from t0 + s dt[b] to t0 + (s + 1) dt[b]; times are that product, never accumulated.  dt: host, one
+ *           per instance.
+ *   roots   a sign change of monitor e in a step (go <= 0 && gn >= 0 or the reverse, ivp.py:149-151) is counted in
+ *           stats[b].n_events[e]; its time  t_s + dt go / (go - gn)  (t_(s+1) when go == gn) is stored in t_events (host,
+ *           [n_instances][7][max_events], NaN beyond the stored ones) while a slot is free.  There is NO dense output and NO Brent: a
+ *           fixed step takes no partial steps, and this secant estimate is O(dt^2) away from the root.  t_events == NULL or
+ *           max_events <= 0: counted only.
+ *   frames  frame_steps: host, n_frames strictly ascending step counts in [0, nsteps], shared by all instances - otherwise -1 before
+ *           anything is touched.  Frame j is the state after frame_steps[j] steps (0: the initial state), written as the kernel passes it
+ *           into frames_dev, device, [n_instances][n_frames][5N] field-major.  n_done (host, may be NULL): frames written per instance;
+ *           frames an instance does not reach are not touched.  n_frames = 0: frame_steps / frames_dev may be NULL.
+ *   stop    marl_set_terminal's limits are honoured: the instance ends at the END of the step in which monitor e has its k[e]-th
+ *           occurrence - status 1, stats[b].t that step's end, the state that step's result, NOT interpolated to the root (a
+ *           deliberate difference from the rule of csrc/marl_terminal.h: there is no dense output to cut the step with).  All sign
+ *           changes of that step are counted and stored, a frame due at it is written.  No limit, or one never met: bit for bit the
+ *           run without limits.
+ *   -2      an instance whose state holds a non-finite value after a step ends there with status -2 (the step was too large):
+ *           stats[b].t that step's end, no monitor processed for that step (event_value: the last finite state's monitors), no frame
+ *           written at it, the state returned as it is.  The other instances are unaffected.
+ *   stats   status 0 / 1 / -2; n_accepted = steps done, n_rejected = 0, nfev = 4 x steps done, h_next = dt, t = t0 + steps dt,
+ *           event_value = the monitors of the returned state, n_events as counted.
+ * Synchronises. */
+int marl_sweep_rk4_watch_dev(marl_ctx* ctx, double* y_dev, double t0, const double* dt, int64_t nsteps, const int64_t* frame_steps,
+                             int64_t n_frames, double* frames_dev, int64_t* n_done, double* t_events, int64_t max_events,
+                             marl_stats* stats);
+/* marl_sweep_rk4_watch_dev for ONE instance with host pointers throughout: y in / out, y_frames [n_frames][5N] (the first *n_done
+ * frames are written), t_events [7][max_events].  Single-instance contexts, N <= 1024. */
+int marl_integrate_rk4_watch(marl_ctx* ctx, double* y, double t0, double dt, int64_t nsteps, const int64_t* frame_steps,
+                             int64_t n_frames, double* y_frames, int64_t* n_done, double* t_events, int64_t max_events,
+                             marl_stats* stats);
 
 /* ---- adaptive Dormand-Prince RK45 ---------------------------------------------------------------
  * Replaces  scipy.integrate.solve_ivp(fun, t_span, y0, method="RK45", first_step=, rtol=, atol=,

@@ -15,6 +15,10 @@ reference (Evolve_scenario.py:19) and returns the same tuple
   ``marl_integrate_dop853_stop``.  Larger grids: ``solver_parms["native_grid"] = True`` takes the large-grid loop, one launch per
   stage, via ``marl_integrate_dop853_grid`` (with a terminal monitor only together with ``native_terminal=True``) - no scipy in
   the loop either.  Without these keys larger grids and terminal monitors take the scipy route below.
+* ``backend == "hip"`` and ``method == "RK4"`` (no counterpart in scipy or the reference): fixed-step classical RK4 with the whole driver
+  inside one kernel via ``marl_integrate_rk4_watch`` - ``solver_parms["dt"]`` is required, ``t_span`` and every ``t_eval`` entry must lie
+  on step ends, N <= 1024; the monitors' root times are secant estimates between step ends (no dense output), ``terminal`` ends the run
+  at the end of the step of the occurrence, and a state that goes non-finite ends it with status -2 (:func:`rk4_schedule`).
 * ``backend == "hip"`` and ``method == "Radau"`` (the reference's default, parameters.py:213): scipy's Radau IIA step
   logic restated natively, with the RHS, the finite-difference Jacobian (the reference's 27-diagonal pattern), the
   block-tridiagonal LU factorisations and every vector operation on the GPU via ``marl_integrate_radau`` - no scipy in the loop.
@@ -62,6 +66,49 @@ def _scipy_events(eq, limits):
     return [make(name, limit) for name, limit in zip(EVENT_NAMES, limits)]
 
 
+RK4_MAX_CELLS = 1024    # the monitored fixed-step loop runs grids of one workgroup
+RK4_ON_GRID = 1e-6      # how far, in steps, a time may lie from a step end
+
+
+def rk4_schedule(solver_parms, t_span, t_eval, N):
+    """``(dt, nsteps, frame_steps)`` of an ``integrate_equations(method="RK4")`` run - a pure function, so that every complaint is
+    raised before a model (and with it a GPU context) exists.  ``solver_parms["dt"]`` is required and positive;
+    ``nsteps = (t1 - t0) / dt`` and every ``t_eval`` entry must lie on a step end, within 1e-6 of a step, the entries strictly
+    ascending within ``t_span``; ``frame_steps`` (None without ``t_eval``) are their step counts.  N > 1024: ValueError."""
+    if int(N) > RK4_MAX_CELLS:
+        raise ValueError(f"method 'RK4': N = {int(N)} exceeds {RK4_MAX_CELLS} cells, the largest grid the monitored fixed-step loop runs "
+                         "(marl_integrate_rk4_watch)")
+    dt = solver_parms.get("dt")
+    if dt is None:
+        raise ValueError("method 'RK4' is a fixed-step method: the solver parameters need 'dt', the step")
+    dt = float(dt)
+    if not (dt > 0.0 and np.isfinite(dt)):
+        raise ValueError(f"method 'RK4': dt = {dt!r} must be positive and finite")
+    t0, t1 = float(t_span[0]), float(t_span[1])
+    if not t1 >= t0:
+        raise ValueError(f"method 'RK4': t_span = ({t0!r}, {t1!r}) must run forward")
+
+    def steps_of(t, what):
+        x = (float(t) - t0) / dt
+        k = int(round(x))
+        if not abs(x - k) <= RK4_ON_GRID:
+            raise ValueError(f"method 'RK4': {what} = {float(t)!r} is not on a step end: (t - t0) / dt = {x!r} with t0 = {t0!r}, dt = {dt!r}")
+        return k
+
+    nsteps = steps_of(t1, "t_span[1]")
+    if t_eval is None:
+        return dt, nsteps, None
+    frame_steps = []
+    for i, t in enumerate(np.asarray(t_eval, dtype=float).ravel()):
+        k = steps_of(t, f"t_eval[{i}]")
+        if k < 0 or k > nsteps:
+            raise ValueError(f"method 'RK4': t_eval[{i}] = {float(t)!r} lies outside t_span = ({t0!r}, {t1!r})")
+        if frame_steps and k <= frame_steps[-1]:
+            raise ValueError(f"method 'RK4': t_eval[{i}] = {float(t)!r} does not follow t_eval[{i - 1}]: the sample times must be strictly ascending")
+        frame_steps.append(k)
+    return dt, nsteps, np.array(frame_steps, dtype=np.int64)
+
+
 def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="../Results/", verbose=True, device=0, terminal=None):
     """``terminal``: the reference's switch (LHeureux_model.py:113-122) - which monitors end the run at their root, as
     :func:`marlpde_amd.LHeureux_model.terminal_counts` reads it.  Native for Radau and BDF; for RK45 / RK23 the solver parameters
@@ -79,6 +126,8 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     if backend != "hip":
         raise ValueError(f"backend {backend!r} is not available here: only 'hip' (MI355X kernels) is implemented; "
                          "use the reference package for its 'numba'/'numpy' CPU backends")
+    if solver_parms.get("method") == "RK4":   # (before the model exists: every complaint about the schedule needs no GPU)
+        rk4_dt, rk4_nsteps, rk4_frames = rk4_schedule(solver_parms, tuple(solver_parms.get("t_span", (0, 1))), tracker_parms.get("t_eval"), N)
     eq = LMAHeureuxPorosityDiff.from_scenario(pde_parms, device=device)
     y0 = eq.get_state(pde_parms["CAIni"], pde_parms["CCIni"], pde_parms["cCaIni"], pde_parms["cCO3Ini"],
                       pde_parms["PhiIni"]).ravel()
@@ -91,7 +140,15 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     scipy_driver = bool(solver_parms.pop("scipy_driver", False))
     native_terminal = bool(solver_parms.pop("native_terminal", False))
     native_grid = bool(solver_parms.pop("native_grid", False))
-    if method in ("RK45", "RK23") and not scipy_driver:
+    if method == "RK4":
+        # fixed-step classical RK4, the driver inside the kernel (marl_integrate_rk4_watch): terminal monitors are honoured directly, at
+        # the end of the step of the occurrence; status -2: the state went non-finite, dt is too large
+        eq.set_terminal(limits)
+        res = eq.integrate_rk4_watch(y0, rk4_dt, rk4_nsteps, t0=t_span[0], frame_steps=rk4_frames)
+        t_out, y_out, t_events = res.t, res.y, res.t_events
+        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
+        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+    elif method in ("RK45", "RK23") and not scipy_driver:
         if any(limits) and not native_terminal:
             eq.close()
             raise ValueError(f"terminal monitors in the {method} loop are opt-in: pass native_terminal=True in the solver parameters for "

@@ -65,7 +65,8 @@ class RK45Result:
         self.message = {0: "The solver successfully reached the end of the integration interval.",
                         1: "A termination event occurred.",
                         -1: "Required step size is less than spacing between numbers.",
-                        2: "Attempt budget exhausted before the end of the interval."}.get(self.status, "?")
+                        2: "Attempt budget exhausted before the end of the interval.",
+                        -2: "The state became non-finite: the fixed step is too large."}.get(self.status, "?")
         self.t_reached = float(stats.t)
         self.h_next = float(stats.h_next)
         self.event_values = np.array(stats.event_value[:])
@@ -269,8 +270,9 @@ class LMAHeureuxPorosityDiff:
         """Make monitors terminal - the reference's ``terminal`` switch (LHeureux_model.py:113-122), for every run of this model from
         now on (marl_set_terminal).  ``spec`` as for :func:`terminal_counts`; None switches it off again.  Radau and BDF single runs,
         Radau, BDF, RK45 and RK23 sweeps and :meth:`integrate_rk45_terminal` / :meth:`integrate_rk23_terminal` end at the root with
-        ``status`` 1; the other integrators (:meth:`integrate_rk45` / :meth:`integrate_rk23` and the ``*_device`` single runs among
-        them) raise while a monitor is terminal."""
+        ``status`` 1; :meth:`sweep_rk4_watch_device` / :meth:`integrate_rk4_watch` end at the END of the step of the occurrence (a fixed
+        step has no dense output to interpolate with) and the plain fixed-step runs ignore the limits; the other integrators
+        (:meth:`integrate_rk45` / :meth:`integrate_rk23` and the ``*_device`` single runs among them) raise while a monitor is terminal."""
         counts = terminal_counts(spec)
         self._check(self._lib.marl_set_terminal(self._ctx, (C.c_int64 * NEVENTS)(*counts)), "marl_set_terminal")
         self._terminal = counts
@@ -371,6 +373,72 @@ class LMAHeureuxPorosityDiff:
         dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, dtype=np.float64), (self.n_instances,)))
         self._check(self._lib.marl_sweep_rk4_dev(self._ctx, C.c_void_p(y_dev_ptr), _as_ptr(dt), int(nsteps)),
                     "marl_sweep_rk4_dev")
+
+    def sweep_rk4_watch_device(self, y_dev_ptr, dt, nsteps, t0=0.0, frame_steps=None, frames_dev_ptr=None, events=False, max_events=64):
+        """:meth:`sweep_rk4_device` with the driver inside the kernel (marl_sweep_rk4_watch_dev; N <= 1024): the seven monitors after
+        every step, frames, terminal monitors (:meth:`set_terminal`) and a stop when the state goes non-finite.  Device states
+        [instances][5N] in place; ``dt`` a scalar or one per instance; step s goes from ``t0 + s dt`` to ``t0 + (s + 1) dt``.
+        Returns one :class:`RK45Result` per instance: ``status`` 0, 1 (a terminal monitor ended the run at the END of its step - the
+        state is that step's result, not interpolated) or -2 (non-finite after a step: ``dt`` too large); ``n_accepted`` the steps done,
+        ``t_reached`` their end, ``event_values`` / ``n_events`` the monitors and their sign changes.
+
+        ``frame_steps``: strictly ascending step counts in [0, nsteps], shared by all instances; frame j is the state after
+        ``frame_steps[j]`` steps, written inside the kernel to ``frames_dev_ptr``, device memory [instances][len(frame_steps)][5N].
+        Each result carries ``t = t0 + frame_steps[:n_frames] * dt``; frames beyond ``n_frames`` are not written.
+
+        ``events=True``: ``t_events``, a list of 7 arrays per instance, ``min(n_events[e], max_events)`` long: the secant estimates
+        ``t_s + dt go / (go - gn)`` of the sign changes - no dense output, no Brent; O(dt^2) from the root."""
+        B = self.n_instances
+        dts = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, dtype=np.float64), (B,)))
+        fs = np.empty(0, dtype=np.int64) if frame_steps is None else np.ascontiguousarray(frame_steps, dtype=np.int64).ravel()
+        if fs.size and not frames_dev_ptr:
+            raise ValueError("sweep_rk4_watch_device: frame_steps needs frames_dev_ptr, device memory [instances][len(frame_steps)][5N]")
+        locate = bool(events) and int(max_events) > 0
+        stats = (MarlStats * B)()
+        n_done = np.zeros(B, dtype=np.int64)
+        tev = np.full((B, NEVENTS, int(max_events)), np.nan) if locate else None
+        rc = self._lib.marl_sweep_rk4_watch_dev(self._ctx, C.c_void_p(y_dev_ptr), float(t0), _as_ptr(dts), int(nsteps),
+                                                _as_ptr(fs) if fs.size else None, fs.size, C.c_void_p(frames_dev_ptr) if fs.size else None,
+                                                _as_ptr(n_done), _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
+        self._check(rc, "marl_sweep_rk4_watch_dev")
+        return [RK45Result(s, t=float(t0) + fs[:int(k)] * dts[b] if frame_steps is not None else None,
+                           t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
+                for b, (s, k) in enumerate(zip(stats, n_done))]
+
+    def integrate_rk4_watch(self, y0, dt, nsteps, t0=0.0, frame_steps=None, events=True, max_events=4096):
+        """:meth:`integrate_rk4` for ONE instance with the driver inside the kernel (marl_integrate_rk4_watch; N <= 1024): see
+        :meth:`sweep_rk4_watch_device` for the rules.  Returns an :class:`RK45Result` whose ``t`` / ``y`` hold the frames the run
+        reached (``y``: (5N, n_frames)) or, without ``frame_steps``, the end point only; ``t_events`` is a list of 7 arrays (every
+        sign change: the run is repeated with a larger buffer when ``max_events`` was too small); ``y_final`` the returned state."""
+        y_start = self._host_state(y0)
+        n = y_start.size
+        fs = np.empty(0, dtype=np.int64) if frame_steps is None else np.ascontiguousarray(frame_steps, dtype=np.int64).ravel()
+        max_events = int(max_events)
+        while True:
+            y = y_start.copy()
+            stats = MarlStats()
+            frames = np.empty((max(fs.size, 1), n))
+            n_done = np.zeros(1, dtype=np.int64)
+            locate = bool(events) and max_events > 0
+            tev = np.full((NEVENTS, max_events), np.nan) if locate else None
+            rc = self._lib.marl_integrate_rk4_watch(self._ctx, _as_ptr(y), float(t0), float(dt), int(nsteps), _as_ptr(fs) if fs.size else None, fs.size,
+                                                    _as_ptr(frames) if fs.size else None, _as_ptr(n_done), _as_ptr(tev) if locate else None,
+                                                    max_events if locate else 0, C.byref(stats))
+            self._check(rc, "marl_integrate_rk4_watch")
+            most = max(stats.n_events[:]) if locate else 0
+            if most <= max_events:
+                break
+            max_events = int(most)
+        t_events = None
+        if events:
+            t_events = [tev[e, :min(int(stats.n_events[e]), max_events)].copy() if locate else np.empty(0) for e in range(NEVENTS)]
+        if frame_steps is not None:
+            k = int(n_done[0])
+            res = RK45Result(stats, float(t0) + fs[:k] * float(dt), frames[:k].T.copy(), t_events)
+        else:
+            res = RK45Result(stats, np.array([stats.t]), y[:, None].copy(), t_events)
+        res.y_final = y
+        return res
 
     def integrate_rk45(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
                        max_attempts=0):

@@ -88,6 +88,8 @@ PROTOTYPES = {
     "marl_integrate_rk4": (_I, [_P, _P, _D, _L]),
     "marl_integrate_rk4_dev": (_I, [_P, _P, _I, _D, _L]),
     "marl_sweep_rk4_dev": (_I, [_P, _P, _P, _L]),
+    "marl_sweep_rk4_watch_dev": (_I, [_P, _P, _D, _P, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
+    "marl_integrate_rk4_watch": (_I, [_P, _P, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
     "marl_integrate_rk45": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
     "marl_integrate_rk45_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
     "marl_sweep_rk45_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),

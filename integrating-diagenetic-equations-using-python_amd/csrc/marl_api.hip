@@ -15,6 +15,7 @@
 #include "../../include/marl_hip.h"
 #include "marl_kernels.h"
 #include "marl_rk23_ctl.h"
+#include "marl_rk4_watch_ctl.h"
 #include "marl_radau.h"
 #include "marl_radau_cr.h"
 #include "marl_radau_batch.h"
@@ -84,6 +85,9 @@ struct marl_ctx {
     // Large-grid DOP853 runs (marl_dop853_grid.h) keep their arena here too: 16 state-shaped buffers in the layout of the state.
     double* dop_k = nullptr;
     size_t dop_k_cap = 0;
+    // monitored RK4 sweeps (marl_rk4_watch.h): the per-instance records, Rk4WatchRec[batch] as doubles, then the seven terminal limits; allocated on first use
+    double* rk4w_recs = nullptr;
+    size_t rk4w_recs_cap = 0;
     int64_t dop_grid_extra = -1;   // large-grid DOP853: the accepted step (its n_acc) whose extra stages K14..K16 lie in the arena; -1: none
     // domain decomposition: this rank's message / the gathered messages (device), and the RCCL communicator (dlopen'ed API)
     double* dd_send = nullptr;
@@ -374,6 +378,7 @@ void marl_ctx_destroy(marl_ctx* ctx)
     if (ctx->sw_ndone) (void)hipFree(ctx->sw_ndone);
     if (ctx->sw_tev) (void)hipFree(ctx->sw_tev);
     if (ctx->dop_k) (void)hipFree(ctx->dop_k);
+    if (ctx->rk4w_recs) (void)hipFree(ctx->rk4w_recs);
     if (ctx->rccl_comm && ctx->rccl_destroy) (void)ctx->rccl_destroy(ctx->rccl_comm);
     if (ctx->dd_send) (void)hipFree(ctx->dd_send);
     if (ctx->dd_gathered) (void)hipFree(ctx->dd_gathered);
@@ -1516,6 +1521,97 @@ int marl_integrate_rk4(marl_ctx* ctx, double* y, double dt, int64_t nsteps)
     HIP_OK(ctx, hipMemcpyAsync(y, ctx->buf[2], n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
     return stream_check(ctx);
+}
+
+// ---- monitored fixed-step RK4, grids of one workgroup (include/marl_hip.h; kernel: marl_rk4_watch.h, a translation unit of its own;
+// rules and record: marl_rk4_watch_ctl.h) ----
+int marl_rk4_watch_launch(int blk, int vd, unsigned grid, hipStream_t stream, double* Y, const void* consts, void* recs, int64_t N, int64_t nsteps,
+                          const int64_t* frame_steps, int64_t n_frames, double* frames, double* t_events, int64_t max_events, const int64_t* terminal);
+
+static void rk4_watch_to_stats(const Rk4WatchRec& r, marl_stats* st)
+{
+    memset(st, 0, sizeof *st);
+    st->nfev = 4 * r.steps;
+    st->n_accepted = r.steps;
+    st->status = r.status;
+    st->t = r.t;
+    st->h_next = r.dt;
+    for (int e = 0; e < 7; e++) { st->event_value[e] = r.g[e]; st->n_events[e] = r.n_events[e]; }
+}
+
+int marl_sweep_rk4_watch_dev(marl_ctx* ctx, double* y_dev, double t0, const double* dt, int64_t nsteps, const int64_t* frame_steps, int64_t n_frames,
+                             double* frames_dev, int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
+{
+    if (!ctx || !y_dev || !dt || !stats || nsteps < 0 || n_frames < 0 || (n_frames > 0 && (!frame_steps || !frames_dev)))
+        return ctx ? fail(ctx, -1, "marl_sweep_rk4_watch_dev: invalid argument") : -1;
+    if (ctx->halo > 0) return fail(ctx, -1, "marl_sweep_rk4_watch_dev: slab contexts (domain decomposition) are not supported");
+    const int blk = sweep_block(ctx);
+    if (!blk)
+        return fail(ctx, -1, "marl_sweep_rk4_watch_dev: N = %lld exceeds the largest one-workgroup window: the monitored RK4 loop runs N <= 1024 cells",
+                    (long long)ctx->N);
+    if (const int64_t bad = rk4_watch_check_frames(frame_steps, n_frames, nsteps); bad >= 0)
+        return fail(ctx, -1, "marl_sweep_rk4_watch_dev: frame_steps[%lld] = %lld: the step counts must be strictly ascending within [0, nsteps = %lld]",
+                    (long long)bad, (long long)frame_steps[bad], (long long)nsteps);
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    const bool roots = t_events && max_events > 0;
+    const size_t B = (size_t)ctx->batch, n_tev = roots ? B * 7 * (size_t)max_events : 0;
+    static_assert(sizeof(Rk4WatchRec) % sizeof(double) == 0 && sizeof(int64_t) == sizeof(double), "the records and step counts live in buffers of doubles");
+    if (int rc = grow_dev(ctx, &ctx->rk4w_recs, &ctx->rk4w_recs_cap, B * (sizeof(Rk4WatchRec) / sizeof(double)) + 7)) return rc;
+    if (n_frames > 0)
+        if (int rc = grow_dev(ctx, &ctx->sw_teval, &ctx->sw_teval_cap, (size_t)n_frames)) return rc;
+    if (roots) {
+        if (int rc = grow_dev(ctx, &ctx->sw_tev, &ctx->sw_tev_cap, n_tev)) return rc;
+        HIP_OK(ctx, hipMemsetAsync(ctx->sw_tev, 0xff, sizeof(double) * n_tev, ctx->stream));   // NaN beyond the roots stored
+    }
+    std::vector<Rk4WatchRec> recs(B);
+    memset(recs.data(), 0, sizeof(Rk4WatchRec) * B);
+    for (size_t b = 0; b < B; b++) { recs[b].t0 = recs[b].t = t0; recs[b].dt = dt[b]; }
+    // (pageable host memory: the copies have left the vector and the caller's array when the calls return)
+    HIP_OK(ctx, hipMemcpyAsync(ctx->rk4w_recs, recs.data(), sizeof(Rk4WatchRec) * B, hipMemcpyHostToDevice, ctx->stream));
+    if (n_frames > 0) HIP_OK(ctx, hipMemcpyAsync(ctx->sw_teval, frame_steps, sizeof(int64_t) * n_frames, hipMemcpyHostToDevice, ctx->stream));
+    int64_t* dlim = reinterpret_cast<int64_t*>(ctx->rk4w_recs + B * (sizeof(Rk4WatchRec) / sizeof(double)));   // the limits, behind the records
+    if (has_terminal(ctx)) HIP_OK(ctx, hipMemcpyAsync(dlim, ctx->terminal, sizeof(int64_t) * 7, hipMemcpyHostToDevice, ctx->stream));
+    const int err = marl_rk4_watch_launch(blk, ctx->var_dphi ? 1 : 0, (unsigned)ctx->batch, ctx->stream, y_dev, ctx->dconsts, ctx->rk4w_recs, ctx->N, nsteps,
+                                          n_frames > 0 ? reinterpret_cast<const int64_t*>(ctx->sw_teval) : nullptr, n_frames, frames_dev,
+                                          roots ? ctx->sw_tev : nullptr, roots ? max_events : 0, has_terminal(ctx) ? dlim : nullptr);
+    if (err != (int)hipSuccess) return fail(ctx, -3, "rk4 watch: kernel launch failed: %s", hipGetErrorString((hipError_t)err));
+    HIP_OK(ctx, hipMemcpyAsync(recs.data(), ctx->rk4w_recs, sizeof(Rk4WatchRec) * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (roots) HIP_OK(ctx, hipMemcpyAsync(t_events, ctx->sw_tev, sizeof(double) * n_tev, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t b = 0; b < B; b++) {
+        rk4_watch_to_stats(recs[b], &stats[b]);
+        if (n_done) n_done[b] = recs[b].next_frame;
+    }
+    return 0;
+}
+
+int marl_integrate_rk4_watch(marl_ctx* ctx, double* y, double t0, double dt, int64_t nsteps, const int64_t* frame_steps, int64_t n_frames,
+                             double* y_frames, int64_t* n_done, double* t_events, int64_t max_events, marl_stats* stats)
+{
+    if (!ctx || !y || !stats || nsteps < 0 || n_frames < 0 || (n_frames > 0 && (!frame_steps || !y_frames)))
+        return ctx ? fail(ctx, -1, "marl_integrate_rk4_watch: invalid argument") : -1;
+    if (ctx->batch != 1) return fail(ctx, -1, "marl_integrate_rk4_watch: single-instance context required (use marl_sweep_rk4_watch_dev)");
+    if (!sweep_block(ctx))
+        return fail(ctx, -1, "marl_integrate_rk4_watch: N = %lld exceeds the largest one-workgroup window: the monitored RK4 loop runs N <= 1024 cells",
+                    (long long)ctx->N);
+    if (const int64_t bad = rk4_watch_check_frames(frame_steps, n_frames, nsteps); bad >= 0)
+        return fail(ctx, -1, "marl_integrate_rk4_watch: frame_steps[%lld] = %lld: the step counts must be strictly ascending within [0, nsteps = %lld]",
+                    (long long)bad, (long long)frame_steps[bad], (long long)nsteps);
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)NF * ctx->N;
+    if (int rc = ensure(ctx, 2, n)) return rc;
+    if (n_frames > 0)
+        if (int rc = ensure(ctx, 3, n * (size_t)n_frames)) return rc;
+    HIP_OK(ctx, hipMemcpyAsync(ctx->buf[2], y, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    int64_t done = 0;
+    if (int rc = marl_sweep_rk4_watch_dev(ctx, ctx->buf[2], t0, &dt, nsteps, frame_steps, n_frames, n_frames > 0 ? ctx->buf[3] : nullptr, &done, t_events,
+                                          max_events, stats))
+        return rc;
+    HIP_OK(ctx, hipMemcpyAsync(y, ctx->buf[2], n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (done > 0) HIP_OK(ctx, hipMemcpyAsync(y_frames, ctx->buf[3], n * (size_t)done * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_done) *n_done = done;
+    return 0;
 }
 
 int marl_sweep_rk45_dev(marl_ctx* ctx, double* y_dev, double t0, double t1, double first_step, double rtol, double atol,

@@ -215,6 +215,26 @@ class HipSweepEngine:
         self.torch.cuda.synchronize(self.device)
         return yd.cpu().numpy()
 
+    def integrate_rk4_watch(self, y0, dt, nsteps, t0=0.0, frame_steps=None, events=False, max_events=64, terminal=None):
+        """Fixed-step RK4 with the driver inside the kernel (marl_sweep_rk4_watch_dev; N <= 1024): y0 (n_local, 5N) host array, ``dt`` a
+        scalar or one per local instance.  Returns (y_final (n_local, 5N), list of RK45Result) like :meth:`integrate_rk45`: with
+        ``frame_steps`` every result carries the frames that instance reached, ``t`` (n_t,) and ``y`` (5N, n_t); with ``events`` the
+        root estimates ``t_events``.  ``terminal`` as for :meth:`integrate_radau`, by the fixed-step rule: the instance ends at the END
+        of the step of the terminal occurrence (status 1).  Status -2: the state went non-finite, the step is too large."""
+        self.model.set_terminal(terminal)
+        yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
+        more = {"events": True, "max_events": max_events} if events else {}
+        if frame_steps is None:
+            res = self.model.sweep_rk4_watch_device(yd.data_ptr(), dt, nsteps, t0=t0, **more)
+            return yd.cpu().numpy(), res
+        n_frames = int(np.size(frame_steps))
+        frames = self.torch.empty((yd.shape[0], max(n_frames, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
+        res = self.model.sweep_rk4_watch_device(yd.data_ptr(), dt, nsteps, t0=t0, frame_steps=frame_steps, frames_dev_ptr=frames.data_ptr(), **more)
+        frames = frames.cpu().numpy()
+        for b, r in enumerate(res):
+            r.y = frames[b, :len(r.t)].T.copy()
+        return yd.cpu().numpy(), res
+
     def close(self):
         if self._model is not None:
             self._model.close()
@@ -308,8 +328,32 @@ def run_sweep_dop853_stop(base_parms, instances, t_span, first_step, rtol, atol,
                       gather, balance, cost, t_eval, events, max_events, terminal=terminal)
 
 
+def run_sweep_rk4(base_parms, instances, dt, nsteps, t0=0.0, y0=None, group=None, device=None, engine_factory=None, gather=True,
+                  balance="contiguous", cost=None, frame_steps=None, events=False, max_events=64, terminal=None):
+    """As :func:`run_sweep_rk45` with fixed-step classical RK4 and the driver inside the kernel (grids of up to 1024 cells;
+    :meth:`HipSweepEngine.integrate_rk4_watch`): ``nsteps`` steps of ``dt`` - a scalar or one per instance - from ``t0``; every instance
+    costs the same, so contiguous shards.  The returned tuple has the layout of :func:`run_sweep_rk45`:
+    ``(y_final, status, n_steps, zeros, t_reached)``; with ``frame_steps`` (strictly ascending step counts in [0, nsteps], the same for
+    every instance) ``n_frames`` and ``y_frames`` of shape (instances, len(frame_steps), 5N) follow - frame j the state after
+    ``frame_steps[j]`` steps, NaN beyond an instance's ``n_frames``; with ``events`` one last element, ``t_events``: the secant estimates
+    of the monitors' sign changes (no dense output: O(dt^2) from the root), at most ``max_events`` each.
+    ``status``: 0, 1 - a terminal monitor (``terminal``, handed to the engine only when given) ended the instance at the END of the step
+    of its occurrence - or -2: the state went non-finite after ``n_steps`` steps, ``dt`` is too large for that instance."""
+    dts = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, dtype=np.float64), (len(instances),)))
+    fs = None if frame_steps is None else np.ascontiguousarray(frame_steps, dtype=np.int64).ravel()
+
+    def call(engine, y0_local, mine, more):
+        kw = {k: v for k, v in more.items() if k != "t_eval"}
+        if fs is not None:
+            kw["frame_steps"] = fs
+        return engine.integrate_rk4_watch(y0_local, dts[mine], int(nsteps), t0=t0, **kw)
+
+    return _run_sweep("integrate_rk4_watch", base_parms, instances, None, None, None, None, 0, y0, group, device, engine_factory, gather,
+                      balance, cost, fs, events, max_events, terminal=terminal, call=call)
+
+
 def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, max_attempts, y0, group, device, engine_factory, gather,
-               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64, batched=False, terminal=None):
+               balance="contiguous", cost=None, t_eval=None, events=False, max_events=64, batched=False, terminal=None, call=None):
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
@@ -336,7 +380,10 @@ def _run_sweep(method, base_parms, instances, t_span, first_step, rtol, atol, ma
             more |= {"batched": True}
         if terminal is not None:   # (passed only when asked for)
             more |= {"terminal": terminal}
-        y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
+        if call is not None:   # (run_sweep_rk4: a fixed-step engine method takes other arguments; t_eval stands for its frame list)
+            y, res = call(engine, y0[mine], mine, more)
+        else:
+            y, res = getattr(engine, method)(y0[mine], t_span, first_step, rtol, atol, max_attempts, **more)
         engine.close()
     else:   # (more ranks than instances)
         y, res = np.empty((0,) + y0.shape[1:]), []
