@@ -140,14 +140,15 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
     scipy_driver = bool(solver_parms.pop("scipy_driver", False))
     native_terminal = bool(solver_parms.pop("native_terminal", False))
     native_grid = bool(solver_parms.pop("native_grid", False))
+    # A native route is chosen here and run once below: (the model's method, its arguments after y0 - None: the adaptive methods'
+    # (t_span, first_step, rtol, atol, t_eval=) -, further keyword arguments, whether the limits go to the library first, the statuses
+    # let through - None: all; 1: a terminal monitor ended the run at t_reached -, whether njev / nlu come from the result)
+    native = None
+    can_stop, cannot_stop = (0, 1, -1), (0, -1)
     if method == "RK4":
         # fixed-step classical RK4, the driver inside the kernel (marl_integrate_rk4_watch): terminal monitors are honoured directly, at
         # the end of the step of the occurrence; status -2: the state went non-finite, dt is too large
-        eq.set_terminal(limits)
-        res = eq.integrate_rk4_watch(y0, rk4_dt, rk4_nsteps, t0=t_span[0], frame_steps=rk4_frames)
-        t_out, y_out, t_events = res.t, res.y, res.t_events
-        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
-        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+        native = (eq.integrate_rk4_watch, (rk4_dt, rk4_nsteps), {"t0": t_span[0], "frame_steps": rk4_frames}, True, None, False)
     elif method in ("RK45", "RK23") and not scipy_driver:
         if any(limits) and not native_terminal:
             eq.close()
@@ -155,45 +156,21 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
                              "the native loop (marl_integrate_rk45_terminal / rk23_terminal) or scipy_driver=True for solve_ivp on the "
                              "HIP RHS, or use method 'Radau' or 'BDF'")
         if any(limits):
-            eq.set_terminal(limits)
             integrate = eq.integrate_rk45_terminal if method == "RK45" else eq.integrate_rk23_terminal
         else:
             integrate = eq.integrate_rk45 if method == "RK45" else eq.integrate_rk23
-        res = integrate(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"],
-                        t_eval=t_eval)
-        t_out, y_out, t_events = res.t, res.y, res.t_events
-        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
-        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the implicit branch)
-            status = -1
-        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+        native = (integrate, None, {}, any(limits), can_stop, False)
     elif method == "DOP853" and not scipy_driver and N <= 1024 and not any(limits):
         # the native loop covers grids of one workgroup; with a terminal monitor it is opt-in (the next branch), and everything else
         # keeps the scipy route below
-        res = eq.integrate_dop853(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
-        t_out, y_out, t_events = res.t, res.y, res.t_events
-        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
-        if status not in (0, -1):
-            status = -1
-        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+        native = (eq.integrate_dop853, None, {}, False, cannot_stop, False)
     elif method == "DOP853" and not scipy_driver and N <= 1024 and native_terminal:
         # a terminal monitor and native_terminal=True: the native loop stops itself (marl_integrate_dop853_stop)
-        eq.set_terminal(limits)
-        res = eq.integrate_dop853_stop(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
-        t_out, y_out, t_events = res.t, res.y, res.t_events
-        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
-        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the RK45 branch)
-            status = -1
-        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+        native = (eq.integrate_dop853_stop, None, {}, True, can_stop, False)
     elif method == "DOP853" and not scipy_driver and N > 1024 and native_grid and (native_terminal or not any(limits)):
         # a grid above one workgroup and native_grid=True: the large-grid loop, one launch per stage (marl_integrate_dop853_grid); it
         # stops itself at a terminal monitor's root, which stays opt-in (native_terminal=True) as everywhere
-        eq.set_terminal(limits)
-        res = eq.integrate_dop853_grid(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval)
-        t_out, y_out, t_events = res.t, res.y, res.t_events
-        nfev, njev, nlu, status, message = res.nfev, 0, 0, res.status, res.message
-        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached, as in the RK45 branch)
-            status = -1
-        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+        native = (eq.integrate_dop853_grid, None, {}, True, can_stop, False)
     elif method in ("Radau", "BDF") and not scipy_driver:
         # the reference's default: the whole implicit loop on the GPU (marl_integrate_radau).  The Jacobian pattern is the
         # reference's (parameters.py:150-199); when the caller's jac_sparsity has the matching shape its scipy column grouping
@@ -205,13 +182,7 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
             from scipy.sparse import csc_matrix
             groups = group_columns(csc_matrix(sp))
         integrate = eq.integrate_radau if method == "Radau" else eq.integrate_bdf   # (marl_integrate_bdf: the same machinery, scipy's BDF step logic)
-        eq.set_terminal(limits)
-        res = integrate(y0, t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"], t_eval=t_eval, groups=groups)
-        t_out, y_out, t_events = res.t, res.y, res.t_events
-        nfev, njev, nlu, status, message = res.nfev, res.njev, res.nlu, res.status, res.message
-        if status not in (0, 1, -1):   # (1: a terminal monitor ended the run at t_reached - without t_eval the state there is the last profile)
-            status = -1
-        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
+        native = (integrate, None, {"groups": groups}, True, can_stop, True)   # (stopped without t_eval: the state at the root is the last profile)
     else:
         from scipy.integrate import solve_ivp
         # the reference forwards every remaining Solver key to solve_ivp; keep only what the method takes
@@ -228,6 +199,17 @@ def integrate_equations(solver_parms, tracker_parms, pde_parms, results_root="..
             covered = Tstar * max(float(te[-1]) for te in t_events if len(te))
         else:
             covered = Tstar * t_span[1] if status == 0 else bar.n * Tstar * t_span[1] / no_progress_updates
+    if native is not None:
+        integrate, args, more, stops, allowed, implicit = native
+        if stops:
+            eq.set_terminal(limits)
+        if args is None:
+            args, more = (t_span, solver_parms["first_step"], solver_parms["rtol"], solver_parms["atol"]), {"t_eval": t_eval, **more}
+        res = integrate(y0, *args, **more)
+        t_out, y_out, t_events = res.t, res.y, res.t_events
+        nfev, njev, nlu = res.nfev, res.njev if implicit else 0, res.nlu if implicit else 0
+        status, message = res.status if allowed is None or res.status in allowed else -1, res.message
+        covered = Tstar * (t_span[1] if status == 0 else res.t_reached)
     wall = time.time() - start
 
     if verbose:

@@ -106,6 +106,118 @@ def terminal_counts(spec):
     return tuple(one(v, name) for v, name in zip(spec, EVENT_NAMES))
 
 
+# -- the one marshalling of the integrators' entries ------------------------------------------------------------------------------------
+# Plain functions of a model-like object `m`: they use its _lib, _ctx, _check, n_instances and terminal only, so that tests can run
+# them on stand-ins.  A new solver family chooses its entry ("The Python host layer") and calls these.
+def _run_head(m, y_ptr, t_span, first_step, rtol, atol):
+    """What every adaptive entry's argument list begins with."""
+    return (m._ctx, y_ptr, float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol))
+
+
+def _groups(groups, n=None):
+    """The column-grouping argument of the implicit entries: a pointer to the int32 array, which it keeps alive (None: the library's
+    structured colouring).  ``n``: the number of entries to insist on."""
+    if groups is None:
+        return None
+    grp = np.ascontiguousarray(groups, dtype=np.int32)
+    if n is not None and grp.size != n:
+        raise ValueError(f"groups has {grp.size} entries, expected {n}")
+    return _as_ptr(grp)
+
+
+def _root_buffer(shape, max_events):
+    return np.full(shape + (NEVENTS, int(max_events)), np.nan)
+
+
+def _root_times(tev, n_events):
+    """The seven arrays of root times an entry left in its rows of ``tev``: ``min(n_events[e], max_events)`` each."""
+    return [tev[e, :min(int(n_events[e]), tev.shape[1])].copy() for e in range(NEVENTS)]
+
+
+def _sweep_results(stats, te=None, n_done=None, tev=None):
+    """One :class:`RK45Result` per instance of a sweep: ``t`` the samples ``te[:n_done[b]]`` it reached (None without ``te``),
+    ``t_events`` its root times (None without the root buffer ``tev``)."""
+    return [RK45Result(s, t=None if te is None else te[:int(n_done[b])].copy(), t_events=None if tev is None else _root_times(tev[b], s.n_events))
+            for b, s in enumerate(stats)]
+
+
+def _sweep_call(m, family, entry, head, takes, t_eval=None, y_eval_dev_ptr=None, tev=None):
+    """Call the sweep entry ``entry`` and build its results.  ``head``: the arguments up to ``max_attempts``.  ``takes`` says which
+    argument groups the entry has between ``head`` and ``stats``: "samples" - (t_eval, n_eval, y_eval, n_frames), None / 0 / None
+    where ``t_eval`` is None or empty; "roots" - (t_events, max_events) from the root buffer ``tev``, None / 0 without one."""
+    B = m.n_instances
+    stats = (MarlStats * B)()
+    args, te, n_done = list(head), None, None
+    if "samples" in takes:
+        te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
+        if te.size and not y_eval_dev_ptr:
+            raise ValueError(f"sweep_{family}_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
+        n_done = np.zeros(B, dtype=np.int64)
+        args += [_as_ptr(te) if te.size else None, te.size, C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done)]
+    if "roots" in takes:
+        args += [_as_ptr(tev), tev.shape[2]] if tev is not None else [None, 0]
+    m._check(getattr(m._lib, entry)(*args, stats), entry)
+    return _sweep_results(stats, None if t_eval is None else te, n_done, tev)
+
+
+def _sweep_choose(m, family, terminal_entry, head, t_eval, y_eval_dev_ptr, events, max_events):
+    """The entry choice of the explicit families and BDF.  While a monitor is terminal: ``terminal_entry``, where the family has one
+    (else the entries below, which refuse the call).  Otherwise marl_sweep_<family>_dev when there is neither ``t_eval`` nor a root to
+    locate (``events`` with room for one), _events_dev when roots are to be located, _eval_dev when not."""
+    locate = bool(events) and int(max_events) > 0
+    if terminal_entry and any(m.terminal):
+        entry, takes = terminal_entry, ("samples", "roots")
+    elif t_eval is None and not locate:
+        entry, takes = f"marl_sweep_{family}_dev", ()
+    elif locate:
+        entry, takes = f"marl_sweep_{family}_events_dev", ("samples", "roots")
+    else:
+        entry, takes = f"marl_sweep_{family}_eval_dev", ("samples",)
+    return _sweep_call(m, family, entry, head, takes, t_eval, y_eval_dev_ptr, _root_buffer((m.n_instances,), max_events) if locate else None)
+
+
+def _with_room(run, max_events):
+    """``run(max_events) -> (what it made, the largest sign-change count)``, repeated with a larger root buffer until every root time
+    fits: solve_ivp returns EVERY root time (a monitor sitting at exactly 0 fires on every accepted step), and the run is
+    deterministic.  Returns what the last run made."""
+    while True:
+        made, most = run(max_events)
+        if most <= max_events:
+            return made
+        max_events = int(most)
+
+
+def _single_result(stats, y, t_events, t=None, frames=None):
+    """The :class:`RK45Result` of a single run that ended in state ``y``: the samples ``t`` / ``frames`` (rows) it reached or, without
+    them, the end point only."""
+    res = RK45Result(stats, np.array([stats.t]), y[:, None].copy(), t_events) if t is None else RK45Result(stats, t, frames.T.copy(), t_events)
+    res.y_final = y
+    return res
+
+
+def _single_run(m, entry, y_start, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts, grp=()):
+    """The single-run driver of every adaptive entry (``grp``: the implicit entries' groups argument, as a 1-tuple)."""
+    n = y_start.size
+    te = None if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64)
+    n_eval = 0 if te is None else te.size
+
+    def run(max_events):
+        y, stats, y_eval = y_start.copy(), MarlStats(), np.empty((max(n_eval, 1), n))
+        tev = _root_buffer((), max_events) if events else None
+        rc = getattr(m._lib, entry)(
+            *_run_head(m, _as_ptr(y), t_span, first_step, rtol, atol), *grp, _as_ptr(te) if n_eval else None, n_eval,
+            _as_ptr(y_eval) if n_eval else None, _as_ptr(tev) if events else None, max_events if events else 0, int(max_attempts), C.byref(stats))
+        m._check(rc, entry)
+        return (y, stats, y_eval, tev), max(stats.n_events[:]) if events else 0
+
+    y, stats, y_eval, tev = _with_room(run, max_events)
+    t_events = _root_times(tev, stats.n_events) if events else None
+    if not n_eval:
+        return _single_result(stats, y, t_events)
+    k = int(np.searchsorted(te, stats.t, side="right"))
+    return _single_result(stats, y, t_events, te[:k].copy(), y_eval[:k])
+
+
 def pack_blocks(instances, length):
     """The marl_params blocks (include/marl_params.h) of a list of instances (constructor-keyword dicts) on a column of `length`:
     what marl_ctx_create / marl_ctx_set_params receive.  A pure function of its arguments - a rank's blocks are the corresponding
@@ -396,14 +508,16 @@ class LMAHeureuxPorosityDiff:
         locate = bool(events) and int(max_events) > 0
         stats = (MarlStats * B)()
         n_done = np.zeros(B, dtype=np.int64)
-        tev = np.full((B, NEVENTS, int(max_events)), np.nan) if locate else None
+        tev = _root_buffer((B,), max_events) if locate else None
         rc = self._lib.marl_sweep_rk4_watch_dev(self._ctx, C.c_void_p(y_dev_ptr), float(t0), _as_ptr(dts), int(nsteps),
                                                 _as_ptr(fs) if fs.size else None, fs.size, C.c_void_p(frames_dev_ptr) if fs.size else None,
                                                 _as_ptr(n_done), _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
         self._check(rc, "marl_sweep_rk4_watch_dev")
-        return [RK45Result(s, t=float(t0) + fs[:int(k)] * dts[b] if frame_steps is not None else None,
-                           t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
-                for b, (s, k) in enumerate(zip(stats, n_done))]
+        res = _sweep_results(stats, fs if frame_steps is not None else None, n_done, tev)
+        for r, h in zip(res, dts):
+            if frame_steps is not None:
+                r.t = float(t0) + r.t * h      # (the frames it reached, as step counts so far)
+        return res
 
     def integrate_rk4_watch(self, y0, dt, nsteps, t0=0.0, frame_steps=None, events=True, max_events=4096):
         """:meth:`integrate_rk4` for ONE instance with the driver inside the kernel (marl_integrate_rk4_watch; N <= 1024): see
@@ -413,32 +527,24 @@ class LMAHeureuxPorosityDiff:
         y_start = self._host_state(y0)
         n = y_start.size
         fs = np.empty(0, dtype=np.int64) if frame_steps is None else np.ascontiguousarray(frame_steps, dtype=np.int64).ravel()
-        max_events = int(max_events)
-        while True:
-            y = y_start.copy()
-            stats = MarlStats()
-            frames = np.empty((max(fs.size, 1), n))
-            n_done = np.zeros(1, dtype=np.int64)
+
+        def run(max_events):
+            y, stats, frames, n_done = y_start.copy(), MarlStats(), np.empty((max(fs.size, 1), n)), np.zeros(1, dtype=np.int64)
             locate = bool(events) and max_events > 0
-            tev = np.full((NEVENTS, max_events), np.nan) if locate else None
+            tev = _root_buffer((), max_events) if locate else None
             rc = self._lib.marl_integrate_rk4_watch(self._ctx, _as_ptr(y), float(t0), float(dt), int(nsteps), _as_ptr(fs) if fs.size else None, fs.size,
                                                     _as_ptr(frames) if fs.size else None, _as_ptr(n_done), _as_ptr(tev) if locate else None,
                                                     max_events if locate else 0, C.byref(stats))
             self._check(rc, "marl_integrate_rk4_watch")
-            most = max(stats.n_events[:]) if locate else 0
-            if most <= max_events:
-                break
-            max_events = int(most)
+            return (y, stats, frames, int(n_done[0]), tev), max(stats.n_events[:]) if locate else 0
+
+        y, stats, frames, k, tev = _with_room(run, int(max_events))
         t_events = None
-        if events:
-            t_events = [tev[e, :min(int(stats.n_events[e]), max_events)].copy() if locate else np.empty(0) for e in range(NEVENTS)]
-        if frame_steps is not None:
-            k = int(n_done[0])
-            res = RK45Result(stats, float(t0) + fs[:k] * float(dt), frames[:k].T.copy(), t_events)
-        else:
-            res = RK45Result(stats, np.array([stats.t]), y[:, None].copy(), t_events)
-        res.y_final = y
-        return res
+        if events:      # (without room for a root nothing is located: seven empty arrays)
+            t_events = _root_times(tev, stats.n_events) if tev is not None else [np.empty(0) for _ in range(NEVENTS)]
+        if frame_steps is None:
+            return _single_result(stats, y, t_events)
+        return _single_result(stats, y, t_events, float(t0) + fs[:k] * float(dt), frames[:k])
 
     def integrate_rk45(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096,
                        max_attempts=0):
@@ -494,37 +600,7 @@ class LMAHeureuxPorosityDiff:
         return self._integrate_rk("dop853_grid", y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
     def _integrate_rk(self, method, y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts):
-        entry = getattr(self._lib, f"marl_integrate_{method}")
-        y_start = self._host_state(y0)
-        n = y_start.size
-        te = None if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64)
-        n_eval = 0 if te is None else te.size
-        while True:
-            y = y_start.copy()
-            stats = MarlStats()
-            y_eval = np.empty((max(n_eval, 1), n))
-            tev = np.full((NEVENTS, max_events), np.nan) if events else None
-            rc = entry(
-                self._ctx, _as_ptr(y), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
-                _as_ptr(te) if n_eval else None, n_eval, _as_ptr(y_eval) if n_eval else None,
-                _as_ptr(tev) if events else None, max_events if events else 0, int(max_attempts), C.byref(stats))
-            self._check(rc, f"marl_integrate_{method}")
-            most = max(stats.n_events[:]) if events else 0
-            if most <= max_events:
-                break
-            # solve_ivp returns EVERY root time (a monitor sitting at exactly 0 fires on every accepted step): the run is
-            # deterministic, so repeat it with a buffer that holds them all
-            max_events = int(most)
-        t_events = None
-        if events:
-            t_events = [tev[e, :min(int(stats.n_events[e]), max_events)].copy() for e in range(NEVENTS)]
-        if n_eval:
-            k = int(np.searchsorted(te, stats.t, side="right"))
-            res = RK45Result(stats, te[:k].copy(), y_eval[:k].T.copy(), t_events)
-        else:
-            res = RK45Result(stats, np.array([stats.t]), y[:, None].copy(), t_events)
-        res.y_final = y
-        return res
+        return _single_run(self, f"marl_integrate_{method}", self._host_state(y0), t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts)
 
     def integrate_radau(self, y0, t_span, first_step, rtol, atol, t_eval=None, events=True, max_events=4096, max_attempts=0,
                         groups=None):
@@ -544,34 +620,8 @@ class LMAHeureuxPorosityDiff:
 
     def _integrate_implicit(self, entry, y0, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts, groups):
         y_start = self._host_state(y0)
-        n = y_start.size
-        te = None if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64)
-        n_eval = 0 if te is None else te.size
-        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        if grp is not None and grp.size != n:
-            raise ValueError(f"groups has {grp.size} entries, expected {n}")
-        while True:
-            y = y_start.copy()
-            stats = MarlStats()
-            y_eval = np.empty((max(n_eval, 1), n))
-            tev = np.full((NEVENTS, max_events), np.nan) if events else None
-            rc = getattr(self._lib, entry)(
-                self._ctx, _as_ptr(y), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
-                _as_ptr(grp) if grp is not None else None, _as_ptr(te) if n_eval else None, n_eval, _as_ptr(y_eval) if n_eval else None,
-                _as_ptr(tev) if events else None, max_events if events else 0, int(max_attempts), C.byref(stats))
-            self._check(rc, entry)
-            most = max(stats.n_events[:]) if events else 0
-            if most <= max_events:
-                break
-            max_events = int(most)     # scipy returns every root time: repeat the (deterministic) run with room for all
-        t_events = [tev[e, :int(stats.n_events[e])].copy() for e in range(NEVENTS)] if events else None
-        if n_eval:
-            k = int(np.searchsorted(te, stats.t, side="right"))
-            res = RK45Result(stats, te[:k].copy(), y_eval[:k].T.copy(), t_events)
-        else:
-            res = RK45Result(stats, np.array([stats.t]), y[:, None].copy(), t_events)
-        res.y_final = y
-        return res
+        return _single_run(self, entry, y_start, t_span, first_step, rtol, atol, t_eval, events, max_events, max_attempts,
+                           grp=(_groups(groups, y_start.size),))
 
     # -- test hooks of the implicit path -------------------------------------------------------------------
     def debug_num_jac(self, y, threshold, groups=None, factor=None):
@@ -580,15 +630,13 @@ class LMAHeureuxPorosityDiff:
         device layout (N, 3, 5, 5) - ``J[i, d, f, fp]`` = d rate(f, i) / d y(fp, i + d - 1) - and the adapted factors (5N, field-major)."""
         y = self._host_state(y)
         n, N = y.size, self.Depths.N
-        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        if grp is not None and grp.size != n:
-            raise ValueError(f"groups has {grp.size} entries, expected {n}")
+        grp = _groups(groups, n)
         fac = np.zeros(n) if factor is None else np.array(factor, dtype=np.float64).ravel()
         if fac.size != n:
             raise ValueError(f"factor has {fac.size} entries, expected {n}")
         J = np.empty((N, 3, 5, 5))
-        self._check(self._lib.marl_debug_num_jac(self._ctx, _as_ptr(y), float(threshold), _as_ptr(grp) if grp is not None else None,
-                                                 _as_ptr(fac), 1 if factor is None else 0, _as_ptr(J)), "marl_debug_num_jac")
+        self._check(self._lib.marl_debug_num_jac(self._ctx, _as_ptr(y), float(threshold), grp, _as_ptr(fac), 1 if factor is None else 0, _as_ptr(J)),
+                    "marl_debug_num_jac")
         return J, fac
 
     def debug_block_solve(self, J, b_r, b_c=None, mu_r=1.0, mu_c=0j, jscale=1.0):
@@ -694,31 +742,16 @@ class LMAHeureuxPorosityDiff:
         ``solve_ivp(..., t_eval=)`` returns (marl_sweep_radau_eval_dev), as :meth:`sweep_rk45_device` does: ``y_eval_dev_ptr`` is device
         memory [instances][len(t_eval)][5N]; each result carries ``t = t_eval[:n_frames]``, the frames stay on the device, and frames
         beyond ``n_frames`` are not written.  Combinable with ``events``."""
-        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        stats = (MarlStats * self.n_instances)()
-        args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
-                _as_ptr(grp) if grp is not None else None, int(max_attempts))
+        head = _run_head(self, C.c_void_p(y_dev_ptr), t_span, first_step, rtol, atol) + (_groups(groups), int(max_attempts))
+        # Radau's own entry choice: its _eval_dev entry takes the root arguments too, and _events_dev is taken even without room for a root
+        # (seven empty arrays); every entry honours terminal monitors
         if t_eval is not None:
-            te = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
-            if te.size and not y_eval_dev_ptr:
-                raise ValueError("sweep_radau_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
-            n_done = np.zeros(self.n_instances, dtype=np.int64)
             locate = bool(events) and int(max_events) > 0
-            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan) if locate else None
-            rc = self._lib.marl_sweep_radau_eval_dev(*args, _as_ptr(te) if te.size else None, te.size,
-                                                     C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
-                                                     _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
-            self._check(rc, "marl_sweep_radau_eval_dev")
-            return [RK45Result(s, t=te[:int(k)].copy(),
-                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
-                    for b, (s, k) in enumerate(zip(stats, n_done))]
+            return _sweep_call(self, "radau", "marl_sweep_radau_eval_dev", head, ("samples", "roots"), t_eval, y_eval_dev_ptr,
+                               _root_buffer((self.n_instances,), max_events) if locate else None)
         if not events:
-            self._check(self._lib.marl_sweep_radau_dev(*args, stats), "marl_sweep_radau_dev")
-            return [RK45Result(s) for s in stats]
-        tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan)
-        self._check(self._lib.marl_sweep_radau_events_dev(*args, _as_ptr(tev), int(max_events), stats), "marl_sweep_radau_events_dev")
-        return [RK45Result(s, t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
-                for b, s in enumerate(stats)]
+            return _sweep_call(self, "radau", "marl_sweep_radau_dev", head, ())
+        return _sweep_call(self, "radau", "marl_sweep_radau_events_dev", head, ("roots",), tev=_root_buffer((self.n_instances,), max_events))
 
     def sweep_bdf_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, groups=None, t_eval=None, y_eval_dev_ptr=None,
                          events=False, max_events=64):
@@ -740,48 +773,8 @@ class LMAHeureuxPorosityDiff:
         While a monitor is terminal (:meth:`set_terminal`) the sweep runs through marl_sweep_bdf_terminal_dev: an instance whose
         terminal monitor occurs ends at that root on the device with ``status`` 1, ``t_reached`` = the root and the state there; the
         results are built as above, with or without ``t_eval`` and ``events``."""
-        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        stats = (MarlStats * self.n_instances)()
-        args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
-                _as_ptr(grp) if grp is not None else None, int(max_attempts))
-        if any(self.terminal):
-            te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
-            if te.size and not y_eval_dev_ptr:
-                raise ValueError("sweep_bdf_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
-            n_done = np.zeros(self.n_instances, dtype=np.int64)
-            locate = bool(events) and int(max_events) > 0
-            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan) if locate else None
-            rc = self._lib.marl_sweep_bdf_terminal_dev(*args, _as_ptr(te) if te.size else None, te.size,
-                                                       C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
-                                                       _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
-            self._check(rc, "marl_sweep_bdf_terminal_dev")
-            return [RK45Result(s, t=te[:int(k)].copy() if t_eval is not None else None,
-                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
-                    for b, (s, k) in enumerate(zip(stats, n_done))]
-        if bool(events) and int(max_events) > 0:
-            te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
-            if te.size and not y_eval_dev_ptr:
-                raise ValueError("sweep_bdf_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
-            n_done = np.zeros(self.n_instances, dtype=np.int64)
-            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan)
-            rc = self._lib.marl_sweep_bdf_events_dev(*args, _as_ptr(te) if te.size else None, te.size,
-                                                     C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
-                                                     _as_ptr(tev), int(max_events), stats)
-            self._check(rc, "marl_sweep_bdf_events_dev")
-            return [RK45Result(s, t=te[:int(k)].copy() if t_eval is not None else None,
-                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
-                    for b, (s, k) in enumerate(zip(stats, n_done))]
-        if t_eval is not None:
-            te = np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
-            if te.size and not y_eval_dev_ptr:
-                raise ValueError("sweep_bdf_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
-            n_done = np.zeros(self.n_instances, dtype=np.int64)
-            rc = self._lib.marl_sweep_bdf_eval_dev(*args, _as_ptr(te) if te.size else None, te.size,
-                                                   C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done), stats)
-            self._check(rc, "marl_sweep_bdf_eval_dev")
-            return [RK45Result(s, t=te[:int(k)].copy()) for s, k in zip(stats, n_done)]
-        self._check(self._lib.marl_sweep_bdf_dev(*args, stats), "marl_sweep_bdf_dev")
-        return [RK45Result(s) for s in stats]
+        head = _run_head(self, C.c_void_p(y_dev_ptr), t_span, first_step, rtol, atol) + (_groups(groups), int(max_attempts))
+        return _sweep_choose(self, "bdf", "marl_sweep_bdf_terminal_dev", head, t_eval, y_eval_dev_ptr, events, max_events)
 
     def sweep_rk45_device(self, y_dev_ptr, t_span, first_step, rtol, atol, max_attempts=0, t_eval=None, y_eval_dev_ptr=None,
                           events=False, max_events=64):
@@ -831,44 +824,10 @@ class LMAHeureuxPorosityDiff:
                          terminal_entry=True):
         """``terminal_entry``: the entry that honours terminal monitors, taken while one is set - True: marl_sweep_<method>_terminal_dev;
         a name: that entry; False: the method has none here, and its other entries refuse the call."""
-        plain, with_eval, with_events = (f"marl_sweep_{method}_dev", f"marl_sweep_{method}_eval_dev", f"marl_sweep_{method}_events_dev")
-        stats = (MarlStats * self.n_instances)()
-        locate = bool(events) and int(max_events) > 0
-        if terminal_entry and any(self.terminal):
-            entry = terminal_entry if isinstance(terminal_entry, str) else f"marl_sweep_{method}_terminal_dev"
-            te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
-            if te.size and not y_eval_dev_ptr:
-                raise ValueError(f"sweep_{method}_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
-            n_done = np.zeros(self.n_instances, dtype=np.int64)
-            tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan) if locate else None
-            rc = getattr(self._lib, entry)(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol),
-                                           float(atol), int(max_attempts), _as_ptr(te) if te.size else None, te.size,
-                                           C.c_void_p(y_eval_dev_ptr) if te.size else None, _as_ptr(n_done),
-                                           _as_ptr(tev) if locate else None, int(max_events) if locate else 0, stats)
-            self._check(rc, entry)
-            return [RK45Result(s, t=te[:int(k)].copy() if t_eval is not None else None,
-                               t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)] if locate else None)
-                    for b, (s, k) in enumerate(zip(stats, n_done))]
-        if t_eval is None and not locate:
-            rc = getattr(self._lib, plain)(self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]),
-                                               float(first_step), float(rtol), float(atol), int(max_attempts), stats)
-            self._check(rc, plain)
-            return [RK45Result(s) for s in stats]
-        te = np.empty(0) if t_eval is None else np.ascontiguousarray(t_eval, dtype=np.float64).ravel()
-        if te.size and not y_eval_dev_ptr:
-            raise ValueError(f"sweep_{method}_device: t_eval needs y_eval_dev_ptr, device memory [instances][len(t_eval)][5N]")
-        n_done = np.zeros(self.n_instances, dtype=np.int64)
-        args = (self._ctx, C.c_void_p(y_dev_ptr), float(t_span[0]), float(t_span[1]), float(first_step), float(rtol), float(atol),
-                int(max_attempts), _as_ptr(te) if te.size else None, te.size, C.c_void_p(y_eval_dev_ptr) if te.size else None,
-                _as_ptr(n_done))
-        if not locate:
-            self._check(getattr(self._lib, with_eval)(*args, stats), with_eval)
-            return [RK45Result(s, t=te[:int(k)].copy()) for s, k in zip(stats, n_done)]
-        tev = np.full((self.n_instances, NEVENTS, int(max_events)), np.nan)
-        self._check(getattr(self._lib, with_events)(*args, _as_ptr(tev), int(max_events), stats), with_events)
-        return [RK45Result(s, t=None if t_eval is None else te[:int(k)].copy(),
-                           t_events=[tev[b, e, :min(int(s.n_events[e]), int(max_events))].copy() for e in range(NEVENTS)])
-                for b, (s, k) in enumerate(zip(stats, n_done))]
+        if terminal_entry is True:
+            terminal_entry = f"marl_sweep_{method}_terminal_dev"
+        head = _run_head(self, C.c_void_p(y_dev_ptr), t_span, first_step, rtol, atol) + (int(max_attempts),)
+        return _sweep_choose(self, method, terminal_entry, head, t_eval, y_eval_dev_ptr, events, max_events)
 
 
 __all__ = ["LMAHeureuxPorosityDiff", "DepthGrid", "RK45Result", "FIELD_NAMES", "EVENT_NAMES", "terminal_counts", "LAYOUT_FIELD_MAJOR", "LAYOUT_TILED"]

@@ -65,6 +65,19 @@ _P = C.c_void_p
 _D = C.c_double
 _I = C.c_int
 _L = C.c_int64
+# the argument lists the adaptive integrators' entries share, named once (include/marl_hip.h)
+_S = C.POINTER(MarlStats)
+_RUN = [_P, _P, _D, _D, _D, _D, _D]                        # ctx, y, t0, t1, first_step, rtol, atol
+_SAMPLES = [_P, _L, _P, _P]                                # a sweep's t_eval, n_eval, y_eval, n_frames
+_ROOTS = [_P, _L]                                          # t_events, max_events
+_SINGLE = _RUN + [_P, _L, _P] + _ROOTS + [_L, _S]          # single run: ..., t_eval, n_eval, y_eval, roots, max_attempts, stats
+_SINGLE_GROUPS = _RUN + [_P] + _SINGLE[7:]                 # ... of an implicit method: groups follows atol
+_SINGLE_DEV = [_P, _P, _I] + _RUN[2:] + [_L, _S]           # single run on device memory: ctx, y, layout, ..., max_attempts, stats
+_SWEEP = _RUN + [_L, _S]                                   # sweep: ..., max_attempts, stats
+_SWEEP_EVAL = _RUN + [_L] + _SAMPLES + [_S]
+_SWEEP_EVENTS = _RUN + [_L] + _SAMPLES + _ROOTS + [_S]     # the _events_dev entries and the ones that stop
+_SWEEP_GROUPS = _RUN + [_P, _L, _S]                        # an implicit method's sweep: groups before max_attempts
+_SWEEP_GROUPS_EVENTS = _RUN + [_P, _L] + _SAMPLES + _ROOTS + [_S]
 PROTOTYPES = {
     "marl_ctx_create": (_I, [C.POINTER(MarlParams), _L, _L, _I, C.POINTER(_P)]),
     "marl_ctx_set_params": (_I, [_P, C.POINTER(MarlParams), _L]),
@@ -88,39 +101,39 @@ PROTOTYPES = {
     "marl_integrate_rk4": (_I, [_P, _P, _D, _L]),
     "marl_integrate_rk4_dev": (_I, [_P, _P, _I, _D, _L]),
     "marl_sweep_rk4_dev": (_I, [_P, _P, _P, _L]),
-    "marl_sweep_rk4_watch_dev": (_I, [_P, _P, _D, _P, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk4_watch": (_I, [_P, _P, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk45": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk45_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_rk45_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_rk45_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, C.POINTER(MarlStats)]),
-    "marl_sweep_rk45_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_rk45_terminal_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_rk23_terminal_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk45_terminal": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk23_terminal": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk23": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_rk23_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_rk23_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_rk23_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, C.POINTER(MarlStats)]),
-    "marl_sweep_rk23_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_dop853": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_dop853_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_dop853_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, C.POINTER(MarlStats)]),
-    "marl_sweep_dop853_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_dop853_stop_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_dop853_stop": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_dop853_grid": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_dop853_grid_dev": (_I, [_P, _P, _I, _D, _D, _D, _D, _D, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_radau": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_integrate_bdf": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _P, _L, _P, _P, _L, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_radau_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_radau_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_radau_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_bdf_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_bdf_eval_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _L, _P, _P, C.POINTER(MarlStats)]),
-    "marl_sweep_bdf_events_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
-    "marl_sweep_bdf_terminal_dev": (_I, [_P, _P, _D, _D, _D, _D, _D, _P, _L, _P, _L, _P, _P, _P, _L, C.POINTER(MarlStats)]),
+    "marl_sweep_rk4_watch_dev": (_I, [_P, _P, _D, _P, _L, _P, _L, _P, _P, _P, _L, _S]),
+    "marl_integrate_rk4_watch": (_I, [_P, _P, _D, _D, _L, _P, _L, _P, _P, _P, _L, _S]),
+    "marl_integrate_rk45": (_I, _SINGLE),
+    "marl_integrate_rk45_dev": (_I, _SINGLE_DEV),
+    "marl_sweep_rk45_dev": (_I, _SWEEP),
+    "marl_sweep_rk45_eval_dev": (_I, _SWEEP_EVAL),
+    "marl_sweep_rk45_events_dev": (_I, _SWEEP_EVENTS),
+    "marl_sweep_rk45_terminal_dev": (_I, _SWEEP_EVENTS),
+    "marl_sweep_rk23_terminal_dev": (_I, _SWEEP_EVENTS),
+    "marl_integrate_rk45_terminal": (_I, _SINGLE),
+    "marl_integrate_rk23_terminal": (_I, _SINGLE),
+    "marl_integrate_rk23": (_I, _SINGLE),
+    "marl_integrate_rk23_dev": (_I, _SINGLE_DEV),
+    "marl_sweep_rk23_dev": (_I, _SWEEP),
+    "marl_sweep_rk23_eval_dev": (_I, _SWEEP_EVAL),
+    "marl_sweep_rk23_events_dev": (_I, _SWEEP_EVENTS),
+    "marl_integrate_dop853": (_I, _SINGLE),
+    "marl_sweep_dop853_dev": (_I, _SWEEP),
+    "marl_sweep_dop853_eval_dev": (_I, _SWEEP_EVAL),
+    "marl_sweep_dop853_events_dev": (_I, _SWEEP_EVENTS),
+    "marl_sweep_dop853_stop_dev": (_I, _SWEEP_EVENTS),
+    "marl_integrate_dop853_stop": (_I, _SINGLE),
+    "marl_integrate_dop853_grid": (_I, _SINGLE),
+    "marl_integrate_dop853_grid_dev": (_I, _SINGLE_DEV),
+    "marl_integrate_radau": (_I, _SINGLE_GROUPS),
+    "marl_integrate_bdf": (_I, _SINGLE_GROUPS),
+    "marl_sweep_radau_dev": (_I, _SWEEP_GROUPS),
+    "marl_sweep_radau_events_dev": (_I, _RUN + [_P, _L] + _ROOTS + [_S]),
+    "marl_sweep_radau_eval_dev": (_I, _SWEEP_GROUPS_EVENTS),
+    "marl_sweep_bdf_dev": (_I, _SWEEP_GROUPS),
+    "marl_sweep_bdf_eval_dev": (_I, _RUN + [_P, _L] + _SAMPLES + [_S]),
+    "marl_sweep_bdf_events_dev": (_I, _SWEEP_GROUPS_EVENTS),
+    "marl_sweep_bdf_terminal_dev": (_I, _SWEEP_GROUPS_EVENTS),
     "marl_ctx_create_slab": (_I, [C.POINTER(MarlParams), _L, _L, _L, _L, _I, C.POINTER(_P)]),
     "marl_slab_load": (_I, [_P, _P]),
     "marl_slab_store": (_I, [_P, _P]),

@@ -65,6 +65,28 @@ def product_grid(**axes):
     return [dict(zip(names, (float(g.flat[i]) for g in grids))) for i in range(grids[0].size)]
 
 
+def _sweep_with_frames(engine, sweep, y0, args, terminal, events, max_events, samples=None, names=("t_eval", "y_eval_dev_ptr"), **fixed):
+    """The frame plumbing of every engine method: set ``terminal`` on the engine's model, upload ``y0`` ((n_local, 5N), already
+    converted by the caller), call the model's ``sweep`` once - ``events`` / ``max_events`` are handed on only when roots are asked
+    for, ``samples`` and a device buffer [n_local][max(len(samples), 1)][5N] for the frames under ``names`` only when samples are -
+    and attach to every result the frames it reached, ``y`` (5N, len(t)).  Returns (y_final (n_local, 5N), the results).  Uses the
+    engine's ``model``, ``torch`` and ``device`` only."""
+    engine.model.set_terminal(terminal)
+    sweep = getattr(engine.model, sweep)
+    yd = engine.torch.from_numpy(y0).to(engine.device)
+    more = dict(fixed, events=True, max_events=max_events) if events else dict(fixed)
+    frames = None
+    if samples is not None:
+        frames = engine.torch.empty((yd.shape[0], max(int(np.size(samples)), 1), yd.shape[1]), dtype=yd.dtype, device=engine.device)
+        more |= {names[0]: samples, names[1]: frames.data_ptr()}
+    res = sweep(yd.data_ptr(), *args, **more)
+    if frames is not None:
+        frames = frames.cpu().numpy()
+        for b, r in enumerate(res):
+            r.y = frames[b, :len(r.t)].T.copy()
+    return yd.cpu().numpy(), res
+
+
 class HipSweepEngine:
     """The product engine: LMAHeureuxPorosityDiff with a batch of instances on one GPU."""
 
@@ -99,7 +121,8 @@ class HipSweepEngine:
 
     def integrate_dop853(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
         """:meth:`integrate_rk45` with DOP853 (marl_sweep_dop853_dev / _eval_dev / _events_dev; N <= 1024): the same arguments and
-        results.  There is no terminal entry: with ``terminal`` set the sweep is refused (:class:`marlpde_amd._abi.MarlError`)."""
+        results.  These entries do not stop: with ``terminal`` set the sweep is refused (:class:`marlpde_amd._abi.MarlError`);
+        :meth:`integrate_dop853_stop` runs the entry that does (marl_sweep_dop853_stop_dev)."""
         return self._integrate_rk("sweep_dop853_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
 
     def integrate_dop853_stop(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
@@ -108,20 +131,8 @@ class HipSweepEngine:
         return self._integrate_rk("sweep_dop853_stop_device", y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal)
 
     def _integrate_rk(self, sweep, y0, t_span, first_step, rtol, atol, max_attempts, t_eval, events, max_events, terminal=None):
-        self.model.set_terminal(terminal)
-        sweep = getattr(self.model, sweep)
-        yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
-        more = {"events": True, "max_events": max_events} if events else {}
-        if t_eval is None:
-            res = sweep(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
-            return yd.cpu().numpy(), res
-        n_eval = int(np.size(t_eval))
-        frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
-        res = sweep(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval, y_eval_dev_ptr=frames.data_ptr(), **more)
-        frames = frames.cpu().numpy()
-        for b, r in enumerate(res):
-            r.y = frames[b, :len(r.t)].T.copy()
-        return yd.cpu().numpy(), res
+        return _sweep_with_frames(self, sweep, np.ascontiguousarray(y0), (t_span, first_step, rtol, atol, max_attempts), terminal, events, max_events,
+                                  t_eval)
 
     def integrate_radau(self, y0, t_span, first_step, rtol, atol, max_attempts, t_eval=None, events=False, max_events=64, terminal=None):
         """The reference's default solver over the shard: every instance its own Radau step logic, advanced together on the device
@@ -129,20 +140,8 @@ class HipSweepEngine:
         :meth:`integrate_rk45` (marl_sweep_radau_eval_dev: samples and roots on the accepted step's dense output, inside the sweep).
         ``terminal`` (see :func:`marlpde_amd.LHeureux_model.terminal_counts`): monitors that end an instance's run at their root -
         status 1, ``t_reached`` the root, the state the dense output there; None: none, whatever an earlier call set."""
-        self.model.set_terminal(terminal)
-        yd = self.torch.from_numpy(np.ascontiguousarray(y0)).to(self.device)
-        more = {"events": True, "max_events": max_events} if events else {}
-        if t_eval is None:
-            res = self.model.sweep_radau_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
-            return yd.cpu().numpy(), res
-        n_eval = int(np.size(t_eval))
-        frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
-        res = self.model.sweep_radau_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
-                                            y_eval_dev_ptr=frames.data_ptr(), **more)
-        frames = frames.cpu().numpy()
-        for b, r in enumerate(res):
-            r.y = frames[b, :len(r.t)].T.copy()
-        return yd.cpu().numpy(), res
+        return _sweep_with_frames(self, "sweep_radau_device", np.ascontiguousarray(y0), (t_span, first_step, rtol, atol, max_attempts), terminal, events,
+                                  max_events, t_eval)
 
     def integrate_bdf(self, y0, t_span, first_step, rtol, atol, max_attempts, workers=None, batched=False, t_eval=None, events=False,
                       max_events=64, terminal=None):
@@ -160,20 +159,8 @@ class HipSweepEngine:
         ``terminal`` as for :meth:`integrate_radau`, either way: the batched sweep stops an instance on the device
         (marl_sweep_bdf_terminal_dev), the single runs stop themselves (marl_integrate_bdf); None: none, whatever an earlier call set."""
         if batched:
-            self.model.set_terminal(terminal)
-            yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
-            more = {"events": True, "max_events": max_events} if events else {}
-            if t_eval is None:
-                res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, **more)
-                return yd.cpu().numpy(), res
-            n_eval = int(np.size(t_eval))
-            frames = self.torch.empty((yd.shape[0], max(n_eval, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
-            res = self.model.sweep_bdf_device(yd.data_ptr(), t_span, first_step, rtol, atol, max_attempts, t_eval=t_eval,
-                                              y_eval_dev_ptr=frames.data_ptr(), **more)
-            frames = frames.cpu().numpy()
-            for b, r in enumerate(res):
-                r.y = frames[b, :len(r.t)].T.copy()
-            return yd.cpu().numpy(), res
+            return _sweep_with_frames(self, "sweep_bdf_device", np.ascontiguousarray(y0, dtype=np.float64), (t_span, first_step, rtol, atol, max_attempts),
+                                      terminal, events, max_events, t_eval)
         from concurrent.futures import ThreadPoolExecutor
         from .LHeureux_model import LMAHeureuxPorosityDiff
         torch = self.torch
@@ -221,19 +208,8 @@ class HipSweepEngine:
         ``frame_steps`` every result carries the frames that instance reached, ``t`` (n_t,) and ``y`` (5N, n_t); with ``events`` the
         root estimates ``t_events``.  ``terminal`` as for :meth:`integrate_radau`, by the fixed-step rule: the instance ends at the END
         of the step of the terminal occurrence (status 1).  Status -2: the state went non-finite, the step is too large."""
-        self.model.set_terminal(terminal)
-        yd = self.torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float64)).to(self.device)
-        more = {"events": True, "max_events": max_events} if events else {}
-        if frame_steps is None:
-            res = self.model.sweep_rk4_watch_device(yd.data_ptr(), dt, nsteps, t0=t0, **more)
-            return yd.cpu().numpy(), res
-        n_frames = int(np.size(frame_steps))
-        frames = self.torch.empty((yd.shape[0], max(n_frames, 1), yd.shape[1]), dtype=yd.dtype, device=self.device)
-        res = self.model.sweep_rk4_watch_device(yd.data_ptr(), dt, nsteps, t0=t0, frame_steps=frame_steps, frames_dev_ptr=frames.data_ptr(), **more)
-        frames = frames.cpu().numpy()
-        for b, r in enumerate(res):
-            r.y = frames[b, :len(r.t)].T.copy()
-        return yd.cpu().numpy(), res
+        return _sweep_with_frames(self, "sweep_rk4_watch_device", np.ascontiguousarray(y0, dtype=np.float64), (dt, nsteps), terminal, events, max_events,
+                                  frame_steps, names=("frame_steps", "frames_dev_ptr"), t0=t0)
 
     def close(self):
         if self._model is not None:
