@@ -116,6 +116,9 @@ struct marl_ctx {
     // chained windows in the streamed loop (rk4_chain_kernel; 4 steps per level, constant porosity diffusion): 0 never, 1 automatic
     // (rk4_chain_auto below), K >= 2: chains of K windows whenever that path is taken
     int64_t rk4_chain = 1;
+    // the LDS layout of the chained kernel: 0 = exchange buffer by field, cache slots one by one (rk4_chain_kernel); 1 = exchange buffer
+    // by cell, cache slots in pairs (rk4_exchange_kernel: 16-byte LDS accesses, the same results bit for bit)
+    int64_t rk4_exchange = 1;
     int64_t rk4_stream_third = 1;   // an odd number of levels goes through a third state buffer, so that no whole-state copy follows (0: copy)
     double* stream_c = nullptr;
     size_t stream_c_cap = 0;
@@ -463,6 +466,11 @@ int marl_set_option(marl_ctx* ctx, const char* name, int64_t value)
     else if (n == "rk45_stream_attempts") ctx->rk45_stream_attempts = value < 1 ? 1 : std::min<int64_t>(value, 1 << 20);
     else if (n == "rk4_small") ctx->rk4_small = value ? 1 : 0;
     else if (n == "rk4_chain") ctx->rk4_chain = value < 0 ? 0 : std::min<int64_t>(value, kChainMax);
+#ifdef MARL_LAB_XCH_PARTS   // (lab builds: 1 = by cell only, 2 = pairs only, 3 = both)
+    else if (n == "rk4_exchange") ctx->rk4_exchange = value < 0 ? 0 : std::min<int64_t>(value, 3);
+#else
+    else if (n == "rk4_exchange") ctx->rk4_exchange = value ? 1 : 0;
+#endif
     else if (n == "rk4_stream_third") ctx->rk4_stream_third = value ? 1 : 0;
     else if (n == "rk4_stream_test_raise") ctx->sq_test_raise = value != 0;
     else if (n == "rk4_stream_max_items") ctx->sq_max_items = value > 0 ? std::min<int64_t>(value, 0x7fffffff) : 0x7fffffff;
@@ -702,8 +710,18 @@ static int64_t rk4_chain_auto(int64_t n, int64_t resident)
 template <int LAYOUT>
 static void launch_chain_t(marl_ctx* ctx, double* a, double* b, double dt, unsigned levels, const ChainShape& sh, unsigned blocks, double* c)
 {
-    hipLaunchKernelGGL((rk4_chain_kernel<256, LAYOUT, 4>), dim3(blocks), dim3(256), 0, ctx->stream, a, b, ctx->dconsts, ctx->slab, dt, levels,
-                       (unsigned)sh.items, ctx->sq, ctx->sq + 2, ctx->sq_sticky, ctx->sq_item_base, ctx->sq_level_base, c, sh.K, sh.nsub_last, sh.bound);
+#define MARL_CHAIN_LAUNCH(KERNEL)                                                                                                                \
+    hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(256), 0, ctx->stream, a, b, ctx->dconsts, ctx->slab, dt, levels, (unsigned)sh.items, ctx->sq, \
+                       ctx->sq + 2, ctx->sq_sticky, ctx->sq_item_base, ctx->sq_level_base, c, sh.K, sh.nsub_last, sh.bound)
+    switch (ctx->rk4_exchange) {
+        case 0: MARL_CHAIN_LAUNCH((rk4_chain_kernel<256, LAYOUT, 4>)); break;
+#ifdef MARL_LAB_XCH_PARTS
+        case 1: MARL_CHAIN_LAUNCH((rk4_exchange_kernel<256, LAYOUT, 4, XCH_CELL>)); break;
+        case 2: MARL_CHAIN_LAUNCH((rk4_exchange_kernel<256, LAYOUT, 4, XCH_PAIRS>)); break;
+#endif
+        default: MARL_CHAIN_LAUNCH((rk4_exchange_kernel<256, LAYOUT, 4>)); break;
+    }
+#undef MARL_CHAIN_LAUNCH
 }
 
 // *result: where the state is afterwards (a or b)

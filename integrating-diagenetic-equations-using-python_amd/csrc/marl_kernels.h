@@ -100,9 +100,20 @@ __device__ unsigned long long marl_lab_phase[8];
 
 // SEAM (rk4_chain_kernel only; 0 = none, and then nothing of it exists): the lane whose stage state is recorded at every evaluation
 // for the next window of a chain, whose thread 0 takes its left neighbour from that record instead of from a recomputed halo.
-template <int BLK, bool REUSE = true, bool VD = false, int SEAM = 0>
+// XCH (rk4_exchange_kernel only; 0 = what every other kernel has): how the exchange buffer and the cache slots lie in LDS.
+//   XCH_CELL   the exchange buffer by cell, [parity][thread][6 doubles] (the five fields and one pad double: a pitch of 48 bytes),
+//              instead of by field, [parity][field][thread].  By field a cell's values lie 2 KB apart and the compiler pairs their
+//              accesses into two-address forms (ds_read2st64_b64: 128 B/clk); by cell they are 16-byte accesses (ds_read_b128:
+//              256 B/clk).  Banks: lane l starts at dword 12 l, bank 4 (3 l mod 16) - 3 is invertible mod 16, so the 16 lanes that a
+//              128-bit read serves per pass cover the 64 banks once, and the 8 lanes of a 128-bit write pass the 32 store banks once.
+//   XCH_PAIRS  the four LDS cache slots as two pairs, [pair][thread][2] (marl_math.h, PointCache): two 16-byte reads per evaluation.
+// The same bytes and values in the same order of use either way: nothing but LDS addresses differs.
+enum : int { XCH_CELL = 1, XCH_PAIRS = 2 };
+template <int BLK, bool REUSE = true, bool VD = false, int SEAM = 0, int XCH = 0>
 struct StencilBlock {
-    static constexpr int EDGE_DOUBLES = 2 * NF * BLK;       // edges [parity][field][thread]
+    static constexpr bool CELL = (XCH & XCH_CELL) != 0, PAIRS = (XCH & XCH_PAIRS) != 0;
+    static constexpr int PITCH = NF + 1;                    // CELL: doubles between the cells of the exchange buffer
+    static constexpr int EDGE_DOUBLES = 2 * (CELL ? PITCH : NF) * BLK;       // edges [parity][field][thread] (CELL: [parity][thread][PITCH])
     static constexpr bool CACHE_LDS = PC_LDS_SLOTS > 0;
     static constexpr bool CACHE = REUSE && (EDGE_DOUBLES + TABLE_DOUBLES + PC_LDS_SLOTS * BLK) * 8 <= 60 * 1024;
     static constexpr int CACHE_DOUBLES = CACHE ? PC_LDS_SLOTS * BLK : 0;
@@ -142,7 +153,9 @@ struct StencilBlock {
     __device__ __forceinline__ unsigned is_last() const { if constexpr (SEAM > 0) return (unsigned)tid + 1u == ((edge_word() >> 20) & 0x1ffu); else return (masks >> 8) & 1u; }
     __device__ __forceinline__ unsigned in_zone() const { if constexpr (SEAM > 0) return w_zone; else return (masks >> 16) & 1u; }
     __device__ __forceinline__ unsigned is_edge() const { return masks & 0x101u; }   // first or last: non-zero
-    PointCache<(CACHE && CACHE_LDS) ? BLK : 0> cache;  // centre of the transcendental expansions (TR_FILL / TR_REUSE / TR_AUTO)
+    static_assert(XCH == 0 || (CACHE && PC_LDS_SLOTS == 4 && (EDGE_DOUBLES + TABLE_DOUBLES) % 2 == 0), "XCH: 16-byte accesses, two pairs of cache slots");
+    PointCache<(CACHE && CACHE_LDS) ? BLK : 0, PAIRS> cache;  // centre of the transcendental expansions (TR_FILL / TR_REUSE / TR_AUTO)
+    __device__ __forceinline__ double* cache_slots(double* l, int t) const { return l + EDGE_DOUBLES + TABLE_DOUBLES + (PAIRS ? 2 * t : t); }
     bool reuse_live = false;     // wave-uniform: the centre is filled and no evaluation since has fallen out of range
     // SEAM: the record in LDS, [evaluation][parity][8 doubles, NF used], and - ONE scalar register, the loop sits at its cap of those too -
     // where the current evaluation writes in it (bits 0-15: 16 * evaluation + 8 * parity; the other parity is what it reads) and whether
@@ -168,7 +181,7 @@ struct StencilBlock {
     {
         if constexpr (SEAM > 0) set_interior(false);   // (every window sets its own)
         else set_window(g0);
-        if constexpr (CACHE && CACHE_LDS) cache.s = lds_ + EDGE_DOUBLES + TABLE_DOUBLES + tid;
+        if constexpr (CACHE && CACHE_LDS) cache.s = cache_slots(lds_, tid);
     }
 
     // Persistent kernels: the per-thread members again, from an index the caller has made opaque inside its work loop - everything
@@ -177,7 +190,7 @@ struct StencilBlock {
     __device__ __forceinline__ void rebind(int t)
     {
         tid = t;
-        if constexpr (CACHE && CACHE_LDS) cache.s = lds + EDGE_DOUBLES + TABLE_DOUBLES + t;
+        if constexpr (CACHE && CACHE_LDS) cache.s = cache_slots(lds, t);
     }
 
     // (Re)position the window: g = global index of this thread's cell.
@@ -224,9 +237,16 @@ struct StencilBlock {
     __device__ __forceinline__ void eval(const double (&ys)[NF], double (&k)[NF], PointAux& aux)
     {
         MARL_PHASE_MARK(4);
-        double* e = lds + parity * (NF * BLK);
+        double* e = lds + parity * ((CELL ? PITCH : NF) * BLK);
+        if constexpr (CELL) {   // (CA, CC), (c, o) as 16-byte stores, Phi as one of 8
+            double* own = e + PITCH * tid;
+            reinterpret_cast<double2v*>(own)[0] = double2v{ys[0], ys[1]};
+            reinterpret_cast<double2v*>(own)[1] = double2v{ys[2], ys[3]};
+            own[4] = ys[4];
+        } else {
 #pragma unroll
-        for (int f = 0; f < NF; f++) e[f * BLK + tid] = ys[f];
+            for (int f = 0; f < NF; f++) e[f * BLK + tid] = ys[f];
+        }
         if constexpr (SEAM > 0) {
             // The recording lane also writes its stage state into the seam record - here, in front of the own-cell phase, so that nothing
             // of the seam lies between the barrier and the stencil phase of its wave.  A scalar branch: three waves of four skip it, no
@@ -251,8 +271,15 @@ struct StencilBlock {
         const int tl = tid > 0 ? tid - 1 : 0;
         const int tr = tid < BLK - 1 ? tid + 1 : BLK - 1;
         double left[NF], right[NF];
+        if constexpr (CELL) {
+            const double* lc = e + PITCH * tl;
+            const double2v s01 = reinterpret_cast<const double2v*>(lc)[0], s23 = reinterpret_cast<const double2v*>(lc)[1];
+            left[0] = s01.x; left[1] = s01.y; left[2] = s23.x; left[3] = s23.y;
+            left[4] = lc[4];   // (8 bytes: lanes l and l + 16 meet in a bank; read as 16 with the pad, the compiler narrows it to this)
+        } else {
 #pragma unroll
-        for (int f = 0; f < NF; f++) left[f] = e[f * BLK + tl];
+            for (int f = 0; f < NF; f++) left[f] = e[f * BLK + tl];
+        }
         if constexpr (SEAM > 0) {
             // Thread 0 of a chained window takes its left neighbour from what the recording lane of the window before wrote at the same
             // evaluation (the other parity; 4 * NSTEPS barriers ago, and the slot is next written 4 * NSTEPS barriers from now).  Wave 0
@@ -271,7 +298,17 @@ struct StencilBlock {
         // the solids are differenced against the upwind neighbour only: with U > 0 in every lane (burial - the normal
         // case) the right-hand values of CA and CC are never used and their two LDS reads are skipped
         const bool need_right_solids = __builtin_amdgcn_ballot_w64(!pl.upw) != 0;
-        if constexpr (CACHE) {
+        if constexpr (CELL) {
+            const double* rc = e + PITCH * tr;
+            const double2v s23 = reinterpret_cast<const double2v*>(rc)[1];
+            right[2] = s23.x; right[3] = s23.y;
+            right[4] = rc[4];
+            asm volatile("" : "=v"(right[0]), "=v"(right[1]));   // (see below)
+            if (need_right_solids) {
+                const double2v s01 = reinterpret_cast<const double2v*>(rc)[0];
+                right[0] = s01.x; right[1] = s01.y;
+            }
+        } else if constexpr (CACHE) {
 #pragma unroll
             for (int f = 2; f < NF; f++) right[f] = e[f * BLK + tr];
             // a wave-uniform branch around the two reads; without them right[0], right[1] hold whatever their registers held: point_rates,
@@ -831,6 +868,170 @@ rk4_chain_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ const
     __shared__ double lds[SB::LDS_DOUBLES];
     __shared__ double seam[H * SB::SEAM_STRIDE];
     __shared__ unsigned s_item, s_abort;
+    const DevConsts& C = consts[0];
+    SB sb(lds, 0, consts);   // tables once per workgroup (barrier inside)
+    sb.seam = seam;
+    // (the step in a scalar pair of its own: it arrives in one wide load with `levels`, `items`, `queue`, `done`, and the allocator keeps -
+    // and, where cold code borrows the registers, reloads in every step - the whole tuple for as long as one member is live)
+    dt = pin_uniform(dt);
+    const unsigned total = levels * items;   // (host: < 2^31)
+    const unsigned chains = items - 1;
+
+    while (true) {
+        // (the shape of this loop: see rk4_stream_kernel)
+        __syncthreads();
+        // the queue's arguments through the segment too, once per item (they shadow the parameters): they arrive in one wide load with the
+        // step size, and while any member of it is held the allocator keeps - and reloads in every step - the whole tuple
+        typedef __attribute__((address_space(1))) unsigned* GlobalWords;
+        ChainArgsPtr G = chain_args();
+        unsigned *const queue = (unsigned*)(GlobalWords)G->queue, *const done = (unsigned*)(GlobalWords)G->done,
+                 *const sticky = (unsigned*)(GlobalWords)G->sticky;
+        const unsigned items = G->items, item_base = G->item_base, level_base = G->level_base;
+        if (threadIdx.x == 0) {
+            s_item = __hip_atomic_fetch_add(&queue[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - item_base;
+            s_abort = 0;
+        }
+        __syncthreads();
+        const unsigned item = __builtin_amdgcn_readfirstlane(s_item);   // (in a scalar register: the trip count below derives from it)
+        if (item >= total) break;
+        const unsigned level = item / items, tile = item - level * items;
+        if (level > 0) {
+            if (threadIdx.x < 3) {
+                const int64_t t = (int64_t)tile - 1 + threadIdx.x;
+                if (t >= 0 && t < (int64_t)items) {
+                    unsigned spins = 0;
+                    while ((int)(__hip_atomic_load(&done[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (level_base + level)) < 0) {
+                        __builtin_amdgcn_s_sleep(4);
+                        if (++spins > STREAM_SPIN_LIMIT ||
+                            ((spins & 255u) == 0 && __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                            __hip_atomic_store(sticky, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            s_abort = 1;
+                            break;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (s_abort) break;
+        }
+        const double* src;
+        double* dst;
+        unsigned nsub;
+        int64_t first, clip;
+        {   // (the arguments through the segment: see ChainArgs)
+            ChainArgsPtr A = chain_args();
+            double *const pA = A->bufA, *const pB = A->bufB, *const pC = A->bufC;
+            const unsigned nlev = A->levels, KK = A->K, nlast = A->nsub_last;
+            const int64_t olo = A->S.out_lo, ohi = A->S.out_hi, bnd = A->bound;
+            src = (const double*)(const __attribute__((address_space(1))) double*)(pC ? (level == 0 ? pA : ((level & 1u) ? pB : pC)) : ((level & 1u) ? pB : pA));
+            dst = (double*)(__attribute__((address_space(1))) double*)(pC ? (level + 1 == nlev ? pA : ((level & 1u) ? pC : pB)) : ((level & 1u) ? pA : pB));
+            // the item's windows (all wave-uniform): window j has its thread 0 on local cell first + j W
+            const bool chain = tile < chains;
+            nsub = chain ? (tile + 1 == chains ? nlast : KK) : 1u;
+            first = olo - H + (chain ? (int64_t)tile * (V + (int64_t)W * (KK - 1)) : bnd);
+            clip = chain ? olo + bnd : ohi;
+        }
+#pragma unroll 1
+        for (unsigned j = 0; j < nsub; j++) {
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));   // opaque: what derives from the thread index is recomputed per window, not carried across the loops
+            sb.rebind(tid);
+            // An INTERIOR window - wholly inside the buffer, neither cell 0 nor cell N - 1 in it, wholly inside or wholly outside the
+            // dissolution zone: all but three or four windows of a grid - is recognised once on the scalar side (wave-uniform).  Its
+            // masks are constants and its loads need no guard: the per-lane 64-bit compares of set_window, the ballot and the
+            // boundary selects run only in the other windows.  Same values either way.
+            // (The tests are signs of 64-bit differences, formed modulo 2^64 - every operand is below 2^62 - and taken from the high
+            // words: scalar subtractions and one 32-bit compare, where a signed 64-bit compare of two scalars is a vector instruction.)
+            ChainArgsPtr A = chain_args();
+            const int64_t n_buf = A->S.n_buf, goff = A->S.goff, ld = A->S.ld;
+            const int64_t lw = first + (int64_t)j * W, gw = lw + goff;
+            const int64_t mlo = C.mask_lo, mhi = C.mask_hi;
+            // (each sign word opaque: combined freely, they are merged back into 64-bit values and compared on the vector side)
+            auto neg = [](int64_t a, int64_t b) {   // < 0: a < b
+                int32_t hi = (int32_t)(((uint64_t)a - (uint64_t)b) >> 32);
+                asm("" : "+s"(hi));
+                return hi;
+            };
+            const int32_t out_any = neg(lw, 0) | neg(n_buf, lw + BLK) | neg(gw, 1) | neg(C.N - 1, gw + BLK);   // < 0: not interior
+            const int32_t zone_part = neg(gw, mlo) | neg(mhi, gw + BLK);       // >= 0: wholly inside the zone
+            const int32_t zone_some = neg(mlo, gw + BLK) & neg(gw, mhi);       // >= 0: wholly outside
+            const bool interior = out_any >= 0 && (zone_part >= 0 || zone_some >= 0);
+            const int64_t l = lw + tid;
+            bool in = true;
+            int64_t la = l;   // the cell the lane loads: its own, or - outside the buffer - a valid one (the value is replaced below)
+            if (!interior) {
+                asm volatile("");   // a real branch
+                in = l >= 0 && l < n_buf;
+                la = in ? l : 0;
+            }
+            double y[NF];
+#pragma unroll
+            for (int f = 0; f < NF; f++) y[f] = __hip_atomic_load(src + at<LAYOUT>(f, la, ld), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (interior) {
+                sb.set_interior(zone_part >= 0);
+            } else {
+                asm volatile("");
+#pragma unroll
+                for (int f = 0; f < NF; f++) y[f] = in ? y[f] : C.bc[f];
+                sb.set_window_seam(gw);
+            }
+            sb.reuse_live = false;   // every window fills its own expansion centre, as an item of rk4_stream_kernel does
+            // (the wave's number through readfirstlane: everything else is then scalar arithmetic; left to itself the compiler builds the
+            // word per lane from lane masks)
+            const int wave = __builtin_amdgcn_readfirstlane(tid) >> 6;
+            sb.seam_pos = (int)(j & 1u) * 8 + (j ? SB::SEAM_READS : 0) + (wave == 0 ? SB::SEAM_WAVE0 : 0)
+                          + (wave == (BLK - H - 1) / 64 ? SB::SEAM_WAVEW : 0);
+            // the lanes that store, [lo, hi): both bounds are scalars of 32 bits.  hi - the window's end or the clip - is formed here, in front
+            // of the evaluations (one word carried instead of the 64-bit clip); lo is read off the seam word behind them (a window with a left
+            // halo of its own is the one that does not read the seam), where `j == 0` itself would be carried as a lane mask, a spilled pair.
+            const int64_t room = clip - lw;
+            int hi = neg(room, BLK - H) < 0 ? (int)room : BLK - H;
+            asm volatile("" : "+s"(hi));
+            rk4_advance<NSTEPS>(sb, y, dt);
+            int sp = sb.seam_pos;
+            asm volatile("" : "+s"(sp));
+            const int lo = (sp & SB::SEAM_READS) ? 0 : H;
+            int ts = threadIdx.x;
+            asm volatile("" : "+v"(ts));    // (the cell index again: two registers less across the evaluations)
+            const int64_t ls = first + (int64_t)j * W + ts;
+            if (ts >= lo && ts < hi) {
+                int64_t lds_ = 0;   // (the tiled layout has no field stride: no pointer to the segment is formed for it)
+                if constexpr (LAYOUT == LAYOUT_FIELD_MAJOR) lds_ = chain_args()->S.ld;
+#pragma unroll
+                for (int f = 0; f < NF; f++) __hip_atomic_store(dst + at<LAYOUT>(f, ls, lds_), y[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        __builtin_amdgcn_s_waitcnt(0);   // this thread's stores - of every window of the item - have been acknowledged
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        __syncthreads();                 // ... and everybody else's (and everybody has read s_item, s_abort)
+        if (threadIdx.x == 0) __hip_atomic_store(&done[tile], level_base + level + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// rk4_chain_kernel with the LDS exchange laid out by cell and the cache slots in pairs (StencilBlock, XCH): the same arguments, the same
+// item loop, the same arithmetic on the same operands in the same order - bit-identical results - and 16-byte LDS accesses where
+// rk4_chain_kernel has two-address 64-bit ones.  The exchange buffer grows by the pad double of each cell, 4 KB: 37 896 B, and four
+// workgroups still share a CU's 160 KB.
+// The body is rk4_chain_kernel's, line for line, written out a second time: moved into a function that both kernels inline, it changed the
+// machine code of rk4_chain_kernel (scalar spills and the order of the prologue; profiles/r11_lab_chain_exchange.log) - and that kernel stays
+// what it is.  What differs: the StencilBlock and the alignment of the LDS block.  A change to one loop belongs in the other too.
+// XCH: which parts of the layout the kernel takes (XCH_CELL | XCH_PAIRS is what ships; lab builds instantiate each part alone too).
+template <int BLK, int LAYOUT, int NSTEPS, int XCH = XCH_CELL | XCH_PAIRS>
+__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4, 8)))
+rk4_exchange_kernel(double* bufA, double* bufB, const DevConsts* __restrict__ consts, Slab S, double dt, unsigned levels, unsigned items,
+                    unsigned* queue, unsigned* done, unsigned* sticky, unsigned item_base, unsigned level_base, double* bufC,
+                    unsigned K, unsigned nsub_last, int64_t bound)
+{
+    constexpr int H = 4 * NSTEPS;
+    constexpr int V = BLK - 2 * H;     // cells the first window of an item writes
+    constexpr int W = BLK - H;         // ... and every later one
+    static_assert(V > 0, "window too small for the fused halo");
+    using SB = StencilBlock<BLK, true, false, BLK - H - 1, XCH>;
+    __shared__ __attribute__((aligned(16))) double lds[SB::LDS_DOUBLES];   // (the 128-bit forms need 16 bytes)
+    __shared__ double seam[H * SB::SEAM_STRIDE];
+    __shared__ unsigned s_item, s_abort;
+    static_assert((SB::LDS_DOUBLES + H * SB::SEAM_STRIDE) * 8 + 8 <= 40960, "four workgroups per CU: 160 KB of LDS");
     const DevConsts& C = consts[0];
     SB sb(lds, 0, consts);   // tables once per workgroup (barrier inside)
     sb.seam = seam;

@@ -252,17 +252,41 @@ enum : int { PC_INVPHI, PC_INVOM, PC_INVDEN, PC_IB, PC_E, PC_TC, PC_SLOTS };
 constexpr int PC_FIRST_LDS = PC_SLOTS - (MARL_CACHE_LDS_SLOTS < PC_SLOTS ? MARL_CACHE_LDS_SLOTS : PC_SLOTS);
 constexpr int PC_LDS_SLOTS = PC_SLOTS - PC_FIRST_LDS;
 
-template <int STRIDE>   // doubles between the LDS slots of one cell; 0: every slot in registers
+typedef double double2v __attribute__((ext_vector_type(2)));   // two doubles, aligned to 16 bytes: one 128-bit LDS access
+
+// PAIRS (rk4_exchange_kernel only): the four LDS slots as [pair][thread][2] instead of [slot][thread] - (PC_INVDEN, PC_IB) and
+// (PC_E, PC_TC), each pair one 16-byte access (a pitch of 16 bytes: no bank is met twice within the 16 lanes of a pass).  `s` is then the
+// cell's first pair, aligned to 16 bytes, and STRIDE the number of cells.  get / set mean what they mean without it.
+template <int STRIDE, bool PAIRS = false>   // doubles between the LDS slots of one cell; 0: every slot in registers
 struct PointCache {
     static constexpr int FIRST_LDS = STRIDE > 0 ? PC_FIRST_LDS : PC_SLOTS;
+    static_assert(!PAIRS || (STRIDE > 0 && PC_LDS_SLOTS == 4), "two pairs of LDS slots");
     // centre: Phi, O2 = cCa*cCO3; cPhi bounds every porosity expansion variable per unit |Phi - centre|;
     // nib = n/(O2-1): first-order variable of the calcite saturation power (n: the exponent in use)
     double Phi, O2, cPhi, nib;
     double* s;                       // this cell's LDS slots (slot j at s[(j - FIRST_LDS) * STRIDE])
     double v[FIRST_LDS > 0 ? FIRST_LDS : 1];
     bool fv_quiet;                   // wave-uniform: in every lane all three Peclet numbers were < 0.9 PECLET_MIN at the centre
-    __device__ __forceinline__ double get(int j) const { return j < FIRST_LDS ? v[j] : s[(j - FIRST_LDS) * STRIDE]; }
-    __device__ __forceinline__ void set(int j, double x) { if (j < FIRST_LDS) v[j] = x; else s[(j - FIRST_LDS) * STRIDE] = x; }
+    __device__ __forceinline__ double get(int j) const
+    {
+        if constexpr (PAIRS) {   // (the pair as ONE 16-byte read; the second get of a pair is the same read, and is merged with the first)
+            if (j >= FIRST_LDS) return reinterpret_cast<const double2v*>(s + ((j - FIRST_LDS) / 2) * 2 * STRIDE)[0][(j - FIRST_LDS) % 2];
+        }
+        return j < FIRST_LDS ? v[j] : s[(j - FIRST_LDS) * STRIDE];
+    }
+    __device__ __forceinline__ void set(int j, double x)
+    {
+        if constexpr (PAIRS) {
+            if (j >= FIRST_LDS) { s[((j - FIRST_LDS) / 2) * 2 * STRIDE + (j - FIRST_LDS) % 2] = x; return; }
+        }
+        if (j < FIRST_LDS) v[j] = x; else s[(j - FIRST_LDS) * STRIDE] = x;
+    }
+    // PAIRS: slots j and j + 1, one pair, as ONE 16-byte store
+    __device__ __forceinline__ void set_pair(int j, double x0, double x1)
+    {
+        static_assert(PAIRS, "set_pair: the paired layout only");
+        reinterpret_cast<double2v*>(s + ((j - FIRST_LDS) / 2) * 2 * STRIDE)[0] = double2v{x0, x1};
+    }
 };
 
 // 10.0 as an fp64 operand of the point evaluation.  The cached modes (the fine-grid kernels) take it from scalar registers: VOP3
@@ -301,9 +325,9 @@ struct PointLocal {
 // RHS flips Newton / step-size decisions.  The fused explicit integrators take the shorter forms (round 3: six
 // instructions less per evaluation - prefactors folded into the saturation terms, rhorat F and DaRi (delta - c) as one fma each, the
 // second-order reciprocal updates as x (1 - x) forms).
-template <int MODE, int STRIDE, bool VD = false, bool LEGACY = false>
+template <int MODE, int STRIDE, bool VD = false, bool LEGACY = false, bool PAIRS = false>   // (PAIRS: deduced from the cache)
 __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask, const HotConsts& K, const DevConsts* __restrict__ C,
-                                            const Tables& T, PointLocal& pl, PointAux& aux, PointCache<STRIDE>& pc, bool& live)
+                                            const Tables& T, PointLocal& pl, PointAux& aux, PointCache<STRIDE, PAIRS>& pc, bool& live)
 {
     static_assert(!LEGACY || MODE == TR_PLAIN, "the legacy operation order is the stand-alone RHS's (no transcendental cache)");
 #ifdef MARL_ABLATE_CORE  // kernel-lab builds only: the skeleton (loads, LDS exchange, barriers, RK combinations)
@@ -415,8 +439,13 @@ __device__ __forceinline__ void point_local(const double (&uc)[NF], bool in_mask
             pc.Phi = Phi; pc.O2 = O2; pc.nib = nsel * ib;
             // |x| = |d| invPhi, |y| = |d| invom, |10 d(1/Phi)| <= 12 |d| invPhi^2, |z| <= 2.2 |d| invPhi invden
             pc.cPhi = fmax(fmax(fabs(invPhi), fabs(invom)), fmax(12.0 * (invPhi * invPhi), 2.2 * fabs(invPhi * invden)));
-            pc.set(PC_INVPHI, invPhi); pc.set(PC_INVOM, invom); pc.set(PC_INVDEN, invden); pc.set(PC_E, ex);
-            pc.set(PC_IB, ib); pc.set(PC_TC, tC);
+            if constexpr (PAIRS) {
+                pc.set(PC_INVPHI, invPhi); pc.set(PC_INVOM, invom);
+                pc.set_pair(PC_INVDEN, invden, ib); pc.set_pair(PC_E, ex, tC);
+            } else {
+                pc.set(PC_INVPHI, invPhi); pc.set(PC_INVOM, invom); pc.set(PC_INVDEN, invden); pc.set(PC_E, ex);
+                pc.set(PC_IB, ib); pc.set(PC_TC, tC);
+            }
             live = true;
         }
     }
